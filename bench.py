@@ -6,11 +6,13 @@ flux, Taylor-Green vortex with exponential forcing, dt = 0.25/nx; BASELINE.md se
 configuration named in ``config.workload`` -- by default C3: k = 2, 1024 x 1024 triangular mesh.
 All state is resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--nx 1024 --degree 2]
+    python bench.py --gpus N --steps K --warmup W [--nx 1024 --degree 2] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0) with the driver's contract plus ``roofline`` (dominant kernel, HIP
 events on the engine's stream) and ``cpu_baseline`` (the numpy/scipy oracle timed on a bounded
-sample of the same workload on this box's host cores, N = 1 only).
+sample of the same workload on this box's host cores, N = 1 only).  ``ms_per_step`` is the wall
+time of one of the K timed steps.  ``--dump-outputs DIR`` writes the fields the last timed step
+computed to DIR (see ``dump_outputs``), so that two builds can be compared output for output.
 
 ``--gpus N`` with N > 1 outside ``torch.distributed.run`` launches the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` started before anything touches
@@ -340,6 +342,28 @@ def lift_kernel_name(eng):
     return {0: "k_edge_lift", 1: "k_edge_lift_pair", 2: "k_edge_lift_mfma"}[eng.kernel_forms()["lift"]]
 
 
+DUMP_SEED = 20240917
+DUMP_MAX_ROWS = 1 << 21  # per array over all ranks: Q (2 values per row) 32 MB + p 16 MB, below 64 MB in all
+
+
+def dump_outputs(eng, out_dir, rank, world):
+    """--dump-outputs: what the timed steps computed, as a caller of the timestepper receives it (solve() returns the
+    velocity Q, shape (n_nodes, 2), and the pressure p), written as float64 DIR/Q.npy and DIR/p.npy.  An array with more
+    rows than DUMP_MAX_ROWS / world keeps a fixed sample of its rows: sorted indices drawn without replacement by a
+    generator seeded with DUMP_SEED, so the same arguments select the same rows in every run and every build.
+    A multi-rank run writes the strip of each rank as <name>_rank<r>.npy."""
+    from incompressibleeulerhdg_amd._lib import HDG_STATE_CURRENT
+
+    Q, p, _ = eng.get_field(HDG_STATE_CURRENT, lam=False)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_ROWS // world
+    for name, a in (("Q", Q), ("p", p)):
+        if a.shape[0] > cap:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], cap, replace=False))]
+        fname = f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"
+        np.save(os.path.join(out_dir, fname), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def alt_stop_rule(build, args, dt, kappa, mp, ssp2_scales, tol="1e-15"):
     """The timed steps once more on a fresh engine with HDG_TRACE_BACKWARD_TOL (read when an engine is built): condensed solves
     stop when their preconditioned residual is below tol * |pressure trace| -- ten units in the last place of the field they
@@ -382,7 +406,11 @@ def main():
     ap.add_argument("--gmres-restart", type=int, default=8)
     ap.add_argument("--tent-solver", type=int, default=None, help="0 GMRES, 1 GMRES cycle + Chebyshev (default: by degree)")
     ap.add_argument("--comm", choices=["rccl", "shm"], default="rccl", help="inter-rank transport for --gpus > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the velocity and pressure of the last timed step to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])
@@ -513,6 +541,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if dist is not None:
         elapsed = reduce_scalar(elapsed, dist.ReduceOp.MAX)
+    if args.dump_outputs:  # before the extra kernel-timing step below advances the state
+        dump_outputs(eng, args.dump_outputs, rank, world)
     sums, cnt = eng.iteration_stats()
     events = eng.solver_events()  # residual replacements / rounding-floor exits of the condensed solves in the timed steps
     launches = eng.launch_stats(reset=True)  # launch census of exactly the timed steps (this rank)

@@ -288,6 +288,48 @@ def test_bench_line_contract(hip_lib):
         assert "alt_stop_rule" not in d  # opt-in only (BENCH_ALT_STOP=1)
 
 
+def test_bench_dump_outputs(hip_lib, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the velocity and pressure of the last timed step as float64 .npy files: the same
+    fields on every run with the same arguments (bit for bit), and the fields the timestepper computes for that workload."""
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from incompressibleeulerhdg_amd import _lib
+    from incompressibleeulerhdg_amd.mesh import UnitSquareMesh
+    from incompressibleeulerhdg_amd.model_problems import TaylorGreen
+    from incompressibleeulerhdg_amd.timesteppers import IncompressibleEulerHDGIMEXSSP2_332
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    k, nx, warmup, steps = 2, 64, 1, 2
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--nx", str(nx), "--degree", str(k), "--steps", str(steps),
+                            "--warmup", str(warmup), "--no-cpu-baseline", "--dump-outputs", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        assert sorted(os.listdir(out)) == ["Q.npy", "p.npy"]
+        dumps.append({name: np.load(out / f"{name}.npy") for name in ("Q", "p")})
+    for name in ("Q", "p"):
+        assert dumps[0][name].dtype == np.float64 and np.all(np.isfinite(dumps[0][name]))
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+    dt, kappa = 0.25 / nx, 0.5
+    ts = IncompressibleEulerHDGIMEXSSP2_332(UnitSquareMesh(nx, nx), k, dt, use_projection_method=True, n_richardson=2)
+    eng = ts._engine
+    mp = TaylorGreen(ts._V_Q, ts._V_p, "exponential", kappa)
+    eng.set_state(ts._V_Q.interpolate(mp.Q_stationary), ts._V_p.interpolate(mp.p_stationary))
+    eng.reconstruct_trace()
+    eng.set_forcing_profile(mp.f_rhs().profile)
+    eng.run_separable(bench.ssp2_scales(warmup, dt, kappa))
+    eng.run_separable(bench.ssp2_scales(steps, dt, kappa, t0=warmup * dt))
+    Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
+    assert dumps[0]["Q"].shape == Q.shape and dumps[0]["p"].shape == p.shape  # small enough to be written whole
+    assert _rel(dumps[0]["Q"], Q) < 1e-10 and _rel(dumps[0]["p"], p) < 1e-10
+
+
 def test_rccl_selftest_loopback(hip_lib):
     """hdg_rccl_selftest: the grouped ncclSend / ncclRecv pattern of a halo exchange (with this rank as both neighbours), an
     all-reduce and an all-gather on a 1-rank RCCL communicator -- the part of the RCCL transport a one-GPU box can run

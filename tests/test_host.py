@@ -270,6 +270,32 @@ def test_bench_watchdog_ends_an_overrunning_phase():
     assert "stuck collective" in r.stderr.decode()
 
 
+def test_bench_dump_outputs_samples_large_fields(tmp_path):
+    """bench.dump_outputs on fields above its bound: float64 files of 64 MB at most, a sorted sample of distinct rows that is
+    the same on every call, whole arrays when they fit, one file per array and rank."""
+    import bench
+
+    class FakeEngine:
+        def get_field(self, which, Q=True, p=True, lam=True):
+            rows = np.arange(3_000_000, dtype=np.float64)  # row i of Q holds (i, -i)
+            return np.stack([rows, -rows], axis=1), 0.5 * np.arange(1_000_000, dtype=np.float64), None
+
+    def dump(name, rank=0, world=1):
+        bench.dump_outputs(FakeEngine(), str(tmp_path / name), rank, world)
+        return {f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+
+    a, b = dump("a"), dump("b")
+    assert sorted(a) == ["Q.npy", "p.npy"]
+    Q, p = a["Q.npy"], a["p.npy"]
+    assert Q.dtype == np.float64 and p.dtype == np.float64
+    assert Q.shape == (bench.DUMP_MAX_ROWS, 2) and np.all(np.diff(Q[:, 0]) > 0) and np.array_equal(Q[:, 1], -Q[:, 0])
+    assert np.array_equal(p, 0.5 * np.arange(1_000_000))
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in a) <= 64 << 20
+    r = dump("r", rank=1, world=2)
+    assert sorted(r) == ["Q_rank1.npy", "p_rank1.npy"] and r["Q_rank1.npy"].shape == (bench.DUMP_MAX_ROWS // 2, 2)
+
+
 def test_unit_disk_mesh_and_general_mesh_output(tmp_path):
     """Product-side UnitDiskMesh (driver.py:184-185) and the VTK writer on a general triangulation (host side only)."""
     from incompressibleeulerhdg_amd.mesh import Function, FunctionSpace, TriangleMesh, UnitDiskMesh
