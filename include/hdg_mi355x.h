@@ -83,6 +83,11 @@ typedef struct hdg_config {
    * of the square (0 means 1: UnitSquareMesh, driver.py:181) */
   int periodic;
   double length;
+  /* outer FGMRES of the implicit DG step (hdg_dg_implicit_step): relative residual (0 means 1e-10), restart length
+   * (0 means 30) and iteration limit (0 means 2000) */
+  double dg_rtol;
+  int dg_restart;
+  int dg_maxit;
 } hdg_config;
 
 typedef struct hdg_handle hdg_handle;
@@ -175,6 +180,20 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales);
  * monolithic according to cfg.use_projection; forcing slot 0 holds f(t_k) */
 int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure);
 
+/* ---- implicit DG discretisation, spaces [DG_{k+1}]^2 x DG_k (IncompressibleEulerDGImplicit, dg_implicit.py:10-136).
+ * Same handle as the first-order implicit HDG stepper (nstages = 1, forcing slot 0 holds f(t_k)); the trace arrays of
+ * the handle are not used.  Single rank only: a distributed handle returns HDG_ERR_UNSUPPORTED.
+ * hdg_dg_implicit_step: one step of dg_implicit.py:116-134 (BDM projection of Q, the coupled (u, phi) solve by flexible
+ * GMRES from a zero guess, Q <- u, p <- phi - mean; the tracer like hdg_implicit_step).  *its = outer iterations. */
+int hdg_dg_implicit_step(hdg_handle* h, int* its);
+/* test hooks, nodal in / nodal out like hdg_apply_advection (outputs are mapped back through the mass matrices):
+ * out = K (u, p) of dg_implicit.py:48-71 for the given BDM velocity Qstar and step dt:
+ *   out_u = u - dt M^-1 F(Q*) u - dt M^-1 B^T p,   out_p = dt M^-1 B u   (B: the weak divergence, non-broken)
+ * and lam = avg(p) in DGT_k (interior edges: mean of the two sides' traces; boundary edges: the one-sided trace). */
+int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
+                          double* out_p);
+int hdg_dg_avg_trace(hdg_handle* h, const double* p, double* lam);
+
 /* iteration statistics accumulated since the last reset (hdg_imex.py:90-93,648-658):
  * sums[4] / counts[4] for tentative, pressure, final pressure, pressure reconstruction */
 int hdg_get_iteration_stats(hdg_handle* h, double* sums, long* counts, int reset);
@@ -196,7 +215,7 @@ int hdg_get_solver_events(hdg_handle* h, long* events, int reset);
  * step), so hdg_step / hdg_run_separable report the same per-solve breakdown as the per-solve calls.  For each label
  * total_ms[i], sumsq_ms[i] (sum of squares, for the standard deviation log_summary prints) and ncalls[i] since the
  * last reset. */
-#define HDG_N_TIMERS 9
+#define HDG_N_TIMERS 10
 int hdg_get_timers(hdg_handle* h, double* total_ms, double* sumsq_ms, long* ncalls, int reset);
 /* Labels 5 .. 8 (no reference counterpart; the measurement SURVEY.md section 8(d) asks for): every launch of the two
  * kernels of a tentative-velocity iteration inside a solver, by FORM -- 5: advection operator in residual form
@@ -205,6 +224,7 @@ int hdg_get_timers(hdg_handle* h, double* total_ms, double* sumsq_ms, long* ncal
  * own event pair IN PLACE, i.e. with the operands and cache state of the solve.  Recorded only while switched on (two event
  * records per launch: about 1 % of a C3 step). */
 int hdg_set_kernel_timing(hdg_handle* h, int on);
+/* Label 9 (dg_implicit_solve): the (u, phi) solve of hdg_dg_implicit_step (dg_implicit.py:126). */
 /* Transport of a distributed handle as the transport itself reports it: this rank, the number of ranks of the strip
  * partition, the size of the communicator (RCCL: ncclCommCount; must equal nranks) and its name ("self", "rccl", "shm";
  * name16: at least 16 bytes).  No reference counterpart (the reference has no explicit communication). */

@@ -68,6 +68,9 @@ class hdg_config(C.Structure):
         ("device", C.c_int),
         ("periodic", C.c_int),
         ("length", C.c_double),
+        ("dg_rtol", C.c_double),
+        ("dg_restart", C.c_int),
+        ("dg_maxit", C.c_int),
     ]
 
 
@@ -120,6 +123,9 @@ SIGNATURES = {
     "hdg_step": [_h],
     "hdg_run_separable": [_h, C.c_int, _dp],
     "hdg_implicit_step": [_h, _ip, _ip],
+    "hdg_dg_implicit_step": [_h, _ip],
+    "hdg_apply_dg_operator": [_h, _dp, _dp, _dp, C.c_double, _dp, _dp],
+    "hdg_dg_avg_trace": [_h, _dp, _dp],
     "hdg_get_iteration_stats": [_h, _dp, _lp, C.c_int],
     "hdg_get_solver_events": [_h, _lp, C.c_int],
     "hdg_get_kernel_forms": [_h, _ip],
@@ -231,6 +237,11 @@ class Engine:
         cfg.device = int(kw.get("device", 0))
         cfg.periodic = 1 if kw.get("periodic", False) else 0
         cfg.length = float(kw.get("length", 1.0))
+        # outer FGMRES of the implicit DG step (same tolerance as the unsplit HDG solves).  The outer iteration count grows
+        # like 1 / h: with restarts of 30 the solve stagnates on 64^2 at k = 1, hence the long cycles
+        cfg.dg_rtol = float(kw.get("dg_rtol", 1e-10))
+        cfg.dg_restart = int(kw.get("dg_restart", 100))
+        cfg.dg_maxit = int(kw.get("dg_maxit", 3000))
         self.cfg = cfg
         self.h = _h()
         self.rank, self.nranks = int(kw.get("rank", 0)), int(kw.get("nranks", 1))
@@ -364,6 +375,26 @@ class Engine:
         self._ck(self.lib.hdg_implicit_step(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def dg_implicit_step(self):
+        """One step of the implicit DG discretisation (hdg_dg_implicit_step); returns the outer iterations."""
+        its = C.c_int()
+        self._ck(self.lib.hdg_dg_implicit_step(self.h, C.byref(its)))
+        return its.value
+
+    def apply_dg_operator(self, Qstar, u, p, dt):
+        """(out_u, out_p) = the DG operator of dg_implicit.py:48-71 applied to (u, p), mapped back through the mass matrices."""
+        Qstar, u, p = _arr(Qstar, self.shape_Q), _arr(u, self.shape_Q), _arr(p, self.shape_p)
+        ou, op = np.empty(self.shape_Q), np.empty(self.shape_p)
+        self._ck(self.lib.hdg_apply_dg_operator(self.h, _ptr(Qstar), _ptr(u), _ptr(p), float(dt), _ptr(ou), _ptr(op)))
+        return ou, op
+
+    def dg_avg_trace(self, p):
+        """avg(p) in DGT_k (nodal trace layout)."""
+        p = _arr(p, self.shape_p)
+        lam = np.empty(self.shape_l)
+        self._ck(self.lib.hdg_dg_avg_trace(self.h, _ptr(p), _ptr(lam)))
+        return lam
+
     def iteration_stats(self, reset=False):
         sums = np.zeros(4)
         cnt = np.zeros(4, dtype=np.int64)
@@ -439,16 +470,20 @@ class Engine:
     TIMER_LABELS = ("timestep", "bdm_projection", "tentative_velocity_solve", "pressure_solve", "unsplit_solve")
     # hdg_set_kernel_timing; no reference counterpart: the two kernels of a tentative-velocity iteration by form
     KERNEL_TIMER_LABELS = ("kernel_advection", "kernel_lift", "kernel_advection_plain", "kernel_lift_plain")
+    # label 9: the (u, phi) solve of the implicit DG step; reported once it has been called
+    DG_TIMER_LABELS = ("dg_implicit_solve",)
 
     def timers(self, reset=False, kernels=False):
         """Device-side section timers (labels of the reference's PerformanceLog): {label: (ncall, total_s, sumsq_s2)};
         kernels=True adds the per-launch brackets of the two kernels of a tentative-velocity iteration."""
-        n = 9  # HDG_N_TIMERS
+        n = 10  # HDG_N_TIMERS
         tot, sq = np.zeros(n), np.zeros(n)
         cnt = np.zeros(n, dtype=np.int64)
         self._ck(self.lib.hdg_get_timers(self.h, _ptr(tot), _ptr(sq), cnt.ctypes.data_as(_lp), 1 if reset else 0))
-        labels = self.TIMER_LABELS + (self.KERNEL_TIMER_LABELS if kernels else ())
-        return {lab: (int(c), t * 1e-3, q * 1e-6) for lab, c, t, q in zip(labels, cnt, tot, sq)}
+        labels = self.TIMER_LABELS + self.KERNEL_TIMER_LABELS + self.DG_TIMER_LABELS
+        out = {lab: (int(c), t * 1e-3, q * 1e-6) for lab, c, t, q in zip(labels, cnt, tot, sq)}
+        return {lab: v for lab, v in out.items()
+                if (lab not in self.KERNEL_TIMER_LABELS or kernels) and (lab not in self.DG_TIMER_LABELS or v[0] > 0)}
 
     LAUNCH_CLASSES = ("advection_apply", "edge_lift", "stage_rhs", "weak_divergence", "condense", "trace_apply", "trace_smooth",
                       "backsub", "vertex_multigrid", "vector_update", "dot", "copy_fill", "other")

@@ -150,7 +150,8 @@ struct Engine {
   // in place (same operands, same cache state as in the solve): what bench.py's roofline block divides by.
   // Round 4: one label per FORM (the s-step tail makes the plain forms the more frequent ones at k >= 2): T_KADV = residual form
   // b - A x, T_KLIFT = lift with the fused Chebyshev step, T_KADV_PLAIN / T_KLIFT_PLAIN = the forms GMRES and the s-step cycles use.
-  enum { T_STEP = 0, T_BDM = 1, T_TENT = 2, T_PRESS = 3, T_UNSPLIT = 4, T_KADV = 5, T_KLIFT = 6, T_KADV_PLAIN = 7, T_KLIFT_PLAIN = 8 };
+  enum { T_STEP = 0, T_BDM = 1, T_TENT = 2, T_PRESS = 3, T_UNSPLIT = 4, T_KADV = 5, T_KLIFT = 6, T_KADV_PLAIN = 7, T_KLIFT_PLAIN = 8,
+         T_DG = 9 /* the (u, phi) solve of the implicit DG step */ };
   double tm_total[HDG_N_TIMERS] = {0}, tm_sumsq[HDG_N_TIMERS] = {0};
   long tm_calls[HDG_N_TIMERS] = {0};
   struct Section { int label; hipEvent_t e0, e1; };
@@ -3544,42 +3545,56 @@ struct Engine {
     axpby(NPv, 0.0, z.p, 1.0 / gamma, z.p);
     axpby(NLv, 0.0, z.l, 1.0 / gamma, z.l);
   }
-  // flexible GMRES(m); x holds the initial guess; convergence on ||b - K x|| relative to its initial value
+  // flexible GMRES(m) of the unsplit solves; x holds the initial guess
   int fgmres(const double* qstar, double gamma, int didx, int psidx, const V3& b, V3& x) {
-    const int m = std::max(1, cfg.unsplit_restart);
-    if ((int)fg_V.size() < m + 1) {
-      while ((int)fg_V.size() < m + 1) fg_V.push_back(alloc3());
-      while ((int)fg_Z.size() < m) fg_Z.push_back(alloc3());
-      fg_r = alloc3(); fg_w = alloc3();
+    return fgmres_blocks(
+        [&](const V3& in, V3& out) { mono_apply(in, qstar, gamma, out); },
+        [&](const V3& in, V3& out) { mono_precond(in, qstar, gamma, didx, psidx, out); }, b, x, fg_V, fg_Z, fg_r, fg_w,
+        std::max(1, cfg.unsplit_restart), cfg.unsplit_rtol, cfg.unsplit_maxit, "unsplit FGMRES");
+  }
+  // block-vector operations of fgmres_blocks: (u, phi, lambda) of the HDG systems, (u, phi) of the DG system
+  void alloc_block(V3& v) { v = alloc3(); }
+  double dot_block(const V3& a, const V3& b) { return dot3(a, b); }
+  void axpby_block(double a, const V3& x, double b, V3& y) { axpby3(a, x, b, y); }
+  void copy_block(V3& d, const V3& s_) { copy3(d, s_); }
+  // right-preconditioned flexible GMRES(m) on block vectors V, restarted; x holds the initial guess; convergence on
+  // ||b - K x|| relative to its initial value, confirmed with the true residual (the preconditioner's inner solves are
+  // inexact).  apply(x, out): out = K x;  precond(r, z): z ~ K^-1 r.  Vb / Zb / r / w: the caller's basis and work vectors.
+  template <class V, class Apply, class Precond>
+  int fgmres_blocks(Apply&& apply, Precond&& precond, const V& b, V& x, std::vector<V>& Vb, std::vector<V>& Zb, V& r, V& w,
+                    int m, double rtol, int maxit, const char* name) {
+    if ((int)Vb.size() < m + 1) {
+      while ((int)Vb.size() < m + 1) { Vb.emplace_back(); alloc_block(Vb.back()); }
+      while ((int)Zb.size() < m) { Zb.emplace_back(); alloc_block(Zb.back()); }
+      alloc_block(r); alloc_block(w);
     }
-    const double rtol = cfg.unsplit_rtol;
     std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), gv(m + 1);
     int its = 0;
     double beta0 = -1.0;
     while (true) {
-      mono_apply(x, qstar, gamma, fg_r);
-      axpby3(1.0, b, -1.0, fg_r);
-      double beta = std::sqrt(dot3(fg_r, fg_r));
+      apply(x, r);
+      axpby_block(1.0, b, -1.0, r);
+      double beta = std::sqrt(dot_block(r, r));
       if (beta0 < 0) beta0 = beta;
-      if (!(beta == beta)) throw NotConverged{"unsplit FGMRES: NaN residual"};
+      if (!(beta == beta)) throw NotConverged{std::string(name) + ": NaN residual"};
       if (beta <= rtol * beta0 || beta == 0.0) return its;
-      copy3(fg_V[0], fg_r);
-      axpby3(0.0, fg_r, 1.0 / beta, fg_V[0]);
+      copy_block(Vb[0], r);
+      axpby_block(0.0, r, 1.0 / beta, Vb[0]);
       std::fill(gv.begin(), gv.end(), 0.0);
       gv[0] = beta;
       int j = 0;
       bool done = false;
       for (; j < m; j++) {
-        mono_precond(fg_V[j], qstar, gamma, didx, psidx, fg_Z[j]);
-        mono_apply(fg_Z[j], qstar, gamma, fg_w);
+        precond(Vb[j], Zb[j]);
+        apply(Zb[j], w);
         for (int l = 0; l <= j; l++) {  // modified Gram-Schmidt
-          double h = dot3(fg_w, fg_V[l]);
+          double h = dot_block(w, Vb[l]);
           H[(size_t)l * m + j] = h;
-          axpby3(-h, fg_V[l], 1.0, fg_w);
+          axpby_block(-h, Vb[l], 1.0, w);
         }
-        double hn = std::sqrt(dot3(fg_w, fg_w));
+        double hn = std::sqrt(dot_block(w, w));
         H[(size_t)(j + 1) * m + j] = hn;
-        if (hn > 0) { copy3(fg_V[j + 1], fg_w); axpby3(0.0, fg_w, 1.0 / hn, fg_V[j + 1]); }
+        if (hn > 0) { copy_block(Vb[j + 1], w); axpby_block(0.0, w, 1.0 / hn, Vb[j + 1]); }
         for (int l = 0; l < j; l++) {
           double a1 = H[(size_t)l * m + j], a2 = H[(size_t)(l + 1) * m + j];
           H[(size_t)l * m + j] = cs[l] * a1 + sn[l] * a2;
@@ -3595,7 +3610,7 @@ struct Engine {
         gv[j] = cs[j] * gv[j];
         its++;
         if (std::fabs(gv[j + 1]) <= rtol * beta0 || hn == 0.0) { j++; done = true; break; }
-        if (its >= cfg.unsplit_maxit) { j++; break; }
+        if (its >= maxit) { j++; break; }
       }
       std::vector<double> y(j, 0.0);
       for (int l = j - 1; l >= 0; l--) {
@@ -3603,14 +3618,14 @@ struct Engine {
         for (int q = l + 1; q < j; q++) acc -= H[(size_t)l * m + q] * y[q];
         y[l] = acc / H[(size_t)l * m + l];
       }
-      for (int l = 0; l < j; l++) axpby3(y[l], fg_Z[l], 1.0, x);
+      for (int l = 0; l < j; l++) axpby_block(y[l], Zb[l], 1.0, x);
       if (done) {
         // confirm with the true residual (the inner solves are inexact)
-        mono_apply(x, qstar, gamma, fg_r);
-        axpby3(1.0, b, -1.0, fg_r);
-        if (std::sqrt(dot3(fg_r, fg_r)) <= 10.0 * rtol * beta0) return its;
+        apply(x, r);
+        axpby_block(1.0, b, -1.0, r);
+        if (std::sqrt(dot_block(r, r)) <= 10.0 * rtol * beta0) return its;
       }
-      if (its >= cfg.unsplit_maxit) throw NotConverged{"unsplit FGMRES reached max iterations"};
+      if (its >= maxit) throw NotConverged{std::string(name) + " reached max iterations"};
     }
   }
   // stage i of the IMEX scheme without the projection method (hdg_imex.py:600-620)
@@ -3777,6 +3792,118 @@ struct Engine {
     if (its_t) *its_t = it1;
     if (its_p) *its_p = it2;
     tracer_end();
+  }
+
+  // ================================================================== implicit DG discretisation (dg_implicit.py:10-136)
+  // Spaces [DG_{k+1}]^2 x DG_k (the HDG spaces without the trace).  With A = I - dt F(Q*) (F: the HDG f_impl, alpha = 1)
+  // the system of dg_implicit.py:48-75 is
+  //     [ A      -dt B^T ] [u  ]   [ Q + dt f ]          B = weak_div(., broken = false)  (hdg_imex.py:353-365)
+  //     [ dt B    0      ] [phi] = [ 0        ]          B^T phi = g(w; phi, avg(phi))  (pgrad with lambda = avg(phi))
+  // Solved with the continuity rows scaled by 1/dt for y = dt phi:  K_dg (u, y) = (A u - g(y, avg y), B u).
+  // K_dg is singular and consistent (phi = const: B^T 1 = 0; the continuity rows sum to zero): GMRES on the consistent
+  // system, then phi is shifted to zero mean like the reference does after MUMPS (dg_implicit.py:130).
+  // Preconditioner (block triangular, right): u~ = A^-1 r_u (inexact GMRES), then the Schur complement B A^-1 B^T is
+  // replaced by the hybridised mixed Poisson operator at tau' = tau / dt (condense / trace CG / back-substitution, as in
+  // mono_precond without the trace rows): K_mp (du, y, lambda) = (0, r_p - B u~, 0), u = u~ + du.
+  struct V2 { double *u, *p; };
+  std::vector<V2> dg_V, dg_Z;
+  V2 dg_r{nullptr, nullptr}, dg_w{nullptr, nullptr}, dg_b{nullptr, nullptr}, dg_x{nullptr, nullptr};
+  double *dg_lam = nullptr, *dg_lam2 = nullptr, *dg_rp = nullptr, *dg_du = nullptr;
+  const int* dg_ecl = nullptr;  // general meshes: (3 c + l) of the cells of every edge (k_g_dg_avg_trace)
+  // EXPERIMENT (HDG_DG_CC = c, read when an engine is built; default 0 = off): Cahouet-Chabard-type term of the Schur
+  // approximation, S^-1 ~ P_HDG^-1 + c dt alpha / h M_p^-1 (M_p = I in the orthonormal basis), structured meshes
+  const double dg_cc = std::getenv("HDG_DG_CC") ? std::atof(std::getenv("HDG_DG_CC")) : 0.0;
+  void alloc_block(V2& v) { v = V2{dalloc(NQ), dalloc(NPv)}; }
+  double dot_block(const V2& a, const V2& b) { return dot(NQ, a.u, b.u, KQ) + dot(NPv, a.p, b.p, KC); }
+  void axpby_block(double a, const V2& x, double b, V2& y) { axpby(NQ, a, x.u, b, y.u); axpby(NPv, a, x.p, b, y.p); }
+  void copy_block(V2& d, const V2& s_) { copy(d.u, s_.u, NQ); copy(d.p, s_.p, NPv); }
+  void dg_alloc() {
+    if (dg_lam) return;
+    if (comm->size > 1) throw std::string("DG discretisation: single rank only");
+    dg_lam = dalloc(NLv); dg_lam2 = dalloc(NLv); dg_rp = dalloc(NPv); dg_du = dalloc(NQ);
+    alloc_block(dg_b); alloc_block(dg_x);
+    if (general) {
+      std::vector<int> ecl((size_t)2 * gm->ne, -1);
+      for (int e = 0; e < gm->ne; e++)
+        for (int sd = 0; sd < 2; sd++) {
+          const int c = gm->ecell[2 * (size_t)e + sd];
+          if (c >= 0) ecl[2 * (size_t)e + sd] = 3 * c + gm->elocal[2 * (size_t)e + sd];
+        }
+      dg_ecl = upload_ints(ecl);
+    }
+  }
+  // lam = avg(p) in DGT_k (k_dg_avg_trace / k_g_dg_avg_trace)
+  void avg_trace(const double* p, double* lam) {
+    tally(LC_OTHER, bP() + bL());
+    if (general) {
+      if (!g_nref) { csr(gd.Rp, p, 1.0, 0.0, lam); return; }  // HDG_GENERAL_CSR_LIFT: the assembled form of the same map
+      dg_alloc();
+      HDG_DISPATCH(k_g_dg_avg_trace<KK><<<(gm->ne + 63) / 64, 64, 0, stream>>>(ggeo, gm->ne, dg_ecl, g_nref, p, lam));
+      return;
+    }
+    halo_P(p);
+    HDG_DISPATCH(k_dg_avg_trace<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, p, lam));
+  }
+  void dg_apply(const V2& x, const double* qstar, double dtt, V2& out) {
+    adv_apply(x.u, qstar, wQ1, dtt);
+    avg_trace(x.p, dg_lam);
+    pgrad(wQ1, 1.0, nullptr, 0.0, x.p, dg_lam, -1.0, out.u);
+    weak_div(x.u, 1.0, out.p, false);
+  }
+  void dg_precond(const V2& r, const double* qstar, double dtt, int psidx, V2& z) {
+    zero(z.u, NQ);
+    gmres(qstar, dtt, 0, r.u, z.u, cfg.unsplit_inner_rtol, 200, false);
+    weak_div(z.u, 1.0, dg_rp, false);
+    axpby(NPv, 1.0, r.p, -1.0, dg_rp);  // r_p - B u~
+    use_pset(psidx);
+    condense(nullptr, dg_rp, nullptr, wL1);
+    zero(dg_lam2, NLv);
+    trace_cg(wL1, dg_lam2, cfg.unsplit_inner_rtol, 200, false);
+    backsub(nullptr, dg_rp, dg_lam2, dg_du, z.p);
+    use_pset(0);
+    axpby(NQ, 1.0, dg_du, 1.0, z.u);
+    if (dg_cc != 0.0 && !general) axpby(NPv, dg_cc * dtt * cfg.alpha_penalty / g.h, dg_rp, 1.0, z.p);
+  }
+  // K_dg (u, y) = b; x holds the initial guess
+  int dg_solve(const double* qstar, double dtt, const V2& b, V2& x) {
+    dg_alloc();
+    ensure_dinv(0, dtt);
+    const int ps = get_pset(cfg.tau / dtt);
+    const int m = cfg.dg_restart > 0 ? cfg.dg_restart : 30;
+    return fgmres_blocks(
+        [&](const V2& in, V2& out) { dg_apply(in, qstar, dtt, out); },
+        [&](const V2& in, V2& out) { dg_precond(in, qstar, dtt, ps, out); }, b, x, dg_V, dg_Z, dg_r, dg_w, m,
+        cfg.dg_rtol > 0.0 ? cfg.dg_rtol : 1e-10, cfg.dg_maxit > 0 ? cfg.dg_maxit : 2000, "DG FGMRES");
+  }
+  // one step of dg_implicit.py:116-134 (slot-0 forcing at the start of the step, as implicit_step)
+  void dg_implicit_step(int* its) {
+    dg_alloc();
+    Timed tm_(*this, T_STEP);
+    const double dtt = cfg.dt;
+    if (tracer_on) {  // dg_implicit.py:117-120: b_tracer is built from the fields at the START of the step
+      cg_project(curQ, uproj);
+      tracer_adv(q_cur, uproj, q_t);
+    }
+    { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
+    lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
+    zero(dg_b.p, NPv);
+    zero(dg_x.u, NQ); zero(dg_x.p, NPv);                             // fresh Function: zero guess
+    int it;
+    { Timed td_(*this, T_DG); it = dg_solve(Qstar[0], dtt, dg_b, dg_x); }  // dg_implicit.py:126
+    copy(curQ, dg_x.u, NQ);                                          // dg_implicit.py:128-130
+    axpby(NPv, 1.0 / dtt, dg_x.p, 0.0, curP);
+    shift(curP, nullptr);
+    it_sum[0] += it; it_cnt[0]++;
+    if (its) *its = it;
+    if (tracer_on) axpby(NPv, dtt, q_t, 1.0, q_cur);  // dg_implicit.py:131-132, after a successful solve only
+  }
+  // operator-level access (hdg_apply_dg_operator): out = K x of dg_implicit.py:48-71 (unscaled rows, phi not y)
+  void dg_operator(const double* qstar, const double* u, const double* p, double dtt, double* out_u, double* out_p) {
+    dg_alloc();
+    adv_apply(u, qstar, wQ4, dtt);
+    avg_trace(p, dg_lam);
+    pgrad(wQ4, 1.0, nullptr, 0.0, p, dg_lam, -dtt, out_u);
+    weak_div(u, dtt, out_p, false);
   }
 
 
@@ -4530,6 +4657,44 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
 int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure) {
   HDG_API_BEGIN(h)
   E.implicit_step(its_tentative, its_pressure);
+  HDG_API_END(h)
+}
+// ---- implicit DG discretisation (dg_implicit.py:10-136), single rank
+static int dg_single_rank(hdg_handle* h) {
+  if (h && h->eng && h->eng->comm && h->eng->comm->size > 1) {
+    h->err = "the DG discretisation runs on one rank only (strip partitions are not supported)";
+    return HDG_ERR_UNSUPPORTED;
+  }
+  return HDG_OK;
+}
+int hdg_dg_implicit_step(hdg_handle* h, int* its) {
+  if (int rc = dg_single_rank(h)) return rc;
+  HDG_API_BEGIN(h)
+  E.dg_implicit_step(its);
+  HDG_API_END(h)
+}
+int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
+                          double* out_p) {
+  if (int rc = dg_single_rank(h)) return rc;
+  HDG_API_BEGIN(h)
+  if (!Qstar || !u || !p || !out_u || !out_p) throw std::string("null argument");
+  E.dg_alloc();
+  E.put_Q(Qstar, E.wQ1);
+  E.put_Q(u, E.wQ2);
+  E.put_P(p, E.wP1);
+  E.dg_operator(E.wQ1, E.wQ2, E.wP1, dt, E.wQ3, E.dg_b.p);
+  E.get_Q(E.wQ3, out_u);
+  E.get_P(E.dg_b.p, out_p);
+  HDG_API_END(h)
+}
+int hdg_dg_avg_trace(hdg_handle* h, const double* p, double* lam) {
+  if (int rc = dg_single_rank(h)) return rc;
+  HDG_API_BEGIN(h)
+  if (!p || !lam) throw std::string("null argument");
+  E.dg_alloc();
+  E.put_P(p, E.wP1);
+  E.avg_trace(E.wP1, E.wL1);
+  E.get_L(E.wL1, lam);
   HDG_API_END(h)
 }
 int hdg_get_iteration_stats(hdg_handle* h, double* sums, long* counts, int reset) {

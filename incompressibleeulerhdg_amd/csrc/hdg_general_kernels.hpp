@@ -358,4 +358,41 @@ __global__ __launch_bounds__(64) void k_g_precon(GGeo G, const double* __restric
   for (int r = 0; r < NP; r++) rp[(long)c * NP + r] = y[r];
 }
 
+// averaged pressure trace of the implicit DG discretisation (k_dg_avg_trace on general meshes): one thread per edge,
+// lambda_e = sum over the (one or two) incident cells of w Pt_{c,l} p_c, w = 1/2 on interior edges and 1 on boundary edges,
+// Pt_{c,l} = sqrt(|e|) / sqrt(det J_c) Nref[l, flip] restricted to the first NL x NP block (cell_edge_blocks).
+// ecl[2 e + side] = 3 c + l of the cells of edge e (-1: no second cell).
+template <int K>
+__global__ __launch_bounds__(64) void k_g_dg_avg_trace(GGeo G, int ne, const int* __restrict__ ecl, const double* __restrict__ Nref,
+                                                       const double* __restrict__ p, double* __restrict__ out) {
+  constexpr int NU = Dim<K>::NU, NP = Dim<K>::NP, NL = Dim<K>::NL, NE = Dim<K>::NE;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= ne) return;
+  const int s0 = ecl[2 * (long)e], s1 = ecl[2 * (long)e + 1];
+  const double w = s1 >= 0 ? 0.5 : 1.0;
+  double acc[NL];
+#pragma unroll
+  for (int a = 0; a < NL; a++) acc[a] = 0.0;
+#pragma unroll
+  for (int side = 0; side < 2; side++) {
+    const int cl = side == 0 ? s0 : s1;
+    if (cl < 0) continue;
+    const int c = cl / 3;
+    const double sc = w * sqrt(G.celen[cl]) * G.inv_sdet[c];
+    const double* __restrict__ Nr = Nref + (long)G.ctab[cl] * NE * NU;
+    double pp[NP];
+#pragma unroll
+    for (int m = 0; m < NP; m++) pp[m] = p[(long)c * NP + m];
+#pragma unroll
+    for (int a = 0; a < NL; a++) {
+      double v = 0.0;
+#pragma unroll
+      for (int m = 0; m < NP; m++) v = fma(Nr[a * NU + m], pp[m], v);
+      acc[a] = fma(sc, v, acc[a]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NL; a++) out[(long)e * NL + a] = acc[a];
+}
+
 }  // namespace hdg

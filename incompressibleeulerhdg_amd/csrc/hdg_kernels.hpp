@@ -1879,6 +1879,40 @@ __global__ __launch_bounds__(128) void k_trace_recon(Geo g, DevTables T, const d
 }
 
 // ------------------------------------------------------------------------------------------
+// averaged pressure trace of the implicit DG discretisation (dg_implicit.py:56-58):
+//   lambda = avg(phi) = (phi+ + phi-) / 2 on interior edges, phi on boundary edges, in DGT_k
+// The trace of a P_k function on an edge lies in P_k, so this is exact, and with it the HDG pressure gradient
+// g(w; phi, avg(phi)) equals the DG one (w.n jumps against avg(phi)).  Same corner threads and edge restriction tables
+// (Pt) as k_trace_recon, pressure part only; entries that are not edges are written as zero.
+// ------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(128) void k_dg_avg_trace(Geo g, DevTables T, const double* __restrict__ p,
+                                                       double* __restrict__ out) {
+  constexpr int NP = Dim<K>::NP, NL = Dim<K>::NL;
+  HDG_CORNER_PROLOGUE
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    const int e = (t == 0) ? 0 : (t == 1 ? 2 : 1);
+    bool valid, hasL, hasU;
+    long cL, cU;
+    if (t == 0) { valid = in_x; hasL = in_y; hasU = below; cL = cidx(g, 0, j, i); cU = cidx(g, 1, j - 1, i); }
+    else if (t == 1) { valid = in_y; hasL = in_x; hasU = left; cL = cidx(g, 0, j, i); cU = cidx(g, 1, j, xm1(g, i)); }
+    else { valid = in_x && in_y; hasL = hasU = true; cL = cidx(g, 0, j, i); cU = cidx(g, 1, j, i); }
+    double acc[NL];
+#pragma unroll
+    for (int m = 0; m < NL; m++) acc[m] = 0.0;
+    if (valid) {
+      const double w = (hasL && hasU) ? 0.5 : 1.0;
+      double pp[NP];
+      if (hasL) { load_cell<NP>(p, g.Nc, cL, pp); mv_acc_ld<NL, NP>(T.Pt[0][e], NP, pp, acc, w); }
+      if (hasU) { load_cell<NP>(p, g.Nc, cU, pp); mv_acc_ld<NL, NP>(T.Pt[1][e], NP, pp, acc, w); }
+    }
+#pragma unroll
+    for (int m = 0; m < NL; m++) out[((long)t * NL + m) * g.G + o] = acc[m];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // pressure-reconstruction right-hand side (hdg_imex.py:201-207):
 //   rp = weak_divergence(psi, v),  v = -b + (Q.grad)Q  (per cell: -(grad psi, v)_K + <psi,{{v}}.n>_int)
 //   rl = - int_{dOmega} mu n.b    (boundary edges only; interior entries zero)

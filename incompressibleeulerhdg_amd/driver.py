@@ -4,7 +4,8 @@
 
 ``--problem taylorgreen`` (unit square), ``--problem shear`` (doubly periodic square, driver.py:182-183) and
 ``--problem kelvinhelmholtz`` (UnitDiskMesh(refinement), driver.py:184-185: the general-mesh path, projection and monolithic)
-are built; the ``conforming`` / ``dg`` discretisations raise.  ``--animation`` (evolution.pvd with
+are built with the ``hdg`` discretisation and, with ``--timestepper implicit``, the ``dg`` one (IncompressibleEulerDGImplicit,
+driver.py:203-213); the ``conforming`` discretisation raises.  ``--animation`` (evolution.pvd with
 the CG vorticity, callbacks.py:30-85) and ``--tracer_advection`` (driver.py:340-344) work on every mesh.  The final fields are written to ``solution.pvd``
 (``--output``) like the reference does (driver.py:356-385).
 """
@@ -25,6 +26,7 @@ from .timesteppers import (
     IncompressibleEulerHDGIMEXImplicit,
     IncompressibleEulerHDGIMEXSSP2_332,
     IncompressibleEulerHDGIMEXSSP3_433,
+    IncompressibleEulerDGImplicit,
     IncompressibleEulerHDGImplicit,
 )
 
@@ -68,7 +70,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.discretisation != "hdg":
+    if args.discretisation == "conforming":
         raise RuntimeError(f"discretisation '{args.discretisation}' is out of scope of the MI355X hot path")
     callbacks = [AnimationCallback("evolution.pvd")] if args.animation else None  # driver.py:187
     if args.problem == "shear":
@@ -77,7 +79,14 @@ def main(argv=None):
         mesh = UnitDiskMesh(refinement_level=args.refinement)  # driver.py:184-185
     else:
         mesh = UnitSquareMesh(args.nx, args.nx, quadrilateral=False)  # driver.py:181
-    if args.timestepper == "implicit":
+    if args.discretisation == "dg":
+        # driver.py:203-213
+        assert not args.use_projection_method, "Can not use projection method with DG discretsation"
+        if args.timestepper != "implicit":
+            raise RuntimeError(f"Invalid timestepping method for DG discretisation: '{args.timestepper}'")
+        timestepper = IncompressibleEulerDGImplicit(mesh, args.degree, args.dt, flux=args.flux, callbacks=callbacks,
+                                                    device=args.device)
+    elif args.timestepper == "implicit":
         timestepper = IncompressibleEulerHDGImplicit(  # driver.py:220-228 (passes n_richardson: SURVEY C-1)
             mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
             n_richardson=args.richardson, callbacks=callbacks, device=args.device)
@@ -114,7 +123,7 @@ def main(argv=None):
     if args.test_pressure_solver:
         # working equivalent of driver.py:308-324 (the reference's call is stale, SURVEY C-4): random
         # velocity-row right-hand side with seed 123456789, untimed first solve, timed second solve
-        if args.timestepper == "implicit":
+        if args.timestepper == "implicit" or args.discretisation == "dg":
             raise RuntimeError("--test_pressure_solver needs an IMEX timestepper")
         rng = np.random.default_rng(123456789)
         f_Q = rng.standard_normal(eng.shape_Q)
