@@ -1,9 +1,18 @@
 // CPU check of the host side of the general-mesh path (no GPU, no HIP): topology, assembled operators, P1 coarse space,
-// smoothed-aggregation hierarchy, continuous space.  Reads "nv nc / coords / cells" from argv[1], degree from argv[2];
-// prints "name value" lines that tests/test_host.py asserts on.  Compiled with g++ by the test.
+// smoothed-aggregation hierarchy, continuous space, repeatability of the threaded per-cell assembly.  Reads
+// "nv nc / coords / cells" from argv[1], degree from argv[2]; prints "name value" lines that tests/test_host.py asserts on.
+// argv[3] == "rows": only the average row length ("rowlen_<operator> <nnz / nrows>") of every operator the engine uploads
+// with upload_csr (hdg_engine.hip), for the default hierarchy (HDG_AMG_MAX_COARSE unset); not printed: the inverse diagonals
+// of the unfused smoother (one entry per row on every mesh) and the tau' copies of the trace operators (the same sparsity as
+// the tau set).  Also "parallel_for_threads": how many threads parallel_for used on the mesh.  Compiled with g++ by the test.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <set>
+#include <thread>
+#include <string>
 #include <vector>
 
 #include "../../incompressibleeulerhdg_amd/csrc/hdg_amg.hpp"
@@ -33,6 +42,19 @@ static double asym(const Csr& A) {  // max |A - A^T|
   return m;
 }
 
+static bool same_bits(const dvec& a, const dvec& b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
+}
+static bool same_csr(const Csr& a, const Csr& b) {
+  return a.nrows == b.nrows && a.ncols == b.ncols && a.rowptr == b.rowptr && a.col == b.col && same_bits(a.val, b.val);
+}
+#define GENERAL_OPS(X)                                                                                                          \
+  X(Pi) X(Wdiv) X(Bdiv) X(Gp) X(Gl) X(Yw) X(Yp) X(S) X(Auu) X(Aup) X(Apu) X(App) X(Wu) X(Wp) X(Dtr) X(Rq) X(Rp) X(Rb)       \
+  X(Psi_p) X(Psi_l) X(Mu_u) X(Mu_p) X(Mu_l) X(Cq) X(Cqi) X(Cp) X(Cpi) X(Cl) X(Cli)
+static void print_rowlen(const char* name, const Csr& A) {
+  std::printf("rowlen_%s %.6f\n", name, A.nrows > 0 ? (double)A.val.size() / A.nrows : 0.0);
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) return 2;
   FILE* f = std::fopen(argv[1], "r");
@@ -53,6 +75,75 @@ int main(int argc, char** argv) {
     std::vector<CellLocal> loc;
     assemble_general(T, M, O, loc);
     std::printf("nv %d\nnc %d\nne %d\nvolume %.15e\n", M.nv, M.nc, M.ne, M.volume);
+    if (argc > 3 && std::string(argv[3]) == "rows") {  // what upload_csr bases the threads per row on
+#define ROWLEN(name) print_rowlen(#name, O.name);
+      GENERAL_OPS(ROWLEN)
+#undef ROWLEN
+      const Csr P0 = p1_to_trace_matrix(T, M), R0 = csr_transpose(P0);
+      print_rowlen("P0", P0);
+      print_rowlen("R0", R0);
+      AmgHierarchy H;
+      amg_build(csr_multiply(R0, csr_multiply(O.S, P0)), H, 2000);  // the engine's default coarsening limit
+      std::printf("amg_levels %d\n", (int)H.lev.size());
+      for (size_t l = 0; l < H.lev.size(); l++) {
+        print_rowlen(("amg_A" + std::to_string(l)).c_str(), H.lev[l].A);
+        if (l + 1 < H.lev.size()) {
+          print_rowlen(("amg_P" + std::to_string(l)).c_str(), H.lev[l].P);
+          print_rowlen(("amg_R" + std::to_string(l)).c_str(), H.lev[l].R);
+        }
+      }
+      if (H.coarse_pinv.nrows > 0) print_rowlen("amg_coarse_pinv", H.coarse_pinv);
+      // element block-Jacobi (HDG_GENERAL_CSR_LIFT / HDG_GENERAL_BLOCK_JACOBI) and the continuous space (cg_setup)
+      print_rowlen("block_jacobi", assemble_block_jacobi(T, M, loc, 0.0375));
+      GeneralCG G;
+      assemble_cg(T, M, O, G);
+      print_rowlen("cg_M", G.M);
+      print_rowlen("cg_Vort", G.Vort);
+      print_rowlen("cg_R", G.R);
+      for (int d = 0; d < 2; d++) {
+        print_rowlen(("cg_Bp" + std::to_string(d)).c_str(), G.Bp[d]);
+        print_rowlen(("cg_Ep" + std::to_string(d)).c_str(), G.Ep[d]);
+      }
+      return 0;
+    }
+    {  // how many threads parallel_for really uses on this mesh (one below 256 cells or on a one-core host)
+      std::mutex mtx;
+      std::set<std::thread::id> ids;
+      parallel_for(M.nc, [&](int) {
+        volatile double w = 0;  // a little work per cell, so that every worker gets to take a chunk
+        for (int i = 0; i < 20000; i++) w = w + 1.0;
+        std::lock_guard<std::mutex> lk(mtx);
+        ids.insert(std::this_thread::get_id());
+      });
+      std::printf("parallel_for_threads %d\n", (int)ids.size());
+    }
+    // the per-cell work runs on several threads above 255 cells (parallel_for): a second assembly of the same mesh, and
+    // of the per-cell tables of k_g_lift and the element block-Jacobi, must reproduce every bit
+    {
+      GeneralOps O2;
+      std::vector<CellLocal> loc2;
+      assemble_general(T, M, O2, loc2);
+      int bad = 0;
+#define SAME(name) if (!same_csr(O.name, O2.name)) { bad++; std::printf("repeat_differs %s\n", #name); }
+      GENERAL_OPS(SAME)
+#undef SAME
+      if (!same_bits(O.one_p, O2.one_p) || !same_bits(O.int_p, O2.int_p) || !same_bits(O.one_l, O2.one_l) || !same_bits(O.xq, O2.xq) ||
+          !same_bits(O.xp, O2.xp)) {
+        bad++;
+        std::printf("repeat_differs vectors\n");
+      }
+      for (const double gamma : {-1.0, 0.0, 0.0375}) {
+        if (!same_bits(assemble_lift_tables(T, M, loc, gamma), assemble_lift_tables(T, M, loc2, gamma))) {
+          bad++;
+          std::printf("repeat_differs lift_tables %g\n", gamma);
+        }
+      }
+      if (!same_csr(assemble_block_jacobi(T, M, loc, 0.0375), assemble_block_jacobi(T, M, loc2, 0.0375))) {
+        bad++;
+        std::printf("repeat_differs block_jacobi\n");
+      }
+      std::printf("repeat_mismatches %d\n", bad);
+    }
     // condensed operator: symmetric, the constants are its kernel
     const double sscale = maxabs(O.S.val);
     std::printf("S_asym %.3e\n", asym(O.S) / sscale);

@@ -7,16 +7,12 @@ Operators at round-off level, whole HDG-IMEX steps at the two-converged-solvers 
 reference's UnitDiskMesh construction is restated from memory on both sides (Firedrake cannot run here): parity unpinned."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
-import scipy.sparse.linalg as spla
+
+from general_mesh_checks import TOL, check_continuous_space_against_oracle, check_operators_against_oracle, smooth_data
+from general_mesh_checks import engine as _engine
+from general_mesh_checks import rel as _rel
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-10
-TOL = 2e-8
-
-
-def _rel(a, b):
-    return np.max(np.abs(np.asarray(a) - np.asarray(b))) / max(np.max(np.abs(b)), 1e-300)
 
 
 def _structured(nx):
@@ -54,80 +50,12 @@ def _mesh(kind):
     return pm, fem.TriMesh(pm.vertices, pm.cells)
 
 
-def _engine(pm, k, dt=0.01, **kw):
-    from incompressibleeulerhdg_amd._lib import Engine
-    from oracle.hdg_oracle import TABLEAUX
-
-    tb = TABLEAUX["imex_ssp2_332"]
-    return Engine(vertices=pm.vertices, cells=pm.cells, degree=k, dt=dt, nstages=3, a_expl=tb["a_expl"], a_impl=tb["a_impl"],
-                  b_expl=tb["b_expl"], b_impl=tb["b_impl"], c_expl=tb["c_expl"], **kw)
-
-
 @pytest.mark.parametrize("kind,k", [("irregular", 1), ("irregular", 2), ("disk1", 2), ("square4", 2), ("disk1", 3), ("irregular", 4)])
 def test_general_mesh_operators(hip_lib, kind, k):
-    from incompressibleeulerhdg_amd import _lib
     from oracle.hdg_oracle import HDGDiscretisation
 
     pm, om = _mesh(kind)
-    d = HDGDiscretisation(0, k, mesh=om)
-    e = _engine(pm, k)
-    assert (e.n_cells, e.n_edges, e.n_u, e.n_p, e.n_l) == (om.ncells, om.nedges, d.nu, d.np_, d.nl)
-    ev, ec = e.general_topology()
-    assert np.array_equal(ev, om.edge_vertices) and np.array_equal(ec[:, 0], om.edge_plus) and np.array_equal(ec[:, 1], om.edge_minus)
-    xq, xp = e.node_coordinates()
-    assert np.allclose(xq, d.node_coords(d.PU).reshape(-1, 2), atol=1e-13) and np.allclose(xp, d.node_coords(d.PP).reshape(-1, 2), atol=1e-13)
-    rng = np.random.default_rng(100 + k)
-    Q, x = rng.standard_normal(e.shape_Q), rng.standard_normal(e.shape_Q)
-    p, lam = rng.standard_normal(e.shape_p), rng.standard_normal(e.shape_l)
-    # conversions, norms, integrals
-    e.set_field(1, Q, p, lam)
-    Q2, p2, l2 = e.get_field(1)
-    assert _rel(Q2, Q) < 1e-12 and _rel(p2, p) < 1e-12 and _rel(l2, lam) < 1e-12
-    nq, npr = e.l2_norms(Q, p)
-    assert abs(nq - d.l2_norm_velocity(Q)) < 1e-11 * nq and abs(npr - d.l2_norm_pressure(p)) < 1e-11 * npr
-    assert abs(e.integrate_pressure(p) - d.int_p @ p) < 1e-12 * max(1.0, abs(d.int_p @ p))
-    # BDM projection (common.py:91-108)
-    assert _rel(e.project_bdm_nodal(Q), d.project_bdm(Q)) < RTOL
-    # advection operator (hdg_imex.py:313-331), both fluxes
-    Qstar = d.project_bdm(Q)
-    gamma = 0.05
-    for flux in ("upwind", "centered"):
-        ef = _engine(pm, k, flux=flux)
-        F = d.assemble_f_impl(Qstar, flux)
-        ref = x.ravel() - gamma * spla.spsolve(d.MQ.tocsc(), F @ x.ravel())
-        assert _rel(ef.apply_advection(Qstar, x, gamma).ravel(), ref) < RTOL, flux
-    # weak / broken divergence
-    Mi = spla.splu(d.MP.tocsc())
-    assert _rel(e.apply_weak_divergence(Q), Mi.solve(d.Wdiv @ Q.ravel())) < RTOL
-    assert _rel(e.apply_weak_divergence(Q, broken=True), Mi.solve(d.Bdiv @ Q.ravel())) < RTOL
-    # condensed trace operator vs the oracle's dense Schur complement
-    n1 = d.NQ + d.NP
-    Kmp = d.K_mp.tocsc()
-    S = Kmp[n1:, n1:].toarray() - Kmp[n1:, :n1] @ spla.splu(Kmp[:n1, :n1].tocsc()).solve(Kmp[n1:, :n1].T.toarray() * 0 + Kmp[:n1, n1:].toarray())
-    mult = np.where(np.repeat(om.interior, d.nl), 2.0, 1.0)
-    Mtr = (sp.diags(1.0 / mult) @ (d.Lm.tocsc() / d.tau)).tocsc()
-    assert _rel(e.apply_trace_operator(lam), spla.spsolve(Mtr, -S @ lam)) < 1e-9
-    assert np.max(np.abs(e.apply_trace_operator(np.ones(e.shape_l)))) < 1e-9
-    # trace reconstruction and the pressure shift
-    e.set_state(Q, p)
-    e.reconstruct_trace()
-    _, p_dev, l_dev = e.get_field(_lib.HDG_STATE_CURRENT)
-    p0 = p - (d.int_p @ p) / om.volume
-    assert _rel(p_dev, p0) < RTOL and _rel(l_dev, d.reconstruct_trace(Q, p0)) < RTOL
-    e.set_field(1, Q, p, lam)
-    e.shift_pressure(1)
-    _, p1, l1 = e.get_field(1)
-    ps, ls = d.shift_pressure(p, lam)
-    assert _rel(p1, ps) < RTOL and _rel(l1, ls) < RTOL
-
-
-def _smooth(seed):
-    rng = np.random.default_rng(seed)
-    a = rng.uniform(-1.0, 1.0, size=(3, 6))
-    Q0 = lambda x, y: (a[0, 0] * np.sin(2 * x + a[0, 1]) * np.cos(1.5 * y) + a[0, 2] * y, a[0, 3] * np.cos(1.7 * x) * np.sin(2 * y + a[0, 4]) + a[0, 5] * x)
-    p0 = lambda x, y: a[1, 0] * np.cos(2 * x + a[1, 1]) * np.sin(1.3 * y + a[1, 2])
-    f = lambda t: (lambda x, y: (a[2, 0] * np.sin(3 * t + x + a[2, 1] * y), a[2, 2] * np.cos(2 * t - y + a[2, 3] * x)))
-    return Q0, p0, f
+    check_operators_against_oracle(pm, om, HDGDiscretisation(0, k, mesh=om), k, seed=100 + k)
 
 
 @pytest.mark.parametrize("kind,k,tableau,R", [("disk1", 1, "imex_ssp2_332", 2), ("irregular", 2, "imex_ssp2_332", 2), ("disk1", 2, "imex_ars3_443", 1),
@@ -145,7 +73,7 @@ def test_general_mesh_whole_steps_on_smooth_random_data(hip_lib, kind, k, tablea
            "imex_ssp3_433": ts_mod.IncompressibleEulerHDGIMEXSSP3_433}[tableau]
     pm, om = _mesh(kind)
     dt, nsteps = 0.02, 2
-    Q0, p0, f = _smooth(7 + k)
+    Q0, p0, f = smooth_data(7 + k)
     d = orc.HDGDiscretisation(0, k, mesh=om)
     o = orc.OracleHDGIMEX(d, dt, tableau, n_richardson=R)
     oQ, op = o.solve(d.interpolate_velocity(Q0), d.interpolate_pressure(p0), lambda t: d.interpolate_velocity(f(t)), nsteps * dt)
@@ -243,7 +171,7 @@ def test_general_mesh_fully_implicit_stepper(hip_lib, kind, k):
 
     pm, om = _mesh(kind)
     dt = 0.02
-    Q0, p0, f = _smooth(21 + k)
+    Q0, p0, f = smooth_data(21 + k)
     d = orc.HDGDiscretisation(0, k, mesh=om)
     oQ, op = orc.OracleHDGImplicit(d, dt).solve(d.interpolate_velocity(Q0), d.interpolate_pressure(p0),
                                                 lambda t: d.interpolate_velocity(f(t)), 2 * dt)
@@ -264,7 +192,7 @@ def test_general_mesh_monolithic_solves(hip_lib, kind, k, stepper):
 
     pm, om = _mesh(kind)
     dt = 0.02
-    Q0, p0, f = _smooth(31 + k)
+    Q0, p0, f = smooth_data(31 + k)
     d = orc.HDGDiscretisation(0, k, mesh=om)
     fo = lambda t: d.interpolate_velocity(f(t))
     if stepper == "implicit":
@@ -289,31 +217,7 @@ def test_general_mesh_continuous_space_and_tracer_operator(hip_lib, kind, k):
 
     pm, om = _mesh(kind)
     d = HDGDiscretisation(0, k, mesh=om)
-    tr = TracerOracle(d)
-    e = _engine(pm, k)
-    assert e.cg_size() == tr.ncg
-    key = lambda X: {tuple(np.round(x * 1e6).astype(np.int64)) for x in X}
-    assert key(e.cg_coordinates()) == key(tr.cg_coords) and len(key(e.cg_coordinates())) == tr.ncg
-    rng = np.random.default_rng(50 + k)
-    u = rng.standard_normal(e.shape_Q)
-    P = e.cg_project_nodal(u)
-    assert _rel(P, tr.cg_project(u)) < 1e-10
-    assert _rel(e.cg_project_nodal(P), P) < 1e-10
-    cont = d.interpolate_velocity(lambda x, y: (x ** (k + 1) - y, x * y ** k + 1.0))
-    assert _rel(e.cg_project_nodal(cont), cont) < 1e-10
-    Q = rng.standard_normal(e.shape_Q)
-    w, xy = tr.vorticity(Q)
-    wd = e.vorticity(Q)
-    order = lambda X: np.lexsort((np.round(X[:, 1] * 1e6), np.round(X[:, 0] * 1e6)))
-    assert _rel(wd[order(e.cg_coordinates())], w[order(xy)]) < 1e-10
-    assert _rel(e.cg_to_broken(wd), tr.R @ w) < 1e-10
-    # rigid rotation (-y, x): vorticity 2 everywhere, also on the polygonal boundary
-    rot = d.interpolate_velocity(lambda x, y: (-y, x))
-    assert np.max(np.abs(e.vorticity(rot) - 2.0)) < 1e-9
-    q = rng.standard_normal(e.shape_p)
-    assert _rel(e.apply_tracer_advection(q, u, project=True), tr.tracer_tendency(q, u)) < 1e-10
-    uc = tr.cg_project(u)
-    assert _rel(e.apply_tracer_advection(q, uc, project=False), tr._lu_mp.solve(tr.tracer_form(q, uc))) < 1e-10
+    check_continuous_space_against_oracle(pm, d, TracerOracle(d), k, seed=50 + k)
 
 
 @pytest.mark.parametrize("kind,k,tableau", [("disk1", 1, "imex_ssp2_332"), ("irregular", 2, "imex_ars3_443"), ("disk1", 2, "implicit")])
@@ -326,7 +230,7 @@ def test_general_mesh_steps_with_tracer(hip_lib, kind, k, tableau):
 
     pm, om = _mesh(kind)
     dt = 0.02
-    Q0, p0, f = _smooth(41 + k)
+    Q0, p0, f = smooth_data(41 + k)
     q0 = lambda x, y: np.sin(1.5 * x + 0.3) * np.cos(1.2 * y) + 0.2 * x
     d = orc.HDGDiscretisation(0, k, mesh=om)
     tr = TracerOracle(d)

@@ -321,33 +321,51 @@ def test_unit_disk_mesh_and_general_mesh_output(tmp_path):
     assert f'NumberOfCells="{m.num_cells()}"' in txt and 'Name="f"' in txt
 
 
-@pytest.mark.parametrize("k,level", [(1, 2), (2, 1), (3, 1)])
-def test_general_mesh_host_side_invariants(tmp_path, k, level):
-    """The host side of the general-mesh path (csrc/hdg_general.hpp, hdg_amg.hpp: plain C++, compiled here with g++, no GPU):
-    condensed operator symmetric with the constants as kernel, BDM projection idempotent, the constraint rows of the
-    monolithic system vanish on constants, the P1 prolongation reproduces constants, every level of the smoothed-aggregation
-    hierarchy keeps symmetry / kernel / partition of unity and gets smaller, the dense pseudo-inverse of the coarsest operator
-    inverts on the range, the continuous space has the mesh's volume, projects constants and gives vorticity 2 for a rotation."""
+def _general_host_check(tmp_path, vertices, cells, k, *extra):
+    """compile tests/host/general_host_check.cpp (once per test) and run it on one mesh: {name: value string}"""
     import shutil
     import subprocess
-
-    from incompressibleeulerhdg_amd.mesh import UnitDiskMesh
 
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")
     exe = tmp_path / "general_host_check"
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "general_host_check.cpp")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-o", str(exe), src], check=True)
-    m = UnitDiskMesh(level)
+    if not exe.exists():
+        src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "general_host_check.cpp")
+        subprocess.run([gxx, "-std=c++17", "-O1", "-pthread", "-o", str(exe), src], check=True)
     with open(tmp_path / "mesh.txt", "w") as f:
-        f.write(f"{len(m.vertices)} {len(m.cells)}\n")
-        np.savetxt(f, m.vertices, fmt="%.17g")
-        np.savetxt(f, m.cells, fmt="%d")
-    out = subprocess.run([str(exe), str(tmp_path / "mesh.txt"), str(k)], check=True, capture_output=True, text=True).stdout
+        f.write(f"{len(vertices)} {len(cells)}\n")
+        np.savetxt(f, vertices, fmt="%.17g")
+        np.savetxt(f, cells, fmt="%d")
+    out = subprocess.run([str(exe), str(tmp_path / "mesh.txt"), str(k), *extra], check=True, capture_output=True, text=True).stdout
     v = {ln.split()[0]: ln.split()[1] for ln in out.strip().splitlines()}
     assert "error" not in v, out
+    return v
+
+
+@pytest.mark.parametrize("k,level", [(1, 2), (2, 1), (3, 1), (2, 3), (1, 4)])
+def test_general_mesh_host_side_invariants(tmp_path, k, level):
+    """The host side of the general-mesh path (csrc/hdg_general.hpp, hdg_amg.hpp: plain C++, compiled here with g++, no GPU):
+    condensed operator symmetric with the constants as kernel, BDM projection idempotent, the constraint rows of the
+    monolithic system vanish on constants, the P1 prolongation reproduces constants, every level of the smoothed-aggregation
+    hierarchy keeps symmetry / kernel / partition of unity and gets smaller, the dense pseudo-inverse of the coarsest operator
+    inverts on the range, the continuous space has the mesh's volume, projects constants and gives vorticity 2 for a rotation.
+    Levels 3 and 4 (512 / 2048 cells) take the threaded branch of parallel_for (256 cells and more, hdg_general.hpp): a
+    second assembly of the same mesh reproduces every assembled operator, the k_g_lift tables and the element block-Jacobi
+    bit for bit (the work is per cell, so the thread schedule must not change a bit).  The check reports how many threads
+    parallel_for used, and asserts two or more wherever the host has more than one core."""
+    from incompressibleeulerhdg_amd.mesh import UnitDiskMesh
+
+    m = UnitDiskMesh(level)
+    v = _general_host_check(tmp_path, m.vertices, m.cells, k)
     f = lambda name: float(v[name])
+    assert int(v["repeat_mismatches"]) == 0, [name for name in v if name.startswith("repeat_differs")]
+    # the repeat runs on threads only where parallel_for uses them: 256 cells and more, on a host with more than one core
+    threads = int(v["parallel_for_threads"])
+    if m.num_cells() < 256 or (os.cpu_count() or 1) == 1:
+        assert threads == 1
+    else:
+        assert threads >= 2, threads
     assert int(v["nc"]) == 8 * 4 ** level and abs(f("volume") - m.volume) < 1e-12
     for name in ("S_asym", "S_null", "Pi_idempotent", "mu_row_constant", "psi_row_constant", "P0_constants", "amg_null", "amg_asym",
                  "amg_P_constants", "coarse_pinv", "cg_M_asym", "cg_projection_rhs_constant", "cg_vorticity_rotation"):
@@ -356,6 +374,47 @@ def test_general_mesh_host_side_invariants(tmp_path, k, level):
     p = k + 1
     assert int(v["ncg"]) == int(v["nv"]) + int(v["ne"]) * (p - 1) + int(v["nc"]) * (p - 1) * (p - 2) // 2
     assert abs(f("cg_volume") - m.volume) < 1e-11
+
+
+def _csr_threads_per_row(avg):
+    """threads per row of k_csr_apply / k_csr_apply3 / k_amg_cheb from the average row length (upload_csr, hdg_engine.hip)"""
+    for tpr, edge in ((1, 3.0), (2, 6.0), (4, 12.0), (8, 24.0), (16, 48.0), (32, 96.0)):
+        if avg <= edge:
+            return tpr
+    return 64
+
+
+# operators whose bucket on the structured square differs from the disk's (interior vertices of valence 6 only, shorter
+# boundary): the disk cases of tests/test_gpu_general_mesh_scale.py reach the level-6 buckets of these
+_SQUARE_BUCKET_EXCEPTIONS = {"Gl", "Auu", "amg_P0", "amg_A1"}
+
+
+def test_general_mesh_scale_cases_meet_the_kernel_forms_of_the_level6_disk(tmp_path):
+    """k_csr_apply / k_csr_apply3 / k_amg_cheb pick their threads per row from each operator's average row length: the meshes
+    of tests/test_gpu_general_mesh_scale.py (disk levels 4 and 5, the square at 63^2 and 128^2) must meet, at k = 2, the form
+    the benchmarked level-6 disk meets, operator by operator -- the assembled operators, the P1 transfer, the algebraic levels,
+    the element block-Jacobi and the continuous-space matrices (the 8- to 128-cell meshes of tests/test_gpu_general_mesh.py
+    do not: their short boundary rows pull the averages down).  The default hierarchy (coarsening down to <= 2000 vertices):
+    level 4 goes straight to the dense solve, level 5 and 6 have one smoothed level, the 128^2 square two (its level-1
+    operator is in another bucket); level 4 meets the smoothed levels under HDG_AMG_MAX_COARSE in the GPU module."""
+    from general_mesh_checks import square_as_general_mesh
+    from incompressibleeulerhdg_amd.mesh import UnitDiskMesh
+
+    def buckets(vertices, cells):
+        v = _general_host_check(tmp_path, vertices, cells, 2, "rows")
+        return {name[len("rowlen_"):]: _csr_threads_per_row(float(x)) for name, x in v.items() if name.startswith("rowlen_")}, int(v["amg_levels"])
+
+    d6, lev6 = buckets(UnitDiskMesh(6).vertices, UnitDiskMesh(6).cells)
+    assert lev6 == 2 and d6["S"] == 8 and d6["amg_A0"] == 4
+    for level, nlev in ((4, 1), (5, 2)):
+        b, lev = buckets(UnitDiskMesh(level).vertices, UnitDiskMesh(level).cells)
+        assert lev == nlev
+        assert b == {n: t for n, t in d6.items() if n in b}, level
+    for nx, nlev in ((63, 2), (128, 3)):
+        b, lev = buckets(*square_as_general_mesh(nx))
+        assert lev == nlev
+        differ = {n for n in d6 if n in b and b[n] != d6[n]}
+        assert differ <= _SQUARE_BUCKET_EXCEPTIONS, (nx, differ)
 
 
 def test_committed_pmc_traffic_belongs_to_the_committed_kernel_sources():
