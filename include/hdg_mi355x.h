@@ -286,6 +286,25 @@ int hdg_node_coordinates(hdg_handle* h, double* xq, double* xp);
 int hdg_l2_norms(hdg_handle* h, const double* Q, const double* p, double* norm_Q, double* norm_p);
 int hdg_integrate_pressure(hdg_handle* h, const double* p, double* integral);
 
+/* ---- flow diagnostics (no reference counterpart).  Nine columns per state, for the velocity u,
+ * pressure p and tracer q:
+ *   0 energy 1/2 int |u|^2;  1 enstrophy 1/2 sum_K int_K (d_x u_y - d_y u_x)^2 (broken curl);  2 div_l2 (sum_K int_K (div u)^2)^1/2;
+ *   3 jump_l2 (sum_F int_F [u.n]^2)^1/2 over every edge once, boundary edges (u.n) included on non-periodic meshes;
+ *   4 int p;  5 int q;  6 1/2 int q^2 (5, 6: NaN without a tracer);  7 max |u| over the nodes of hdg_node_coordinates;
+ *   8 dt max_K (max nodal |u| in K) / h_K, h_K the shortest edge of K.
+ * Strip partitions: every rank passes its own strip and receives the global values (collective).
+ * hdg_compute_diagnostics: the nine values of nodal fields (layouts of hdg_set_state; q NULL: no tracer) into out[9].
+ * hdg_set_diagnostics: capacity > 0 switches per-step recording on into a device buffer of `capacity` rows and records the
+ *   current state as the first row; every completed step then appends one row without host synchronisation: hdg_step, each
+ *   step of hdg_run_separable, hdg_finish_step (with a tracer on: hdg_tracer_finish_step instead), hdg_implicit_step,
+ *   hdg_dg_implicit_step.  Rows beyond the capacity are dropped and counted.  capacity = 0 switches recording off.
+ * hdg_get_diagnostics: copies min(*n_rows, max_rows) recorded rows (9 doubles each) to `rows`, *n_rows = rows recorded;
+ *   reset != 0 empties the buffer.  Returns HDG_ERR_ARG (rows and *n_rows still filled) when rows were dropped. */
+#define HDG_N_DIAGNOSTICS 9
+int hdg_compute_diagnostics(hdg_handle* h, const double* Q, const double* p, const double* q, double* out);
+int hdg_set_diagnostics(hdg_handle* h, int capacity);
+int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset);
+
 /* kernel-level access for parity tests and micro-benchmarks (nodal in / nodal out) */
 int hdg_apply_advection(hdg_handle* h, const double* Qstar, const double* x, double gamma, double* y);
 int hdg_apply_trace_operator(hdg_handle* h, const double* lam, double* out);

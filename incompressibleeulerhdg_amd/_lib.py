@@ -29,6 +29,10 @@ HDG_COMM_RCCL = 1
 HDG_COMM_SHM = 2
 
 
+# columns of hdg_compute_diagnostics / hdg_get_diagnostics
+DIAGNOSTICS = ("energy", "enstrophy", "div_l2", "jump_l2", "p_integral", "tracer_integral", "tracer_half_sq", "max_speed", "cfl")
+
+
 class HDGError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERRORS.get(code, code)}: {msg}")
@@ -76,7 +80,7 @@ class hdg_config(C.Structure):
 
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
-    srcs = [SRC, HEADER] + [os.path.join(_HERE, "csrc", f) for f in ("hdg_kernels.hpp", "hdg_schur_mfma.hpp", "hdg_tables.hpp", "hdg_comm.hpp", "hdg_cg.hpp", "hdg_general.hpp", "hdg_general_kernels.hpp", "hdg_trace_tile.hpp", "hdg_trace_tile3.hpp", "hdg_side_rows.hpp", "hdg_amg.hpp")]
+    srcs = [SRC, HEADER] + [os.path.join(_HERE, "csrc", f) for f in ("hdg_kernels.hpp", "hdg_schur_mfma.hpp", "hdg_tables.hpp", "hdg_comm.hpp", "hdg_cg.hpp", "hdg_general.hpp", "hdg_general_kernels.hpp", "hdg_trace_tile.hpp", "hdg_trace_tile3.hpp", "hdg_side_rows.hpp", "hdg_amg.hpp", "hdg_diagnostics.hpp")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -152,6 +156,9 @@ SIGNATURES = {
     "hdg_apply_trace_operator": [_h, _dp, _dp],
     "hdg_apply_weak_divergence": [_h, _dp, C.c_int, _dp],
     "hdg_time_kernel": [_h, C.c_int, C.c_int, _dp],
+    "hdg_compute_diagnostics": [_h, _dp, _dp, _dp, _dp],
+    "hdg_set_diagnostics": [_h, C.c_int],
+    "hdg_get_diagnostics": [_h, _dp, C.c_int, _ip, C.c_int],
 }
 
 
@@ -550,6 +557,31 @@ class Engine:
         out = np.empty(self.shape_p)
         self._ck(self.lib.hdg_apply_weak_divergence(self.h, _ptr(Q), 1 if broken else 0, _ptr(out)))
         return out
+
+    # --- flow diagnostics (include/hdg_mi355x.h: hdg_compute_diagnostics / hdg_set_diagnostics / hdg_get_diagnostics)
+    def compute_diagnostics(self, Q, p, q=None):
+        """The nine diagnostics of nodal fields (DIAGNOSTICS order); q None: no tracer (columns 5, 6 NaN)."""
+        Q, p = _arr(Q, self.shape_Q), _arr(p, self.shape_p)
+        q = None if q is None else _arr(q, self.shape_p)
+        out = np.empty(len(DIAGNOSTICS))
+        self._ck(self.lib.hdg_compute_diagnostics(self.h, _ptr(Q), _ptr(p), _ptr(q), _ptr(out)))
+        return out
+
+    def set_diagnostics(self, capacity):
+        """Record one row per completed step into a device buffer of `capacity` rows (the current state is the first
+        row); 0 switches recording off."""
+        self._ck(self.lib.hdg_set_diagnostics(self.h, int(capacity)))
+
+    def diagnostics(self, reset=False):
+        """The recorded rows, (n, 9) in DIAGNOSTICS order.  Raises HDGError when rows were dropped beyond the capacity."""
+        n = C.c_int(0)
+        rc = self.lib.hdg_get_diagnostics(self.h, None, 0, C.byref(n), 0)  # the row count (dropped rows: the call below)
+        if rc not in (0, -1):
+            self._ck(rc)
+        rows = np.empty((n.value, len(DIAGNOSTICS)))
+        self._ck(self.lib.hdg_get_diagnostics(self.h, _ptr(rows) if n.value else None, n.value, C.byref(n),
+                                              1 if reset else 0))
+        return rows
 
     def time_kernel(self, kernel, reps):
         ms = C.c_double()

@@ -37,6 +37,7 @@
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
 #include "hdg_amg.hpp"
+#include "hdg_diagnostics.hpp"
 
 namespace hdg {
 
@@ -4235,6 +4236,108 @@ struct Engine {
     if (tracer_on) copy(q_cur, q_fin, NPv);
   }
 
+  // ------------------------------------------------------------------ flow diagnostics (hdg_diagnostics.hpp)
+  // Recording (diag_cap > 0): every completed step appends one row to diag_rows on the stream, no host synchronisation;
+  // rows beyond the capacity are counted (diag_dropped) and reported when the rows are fetched.  Switched off, no step
+  // issues a single launch more.
+  double *diag_part = nullptr, *diag_acc = nullptr, *diag_gat = nullptr, *diag_out = nullptr, *diag_rows = nullptr;
+  double *diag_Qw = nullptr, *diag_pw = nullptr, *diag_qw = nullptr;  // hdg_compute_diagnostics: modal copies of the inputs
+  const double *diag_hmin = nullptr, *diag_gVu = nullptr;  // general meshes: shortest edge per cell, unscaled modal -> nodal
+  const int* diag_ecl = nullptr;                            // general meshes: (3 c + l) of the cells of every edge
+  int diag_ncb = 0, diag_neb = 0, diag_cap = 0, diag_alloc_rows = 0;
+  long diag_n = 0, diag_dropped = 0;
+  void diag_alloc() {
+    if (diag_part) return;
+    if (general) {
+      const GMesh& M = *gm;
+      diag_ncb = (M.nc + DIAG_BLOCK - 1) / DIAG_BLOCK;
+      diag_neb = (M.ne + DIAG_BLOCK - 1) / DIAG_BLOCK;
+      std::vector<int> ecl((size_t)2 * M.ne, -1);
+      for (int e = 0; e < M.ne; e++)
+        for (int sd = 0; sd < 2; sd++) {
+          const int c = M.ecell[2 * (size_t)e + sd];
+          if (c >= 0) ecl[2 * (size_t)e + sd] = 3 * c + M.elocal[2 * (size_t)e + sd];
+        }
+      dvec hm((size_t)M.nc);
+      for (int c = 0; c < M.nc; c++) {
+        double h = M.elen[(size_t)M.cedge[3 * (size_t)c]];
+        for (int l = 1; l < 3; l++) h = std::min(h, M.elen[(size_t)M.cedge[3 * (size_t)c + l]]);
+        hm[(size_t)c] = h;
+      }
+      diag_ecl = upload_ints(ecl);
+      diag_hmin = upload(hm);
+      diag_gVu = upload(gtab->Vu);
+    } else {
+      diag_ncb = (int)cell_grid().x;
+      diag_neb = (int)corner_grid().x;
+    }
+    diag_part = dalloc((long)diag_ncb * DIAG_NPART + 2L * diag_neb);
+    diag_acc = dalloc(DIAG_NACC);
+    diag_gat = dalloc(2L * comm->size);
+    diag_out = dalloc(DIAG_NCOL);
+  }
+  // the nine columns of (Q, p, q) (modal, device; q may be null) into the device row `row`; Qn: nodal copy of Q in the
+  // boundary layout for the maxima (null: from Q)
+  void diag_pass(const double* Q, const double* p, const double* q, double* row, const double* Qn = nullptr) {
+    diag_alloc();
+    if (!row) throw std::string("diagnostics: no row buffer");
+    double* cpart = diag_part;
+    double* epart = diag_part + (long)diag_ncb * DIAG_NPART;
+    tally(LC_OTHER, bQ() + bP() * (q ? 2.0 : 1.0));
+    if (general) {
+      HDG_DISPATCH(k_g_diag_cell<KK><<<diag_ncb, DIAG_BLOCK, 0, stream>>>(ggeo, diag_gVu, diag_hmin, Q, p, q, Qn, cpart));
+      tally(LC_OTHER, 2.0 * bQ());
+      HDG_DISPATCH(k_g_diag_edge<KK><<<diag_neb, DIAG_BLOCK, 0, stream>>>(ggeo, gm->ne, diag_ecl, Q, epart));
+    } else {
+      HDG_DISPATCH(k_diag_cell<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, Q, p, q, Qn, cpart));
+      halo_Q(Q);  // the edges of the strip's bottom row (and the periodic wrap) read the neighbour's cells
+      tally(LC_OTHER, 3.0 * bQ());
+      HDG_DISPATCH(k_diag_edge<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, Q, epart));
+    }
+    tally(LC_OTHER, 0.0);
+    k_diag_reduce<<<1, 1024, 0, stream>>>(diag_ncb, cpart, diag_neb, epart, diag_acc);
+    const double* mxs = diag_acc + 7;
+    if (comm->size > 1) {  // sums over the owned cells and edges of every rank; maxima gathered, taken by k_diag_row
+      comm->allreduce_sum(diag_acc, 7, stream);
+      comm->allgather(diag_acc + 7, diag_gat, 2, stream);
+      n_reduce++; n_gather++;
+      mxs = diag_gat;
+    }
+    tally(LC_OTHER, 0.0);
+    k_diag_row<<<1, 64, 0, stream>>>(diag_acc, mxs, comm->size, cfg.dt, q ? 1 : 0, row);
+  }
+  // end of a completed step: one row of the current state
+  void diag_record() {
+    if (diag_cap <= 0) return;
+    if (diag_n >= diag_cap) { diag_dropped++; return; }
+    diag_pass(curQ, curP, tracer_on ? q_cur : nullptr, diag_rows + diag_n * DIAG_NCOL);
+    diag_n++;
+  }
+  void diag_set(int cap) {
+    if (cap < 0) throw std::string("diagnostics capacity must be >= 0");
+    diag_n = 0; diag_dropped = 0; diag_cap = cap;
+    if (cap == 0) return;
+    if (cap > diag_alloc_rows) { diag_rows = dalloc((long)cap * DIAG_NCOL); diag_alloc_rows = cap; }
+    diag_record();  // row 0: the state as it is now
+  }
+  void diag_fetch(double* rows, long nrows) {
+    if (nrows > 0) HIPCHECK(hipMemcpyAsync(rows, diag_rows, sizeof(double) * DIAG_NCOL * nrows, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  void diag_compute(const double* Q, const double* p, const double* q, double* out) {
+    diag_alloc();  // before diag_out is read below
+    if (!diag_Qw) { diag_Qw = dalloc(NQ); diag_pw = dalloc(NPv); }
+    if (q) {
+      if (!diag_qw) diag_qw = dalloc(NPv);
+      put_P(q, diag_qw);
+    }
+    put_P(p, diag_pw);
+    put_Q(Q, diag_Qw);  // last: the staging buffer hQ_dev keeps the nodal velocity for the maxima
+    diag_pass(diag_Qw, diag_pw, q ? diag_qw : nullptr, diag_out, hQ_dev);
+    HIPCHECK(hipMemcpyAsync(out, diag_out, sizeof(double) * DIAG_NCOL, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+
   // ------------------------------------------------------------------ host <-> device fields
   long n_edges() const {
     if (general) return gm->ne;
@@ -4637,11 +4740,13 @@ int hdg_stage_update(hdg_handle* h, int stage) {
 int hdg_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.finish_step();
+  if (!E.tracer_on) E.diag_record();  // with a tracer the row is taken after hdg_tracer_finish_step
   HDG_API_END(h)
 }
 int hdg_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.step();
+  E.diag_record();
   HDG_API_END(h)
 }
 int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
@@ -4650,6 +4755,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
   for (int n = 0; n < nsteps; n++) {
     for (int sl = 0; sl <= E.s; sl++) { E.bscale[sl] = scales[(long)n * (E.s + 1) + sl]; E.bsep[sl] = 1; }
     E.step();
+    E.diag_record();
     E.harvest_completed();  // keeps the number of live timer events bounded over a long run
   }
   HDG_API_END(h)
@@ -4657,6 +4763,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
 int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure) {
   HDG_API_BEGIN(h)
   E.implicit_step(its_tentative, its_pressure);
+  E.diag_record();
   HDG_API_END(h)
 }
 // ---- implicit DG discretisation (dg_implicit.py:10-136), single rank
@@ -4671,6 +4778,7 @@ int hdg_dg_implicit_step(hdg_handle* h, int* its) {
   if (int rc = dg_single_rank(h)) return rc;
   HDG_API_BEGIN(h)
   E.dg_implicit_step(its);
+  E.diag_record();
   HDG_API_END(h)
 }
 int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
@@ -4788,6 +4896,7 @@ int hdg_tracer_stage(hdg_handle* h, int stage) {
 int hdg_tracer_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.tracer_finish_step();
+  if (E.tracer_on) E.diag_record();
   HDG_API_END(h)
 }
 int hdg_cg_size(hdg_handle* h, long* n_cg) {
@@ -4892,6 +5001,30 @@ int hdg_integrate_pressure(hdg_handle* h, const double* p, double* integral) {
   E.put_P(p, E.wP1);
   *integral = E.general ? E.dot(E.NPv, E.wP1, E.d_int_p, hdg::Engine::KC)
                         : E.g.h / std::sqrt(2.0) * E.dot(E.g.Nc, E.wP1, E.ones_c, hdg::Engine::KC);
+  HDG_API_END(h)
+}
+int hdg_compute_diagnostics(hdg_handle* h, const double* Q, const double* p, const double* q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!Q || !p || !out) throw std::string("null argument");
+  E.diag_compute(Q, p, q, out);
+  HDG_API_END(h)
+}
+int hdg_set_diagnostics(hdg_handle* h, int capacity) {
+  HDG_API_BEGIN(h)
+  E.diag_set(capacity);
+  HDG_API_END(h)
+}
+int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset) {
+  HDG_API_BEGIN(h)
+  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
+  const long n = E.diag_n, dropped = E.diag_dropped;
+  const long ncopy = std::min<long>(n, max_rows);
+  E.diag_fetch(rows, ncopy);
+  if (n_rows) *n_rows = (int)n;
+  if (reset) { E.diag_n = 0; E.diag_dropped = 0; }
+  if (dropped > 0)
+    throw std::string("diagnostics: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
+        std::to_string(E.diag_cap) + " rows";
   HDG_API_END(h)
 }
 int hdg_time_kernel(hdg_handle* h, int kernel, int reps, double* ms_per_launch) {

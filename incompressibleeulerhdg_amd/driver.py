@@ -15,6 +15,7 @@ import time
 
 import numpy as np
 
+from ._lib import DIAGNOSTICS
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
@@ -65,7 +66,37 @@ def build_parser():
     parser.add_argument("--output", type=str, default="solution.pvd",
                         help="VTK collection written at the end like the reference's solution.pvd ('' = no output)")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    parser.add_argument("--diagnostics", metavar="FILE", type=str, default=None,
+                        help="record energy, enstrophy, divergence, jumps, integrals, maximum speed and CFL number of every "
+                             "step on the device and write them to FILE (CSV); also prints the solver events")
     return parser
+
+
+def report_solver_events(events):
+    """Events of the condensed and tentative-velocity solves (hdg_get_solver_events); warns on rounding-floor exits."""
+    print("solver events")
+    print(40 * "-")
+    for name, n in events.items():
+        print(f"  {name:<27s} : {n:8d}")
+    print()
+    if events["cg_floor_exits"] > 0:
+        print(f"WARNING: {events['cg_floor_exits']} condensed CG solve(s) ended at the rounding floor, not at the relative "
+              "tolerance")
+        print()
+
+
+def write_diagnostics(path, diag):
+    """CSV with one row per recorded state (step, t, the nine diagnostics); prints the first and the last row."""
+    names = list(DIAGNOSTICS)
+    n = len(diag["t"])
+    with open(path, "w") as f:
+        f.write(",".join(["step", "t"] + names) + "\n")
+        for i in range(n):
+            f.write(",".join([str(i), repr(float(diag["t"][i]))] + [repr(float(diag[c][i])) for c in names]) + "\n")
+    print(f"diagnostics ({n} rows) written to {path}")
+    for i in sorted({0, n - 1}):
+        print(f"  step {i:6d}  t = {diag['t'][i]:.6g}  " + "  ".join(f"{c} = {diag[c][i]:.6e}" for c in names))
+    print()
 
 
 def main(argv=None):
@@ -157,7 +188,12 @@ def main(argv=None):
     # driver.py:340-344
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None
     kw = {"fused": True} if (args.fused and args.timestepper != "implicit") else {}
+    if args.diagnostics:
+        kw["diagnostics"] = True
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
+    if args.diagnostics:
+        report_solver_events(eng.solver_events())
+        write_diagnostics(args.diagnostics, timestepper.diagnostics)
     log_summary()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here

@@ -7,7 +7,7 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from .._lib import Engine
+from .._lib import DIAGNOSTICS, Engine
 from ..mesh import Function, FunctionSpace
 
 __all__ = ["IncompressibleEuler"]
@@ -30,6 +30,7 @@ class IncompressibleEuler(ABC):
         self._engine = None
         # common.py:72-73
         self.domain_volume = float(mesh.volume) if getattr(mesh, "general", False) else float(getattr(mesh, "L", 1.0)) ** 2
+        self.diagnostics = None  # solve(..., diagnostics=True): dict of the recorded series
 
     # -- engine and function spaces ------------------------------------------------------------
     def _create_engine(self, **kw):
@@ -103,6 +104,33 @@ class IncompressibleEuler(ABC):
         self.q_tracer = Function(self._V_q, self._engine.get_tracer(), "tracer")
         return self.q_tracer
 
+    # -- flow diagnostics (include/hdg_mi355x.h: hdg_compute_diagnostics) ----------------------
+    def compute_diagnostics(self, Q, p, q=None):
+        """Energy, enstrophy, divergence, normal jumps, pressure and tracer integrals, maximum speed and CFL number of the
+        given fields (what _as_nodal_* accepts; q None: no tracer, the tracer entries are NaN), computed on the device.
+        Returns a dict keyed by the names of ``_lib.DIAGNOSTICS``."""
+        qn = None if q is None else self._as_nodal_pressure(q)
+        vals = self._engine.compute_diagnostics(self._as_nodal_velocity(Q), self._as_nodal_pressure(p), qn)
+        return {name: float(v) for name, v in zip(DIAGNOSTICS, vals)}
+
+    def _start_diagnostics(self, on, nt):
+        """Record nt + 1 rows on the device: the current state (row 0) and the state after every step."""
+        self.diagnostics = None
+        if on:
+            self._engine.set_diagnostics(nt + 1)
+
+    def _finish_diagnostics(self, on):
+        """Fetch the recorded rows once (self.diagnostics: t and the nine series) and switch recording off."""
+        if not on:
+            return
+        try:
+            rows = self._engine.diagnostics(reset=True)
+        finally:
+            self._engine.set_diagnostics(0)
+        self.diagnostics = {"t": np.arange(rows.shape[0]) * self._dt}
+        for i, name in enumerate(DIAGNOSTICS):
+            self.diagnostics[name] = rows[:, i].copy()
+
     @abstractmethod
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""

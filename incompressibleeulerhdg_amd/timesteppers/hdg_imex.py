@@ -122,11 +122,13 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
             self._engine.set_forcing_nodal(slot, self._as_nodal_velocity(f_rhs(t)))
 
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False):
         """Propagate the solution to T_final with nt timesteps; returns (Q, p).
 
         ``fused=True`` runs each step as one device-resident ``hdg_step`` call instead of the
         per-solve calls that mirror the reference's loop (identical results, no per-solve timers).
+        ``diagnostics=True`` records the flow diagnostics of the initial state and of every step on the device and
+        stores them as ``self.diagnostics`` (dict of arrays: ``t`` and the names of ``_lib.DIAGNOSTICS``).
         """
         eng = self._engine
         tracer = self._init_tracer(q_initial)  # hdg_imex.py:523-529
@@ -140,6 +142,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
             a.reset()
         eng.iteration_stats(reset=True)
         eng.timers(reset=True)
+        self._start_diagnostics(diagnostics, nt)
         for callback in self.callbacks:
             callback.reset()
             Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
@@ -186,6 +189,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
                 qt = self._tracer_function() if tracer else None
                 for callback in self.callbacks:
                     callback(Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p"), tn + self._dt, q_tracer=qt)
+        self._finish_diagnostics(diagnostics)
         if fused:
             # per-solve breakdown of the fused steps from the engine's device-side timers (same labels as the
             # host timers of the per-solve path; "timestep" is already timed on the host)
