@@ -79,7 +79,8 @@ typedef struct hdg_config {
   int unsplit_maxit;
   int device;            /* HIP device ordinal */
   /* mesh variants: periodic != 0 selects the doubly periodic square
-   * PeriodicSquareMesh(nx, nx, L) of driver.py:182-183 (no boundary edges, 3 nx ny edges, single rank); length = side
+   * PeriodicSquareMesh(nx, nx, L) of driver.py:182-183 (no boundary edges, 3 nx ny edges; one rank or periodic strips,
+   * hdg_create_distributed); length = side
    * of the square (0 means 1: UnitSquareMesh, driver.py:181) */
   int periodic;
   double length;
@@ -121,7 +122,13 @@ const char* hdg_last_error(const hdg_handle* h); /* h may be NULL for create err
  * bottom row).  backend HDG_COMM_RCCL: `token` = the 128 bytes from hdg_rccl_unique_id of rank 0
  * (one GPU per rank); HDG_COMM_SHM: `token` = name of a POSIX shared-memory segment, host-staged
  * transport for several ranks on one node (also on one GPU).  Reductions are over owned entries and
- * identical on every rank, so all ranks take the same Krylov iterations. */
+ * identical on every rank, so all ranks take the same Krylov iterations.
+ * Periodic strips (cfg->periodic != 0, nranks > 1): the same ownership of cell rows, with ny / nranks >= 2 and an even nx
+ * (HDG_ERR_ARG otherwise).  Rank r's lower neighbour is (r - 1) mod nranks and its upper one (r + 1) mod nranks, and there is
+ * NO duplicated top row: a rank owns its bottom H-edge row and its ny_local rows of each edge family (3 nx ny_local edges).
+ * Its host arrays are its own rows in the single-rank periodic numbering, so concatenating the strips in rank order, per
+ * cell array and per edge family (H, V, D), gives the single-rank arrays exactly.  The continuous space (tracer, vorticity,
+ * hdg_cg_*) and the DG discretisation stay single-rank there as on the unit square. */
 #define HDG_COMM_RCCL 1
 #define HDG_COMM_SHM 2
 int hdg_create_distributed(const hdg_config* cfg, int rank, int nranks, int backend, const char* token, hdg_handle** out);

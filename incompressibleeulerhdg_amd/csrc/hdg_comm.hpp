@@ -39,9 +39,14 @@ struct CommError {
 struct Comm {
   int rank = 0, size = 1;
   bool failed = false;  // a collective of this rank failed: tear the communicator down without waiting for the peers
+  // periodic strips (set by the engine): the ranks form a ring, rank 0's lower neighbour is size-1 and vice versa.  With
+  // two ranks both neighbours are the same peer.
+  bool ring = false;
+  int lower() const { return rank > 0 ? rank - 1 : (ring ? size - 1 : -1); }  // -1: no neighbour
+  int upper() const { return rank < size - 1 ? rank + 1 : (ring ? 0 : -1); }
   virtual ~Comm() {}
-  // send `n` doubles from slo to rank-1 and from shi to rank+1; receive the neighbours' messages
-  // into rlo (from rank-1) and rhi (from rank+1).  Missing neighbours are skipped.
+  // send `n` doubles from slo to lower() and from shi to upper(); receive the neighbours' messages
+  // into rlo (from lower()) and rhi (from upper()).  Missing neighbours are skipped.
   virtual void exchange(const double* slo, double* rlo, const double* shi, double* rhi, size_t n, hipStream_t st) {}
   virtual void allreduce_sum(double* dev, int n, hipStream_t st) {}
   // every rank contributes n doubles; recv holds size*n doubles in rank order
@@ -96,14 +101,27 @@ struct CommRccl : Comm {
     if (r != ncclSuccess) { failed = true; throw CommError{std::string(what) + ": " + ncclGetErrorString(r)}; }
   }
   void exchange(const double* slo, double* rlo, const double* shi, double* rhi, size_t n, hipStream_t st) override {
+    const int lo = lower(), hi = upper();
     ck(ncclGroupStart(), "ncclGroupStart");
-    if (rank > 0) {
-      ck(ncclSend(slo, n, ncclDouble, rank - 1, comm, st), "ncclSend");
-      ck(ncclRecv(rlo, n, ncclDouble, rank - 1, comm, st), "ncclRecv");
-    }
-    if (rank < size - 1) {
-      ck(ncclSend(shi, n, ncclDouble, rank + 1, comm, st), "ncclSend");
-      ck(ncclRecv(rhi, n, ncclDouble, rank + 1, comm, st), "ncclRecv");
+    if (lo >= 0 && lo == hi) {
+      // Ring of two ranks: the one peer is both neighbours.  RCCL matches the messages between one pair of ranks in the
+      // order they are posted, so the posting order decides which buffer receives what.  The peer's "to lower" message
+      // (its lowest rows) belongs in OUR upper ghost rows and its "to upper" message in our lower ones: both ranks post
+      // send(slo), send(shi), recv(rhi), recv(rlo), so the first send of either rank meets the first receive (rhi) of the
+      // other and the second send the second receive (rlo) -- correct by construction, with no tag.
+      ck(ncclSend(slo, n, ncclDouble, lo, comm, st), "ncclSend");
+      ck(ncclSend(shi, n, ncclDouble, hi, comm, st), "ncclSend");
+      ck(ncclRecv(rhi, n, ncclDouble, hi, comm, st), "ncclRecv");
+      ck(ncclRecv(rlo, n, ncclDouble, lo, comm, st), "ncclRecv");
+    } else {
+      if (lo >= 0) {
+        ck(ncclSend(slo, n, ncclDouble, lo, comm, st), "ncclSend");
+        ck(ncclRecv(rlo, n, ncclDouble, lo, comm, st), "ncclRecv");
+      }
+      if (hi >= 0) {
+        ck(ncclSend(shi, n, ncclDouble, hi, comm, st), "ncclSend");
+        ck(ncclRecv(rhi, n, ncclDouble, hi, comm, st), "ncclRecv");
+      }
     }
     ck(ncclGroupEnd(), "ncclGroupEnd");
   }
@@ -192,16 +210,20 @@ struct CommShm : Comm {
   void exchange(const double* slo, double* rlo, const double* shi, double* rhi, size_t n, hipStream_t st) override {
     if (n > cap_halo) throw CommError{"halo message exceeds the shared-memory slot"};
     const uint64_t e = ++e_halo;
-    const bool lo = rank > 0, hi = rank < size - 1;
+    // Ring of two ranks (lower() == upper()): our two messages go into the peer's two different slots (slo -> its
+    // from-upper slot, shi -> its from-lower slot), and both epoch waits are on the same peer, which is harmless: its
+    // halo_read / halo_sent counters order the whole exchange, not one direction of it.
+    const int lr = lower(), ur = upper();
+    const bool lo = lr >= 0, hi = ur >= 0;
     if (lo) (void)hipMemcpyAsync(stage.data(), slo, n * sizeof(double), hipMemcpyDeviceToHost, st);
     if (hi) (void)hipMemcpyAsync(stage.data() + cap_halo, shi, n * sizeof(double), hipMemcpyDeviceToHost, st);
     (void)hipStreamSynchronize(st);
     // the receiver must have consumed the previous message before its slot is overwritten
-    if (lo) { wait_ge(hdr(rank - 1)->halo_read, e - 1, "lower neighbour (read)"); std::memcpy(halo_slot(rank - 1, 1), stage.data(), n * sizeof(double)); }
-    if (hi) { wait_ge(hdr(rank + 1)->halo_read, e - 1, "upper neighbour (read)"); std::memcpy(halo_slot(rank + 1, 0), stage.data() + cap_halo, n * sizeof(double)); }
+    if (lo) { wait_ge(hdr(lr)->halo_read, e - 1, "lower neighbour (read)"); std::memcpy(halo_slot(lr, 1), stage.data(), n * sizeof(double)); }
+    if (hi) { wait_ge(hdr(ur)->halo_read, e - 1, "upper neighbour (read)"); std::memcpy(halo_slot(ur, 0), stage.data() + cap_halo, n * sizeof(double)); }
     hdr(rank)->halo_sent.store(e, std::memory_order_release);
-    if (lo) { wait_ge(hdr(rank - 1)->halo_sent, e, "lower neighbour (send)"); (void)hipMemcpyAsync(rlo, halo_slot(rank, 0), n * sizeof(double), hipMemcpyHostToDevice, st); }
-    if (hi) { wait_ge(hdr(rank + 1)->halo_sent, e, "upper neighbour (send)"); (void)hipMemcpyAsync(rhi, halo_slot(rank, 1), n * sizeof(double), hipMemcpyHostToDevice, st); }
+    if (lo) { wait_ge(hdr(lr)->halo_sent, e, "lower neighbour (send)"); (void)hipMemcpyAsync(rlo, halo_slot(rank, 0), n * sizeof(double), hipMemcpyHostToDevice, st); }
+    if (hi) { wait_ge(hdr(ur)->halo_sent, e, "upper neighbour (send)"); (void)hipMemcpyAsync(rhi, halo_slot(rank, 1), n * sizeof(double), hipMemcpyHostToDevice, st); }
     (void)hipStreamSynchronize(st);
     hdr(rank)->halo_read.store(e, std::memory_order_release);
   }

@@ -603,16 +603,22 @@ struct Engine {
     // tested on every multi-rank test over the shared-memory transport, but ncclSend / ncclRecv on a second stream beside
     // kernels has never run on two devices (round-3 advisor finding): the first multi-GPU run uses the plain single-stream order
     overlap_on = !std::getenv("HDG_NO_OVERLAP") && std::getenv("HDG_OVERLAP") != nullptr;
-    if (periodic && comm->size > 1) throw std::string("the periodic mesh is implemented for a single rank");
     if (periodic && (c.nx % 2 != 0)) throw std::string("the periodic mesh needs an even nx (red-black coarse-grid sweeps)");
-    if (periodic && g.ny < 4) throw std::string("the periodic mesh needs at least 4 cell rows");
+    if (periodic && c.ny < 4) throw std::string("the periodic mesh needs at least 4 cell rows");
+    if (periodic && comm->size > 1 && g.ny < PERIODIC_MIN_ROWS)
+      throw std::string("periodic strips need at least ") + std::to_string(PERIODIC_MIN_ROWS) + " cell rows per rank (ny / ranks = " +
+          std::to_string(g.ny) + ")";
     if (periodic) {
       // y-periodicity without touching a kernel: the strip pretends to lie in the middle of a taller mesh (no physical
-      // boundary test in y fires, the top H row is a ghost copy of the bottom one like on a rank below another) and its
-      // ghost rows are filled from its own opposite side (halo_rows -> k_wrap_rows)
-      g.joff = g.ny; g.nyg = 3 * g.ny; g.nyc = g.ny;
+      // boundary test in y fires, the top H row is a ghost copy of the bottom one like on a rank below another).  One rank:
+      // its ghost rows are filled from its own opposite side (halo_rows -> k_wrap_rows).  P > 1 ranks (periodic strips): rank
+      // r owns the cell / vertex / bottom H-edge rows r ny/P .. (r+1) ny/P - 1 of the global mesh, all strips sit in the SAME
+      // taller mesh, and the ghost rows come from the ring neighbours (r -/+ 1) mod P (Comm::ring)
+      g.joff = c.ny + comm->rank * g.ny; g.nyg = 3 * c.ny; g.nyc = g.ny;
+      comm->ring = comm->size > 1;
     }
     g.px = periodic ? 1 : 0;
+    g.pj0 = periodic ? comm->rank * g.ny : 0;
     g.P = ((c.nx + 1 + 15) / 16) * 16;
     g.G = (long)(g.ny + 2 * GH) * g.P;
     g.R = g.ny + 2 * GH;
@@ -797,8 +803,13 @@ struct Engine {
     if (n == g.Nc) return 8.0 * 2.0 * g.nx * g.ny;
     return 8.0 * (double)n;
   }
+  // The one place that decides whether this strip has a lower / upper neighbour: on the unit square every rank but the
+  // bottom / top one; on the periodic square always -- the ring neighbours on P > 1 ranks, the strip's own opposite side on
+  // one rank (k_wrap_rows; every use of the answer on one rank sits behind a comm->size > 1 test or is the tile kernels' wrap)
+  bool has_lo() const { return periodic || (comm->size > 1 && comm->rank > 0); }
+  bool has_hi() const { return periodic || (comm->size > 1 && comm->rank < comm->size - 1); }
   void halo_rows(double* v, long plane_stride, int row_len, int nplanes, int kind, int depth = 1, int gh = GH) {
-    if (periodic && halo_on) {  // ghost rows = the owned rows of the opposite side
+    if (periodic && comm->size == 1 && halo_on) {  // ghost rows = the owned rows of the opposite side
       k_wrap_rows<<<std::min(vec_blocks((long)nplanes * row_len * gh), 512), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, g.ny, gh);
       return;
     }
@@ -814,8 +825,8 @@ struct Engine {
     const int nbh = std::min(nb, 256);
     k_pack_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, gh, gh + g.ny - depth, hb_slo, hb_shi);
     comm->exchange(hb_slo, hb_rlo, hb_shi, hb_rhi, (size_t)n, stream);
-    k_unpack_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, comm->rank > 0 ? gh - depth : -1,
-                                                    comm->rank < comm->size - 1 ? gh + g.ny : -1, hb_rlo, hb_rhi);
+    k_unpack_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, has_lo() ? gh - depth : -1,
+                                                    has_hi() ? gh + g.ny : -1, hb_rlo, hb_rhi);
   }
   // ---- self-check of the ghost-row bookkeeping (HDG_FLOW_CHECK=1, tests): whenever a stencil input is NOT exchanged because
   // the bookkeeping calls its ghost rows valid, exchange anyway into the receive buffers and compare with what is there.
@@ -826,15 +837,15 @@ struct Engine {
   long fc_count = 0;
   double fc_worst = 0.0;
   void halo_rows_compare(const double* v, long plane_stride, int row_len, int nplanes, int depth, int gh = GH) {
-    if (comm->size == 1 || !halo_on || periodic || depth < 1) return;
+    if (comm->size == 1 || !halo_on || depth < 1) return;
     const long n = (long)nplanes * row_len * depth;
     if ((size_t)n > cap_halo) throw std::string("halo buffer too small");
     if (!d_fc) d_fc = reinterpret_cast<unsigned long long*>(dalloc(2));
     const int nbh = std::min(vec_blocks(n), 256);
     k_pack_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, gh, gh + g.ny - depth, hb_slo, hb_shi);
     comm->exchange(hb_slo, hb_rlo, hb_shi, hb_rhi, (size_t)n, stream);
-    k_compare_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, comm->rank > 0 ? gh - depth : -1,
-                                                     comm->rank < comm->size - 1 ? gh + g.ny : -1, hb_rlo, hb_rhi, d_fc);
+    k_compare_rows<<<dim3(nbh, 2), 256, 0, stream>>>(v, plane_stride, row_len, nplanes, depth, has_lo() ? gh - depth : -1,
+                                                     has_hi() ? gh + g.ny : -1, hb_rlo, hb_rhi, d_fc);
     fc_count++;
   }
   void flow_check_input(const double* in, int kind, int depth) {
@@ -896,7 +907,7 @@ struct Engine {
       static const bool off = std::getenv("HDG_NO_EXT") != nullptr;
       if (E.fl.nest++ == 0) {
         E.fl.v.clear();
-        E.fl.Dx = (off || E.comm->size == 1 || E.periodic || !E.halo_on) ? 1 : std::min(DX_DEFAULT, E.g.ny);
+        E.fl.Dx = (off || E.comm->size == 1 || !E.halo_on) ? 1 : std::min(DX_DEFAULT, E.g.ny);
       }
     }
     ~FlowScope() noexcept(false) {
@@ -911,7 +922,7 @@ struct Engine {
   int stencil_in(const double* in, int kind, Pending* defer = nullptr) {
     const int depth = fl.active() ? fl.Dx : 1;
     if (!fl.active() || fl.get(in) < 1) {
-      const bool real_exchange = comm->size > 1 && halo_on && !periodic;
+      const bool real_exchange = comm->size > 1 && halo_on;
       if (defer && real_exchange && overlap_on && kind != FP) {
         defer->on = true; defer->v = in; defer->kind = kind; defer->depth = depth;  // the caller runs it (halo_run)
       } else {
@@ -932,8 +943,8 @@ struct Engine {
   Geo g_ext(int ext) const {  // this launch's geometry: ext ghost rows towards every existing neighbour
     Geo c = g;
     if (comm->size > 1 && ext > 0) {
-      c.elo = comm->rank > 0 ? ext : 0;
-      c.ehi = comm->rank < comm->size - 1 ? ext : 0;
+      c.elo = has_lo() ? ext : 0;
+      c.ehi = has_hi() ? ext : 0;
       c.rows_xcd = (c.ny + c.elo + c.ehi + 7) / 8;
       c.rows_xcdc = (c.nyc + c.elo + c.ehi + 7) / 8;
       c.wrows = c.ny + c.elo + c.ehi;
@@ -947,12 +958,12 @@ struct Engine {
   // runs on the compute stream while pack -> send/recv -> unpack run on the communication stream; the boundary launch
   // (ghost rows and the first / last owned row, ONE launch with a gap over the interior) waits for the unpack.
   bool can_split(const Geo& full) const {
-    const int lo = comm->rank > 0 ? 1 : 0, hi = comm->rank < comm->size - 1 ? 1 : 0;
+    const int lo = has_lo() ? 1 : 0, hi = has_hi() ? 1 : 0;
     return overlap_on && comm->size > 1 && full.ny - lo - hi >= 2 && (full.elo + lo + full.ehi + hi) > 0;
   }
   Geo window_interior(const Geo& full) const {
     Geo c = full;
-    const int lo = comm->rank > 0 ? 1 : 0, hi = comm->rank < comm->size - 1 ? 1 : 0;
+    const int lo = has_lo() ? 1 : 0, hi = has_hi() ? 1 : 0;
     c.wskip = full.elo + lo; c.wgap0 = 0; c.wgapn = 0;
     c.wrows = full.ny - lo - hi;
     c.wrowsc = full.nyc - lo - hi;
@@ -962,7 +973,7 @@ struct Engine {
   }
   Geo window_boundary(const Geo& full) const {
     Geo c = full;
-    const int lo = comm->rank > 0 ? 1 : 0, hi = comm->rank < comm->size - 1 ? 1 : 0;
+    const int lo = has_lo() ? 1 : 0, hi = has_hi() ? 1 : 0;
     c.wskip = 0;
     c.wgap0 = full.elo + lo;                    // the rows below the interior ...
     c.wgapn = full.ny - lo - hi;                // ... then skip it (cells)
@@ -1020,7 +1031,7 @@ struct Engine {
     const Geo full = g_ext(ext);
     if (ext_out) *ext_out = ext;
     if (pd.on && can_split(full)) {
-      const int lo = comm->rank > 0 ? 1 : 0, hi = comm->rank < comm->size - 1 ? 1 : 0;
+      const int lo = has_lo() ? 1 : 0, hi = has_hi() ? 1 : 0;
       halo_mark(pd);
       launch(window_interior(full));
       halo_run(pd);
@@ -2907,7 +2918,12 @@ struct Engine {
   // barriers cost; k = 4 at 512^2 (row-stencil kernels -> edge form) 5.32 -> 4.60.  Default: the edge form at k = 4 only.
   int trace_tile3_env = std::getenv("HDG_TRACE_TILE3") ? std::atoi(std::getenv("HDG_TRACE_TILE3")) : -1;
   bool tile3() const { return trace_tile3_env >= 0 ? trace_tile3_env != 0 : K >= 4; }
-  static constexpr int TILE_HALO_R = 5;  // ghost rows of r the tiled preconditioner reads on a strip (pre: 3 computed + 2 halo)
+  static constexpr int TILE_HALO_R = 5;
+  // Periodic strips: the shortest strip that is accepted.  Every exchange sends at most the strip's own rows (the solvers'
+  // depth is Dx = min(DX_DEFAULT, ny), the tiled preconditioner's TILE_HALO_R only runs on strips of >= 8 rows), so one row
+  // would be enough for the ghost depth; with one row, though, a rank's lower and upper messages are the same owned row,
+  // a case nothing else exercises.  Two rows is the shortest strip the unit-square partition is tested at as well.
+  static constexpr int PERIODIC_MIN_ROWS = 2;  // ghost rows of r the tiled preconditioner reads on a strip (pre: 3 computed + 2 halo)
   bool use_trace_tile() const {
     static const bool off = std::getenv("HDG_TRACE_NO_TILE") != nullptr;
     static const int nsm = std::getenv("HDG_TRACE_SMOOTH_ITS") ? std::atoi(std::getenv("HDG_TRACE_SMOOTH_ITS")) : 2;
@@ -2920,6 +2936,15 @@ struct Engine {
     return !off && fuse && nsm == 2 && cfg.trace_precond == 1 && !general && halo_on && (K <= 3 || tile3()) &&
            (comm->size == 1 || (strips && g.ny >= TILE_HALO_R));
   }
+  // periodic strips: the vertex grid has exactly ny rows and every rank restricts onto its own ny/P of them (k_trace_to_p1p at
+  // rows pj0 ..), so the rank blocks are disjoint and lie in rank order: ONE all-gather, in place, assembles the global
+  // right-hand side; the replicated V-cycle (fused legs, dense tail) then runs on every rank as on one rank
+  void gather_periodic_rhs() {
+    if (comm->size == 1) return;
+    const long blk = (long)g.ny * g.nx;
+    comm->allgather(mg_b[0] + (long)g.pj0 * g.nx, mg_b[0], (size_t)blk, stream);
+    n_gather++;
+  }
   // vertex-grid correction of the trace preconditioner: mg_b[0] <- restriction of `res` (owned edges), one V-cycle, result in
   // mg_x[0] (global vertex numbering; on a strip valid on the rank's vertex rows and the 3 rows around them)
   void coarse_correction(const double* res) {
@@ -2927,6 +2952,7 @@ struct Engine {
     tally(LC_MG, bL() + 8.0 * (g.nx + 1.0) * (g.ny + 1.0));
     if (periodic) {  // (row -1 of `res` comes from the pre kernel's ghost rows)
       k_trace_to_p1p<<<corner_grid(), bs(), 0, stream>>>(g, NL, res, mg_b[0], dt.elen[0], dt.elen[2], dt.elen[1]);
+      gather_periodic_rhs();
       run_vcycle();
       return;
     }
@@ -3054,8 +3080,8 @@ struct Engine {
       const double nvtx = 8.0 * (g.nx + 1.0) * (g.ny + 1.0);
       // strip partition: the ONE exchange of a CG iteration -- r, 5 ghost rows deep (the pre kernel computes z on 3 ghost rows
       // towards every neighbour from r on 5; the post kernel then finds its halo of z and r locally)
-      const bool has_lo = periodic || (comm->size > 1 && comm->rank > 0), has_hi = periodic || (comm->size > 1 && comm->rank < comm->size - 1);
-      if (periodic) halo_L(r, TILE_HALO_R);  // (k_wrap_rows: every ghost row from the opposite side)
+      const bool has_lo = this->has_lo(), has_hi = this->has_hi();
+      if (periodic && comm->size == 1) halo_L(r, TILE_HALO_R);  // (k_wrap_rows: every ghost row from the opposite side)
       else if (comm->size > 1) {
         if (fl.get(r) < TILE_HALO_R) { halo_L(r, TILE_HALO_R); fl.set(r, TILE_HALO_R); }
         else if (flow_check) flow_check_input(r, FL, TILE_HALO_R);
@@ -3134,6 +3160,7 @@ struct Engine {
     if (periodic) {
       halo_L(wL2);
       k_trace_to_p1p<<<corner_grid(), bs(), 0, stream>>>(g, NL, wL2, mg_b[0], dt.elen[0], dt.elen[2], dt.elen[1]);
+      gather_periodic_rhs();
       run_vcycle();
       k_p1p_to_trace<<<corner_grid(), bs(), 0, stream>>>(g, NL, mg_x[0], z, 1.0, dt.elen[0], dt.elen[2], dt.elen[1]);
       fl.set(z, 0);  // owned rows only: the wrapped ghost rows are stale
@@ -4394,7 +4421,7 @@ struct Engine {
         for (int i = 0; i < g.nx; i++)
           for (int sh = 0; sh < 2; sh++) {
             const long c = 2 * ((long)j * g.nx + i) + sh;
-            const int joff_true = periodic ? 0 : g.joff;
+            const int joff_true = periodic ? g.pj0 : g.joff;
             const double x0 = (sh == 0 ? i : i + 1) * g.h, y0 = (joff_true + (sh == 0 ? j : j + 1)) * g.h;
             const double sg = sh == 0 ? 1.0 : -1.0;
             for (long n = 0; n < nn; n++) {

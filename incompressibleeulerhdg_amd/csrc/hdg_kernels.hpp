@@ -56,8 +56,11 @@ struct Geo {
   //   x: px != 0 -> column indices wrap (only lanes 0 / nx-1 take another address); corner kernels run nx columns.
   //   y: no kernel knows about it: the engine pretends that the strip lies in the middle of a taller mesh (joff = ny,
   //      nyg = 3 ny: every physical-boundary test in y is false) and fills the ghost rows from the opposite side of
-  //      the strip before every stencil operator, exactly as it would from a neighbouring rank.
+  //      the strip before every stencil operator, exactly as it would from a neighbouring rank.  On P > 1 ranks (periodic
+  //      strips) the ghost rows come from the two neighbours of a ring instead, and every strip lies inside the same taller
+  //      mesh (joff = ny_global + pj0).
   int px;
+  int pj0;  // periodic square: global row of the strip's first vertex / cell row (0 on one rank); the vertex grid is global
   // THIS launch also computes elo ghost rows below and ehi above the owned rows (at most GH - 1; rows_xcd / rows_xcdc
   // of the copy cover the extended range): the stencil operators of the two solvers (Engine::Flow).
   int elo, ehi;
@@ -3338,9 +3341,9 @@ __global__ void k_p1p_prolong_add(int nc, const double* __restrict__ xc, double*
 __global__ void k_p1p_to_trace(Geo g, int NL, const double* __restrict__ xc, double* __restrict__ l, double accumulate,
                                double lH, double lV, double lD) {
   HDG_CORNER_PROLOGUE
-  const int n = g.nx, i1 = pw(i + 1, n), j1 = pw(j + 1, n);
+  const int n = g.nx, J = g.pj0 + j, i1 = pw(i + 1, n), j1 = pw(J + 1, n);  // (owned corner rows: J < n)
   const double r3 = 0.57735026918962576451;
-  const double v00 = xc[j * n + i], v10 = xc[j * n + i1], v01 = xc[j1 * n + i];
+  const double v00 = xc[J * n + i], v10 = xc[J * n + i1], v01 = xc[j1 * n + i];
   const double ea[3] = {v00, v00, v10}, eb[3] = {v10, v01, v01}, len[3] = {lH, lV, lD};
 #pragma unroll
   for (int t = 0; t < 3; t++) {
@@ -3364,7 +3367,7 @@ __global__ void k_trace_to_p1p(Geo g, int NL, const double* __restrict__ l, doub
   double acc = sH * (H0[o] - r3 * H1[o]) + sH * (H0[oL] + r3 * H1[oL])          // H(i,j) a-end, H(i-1,j) b-end
              + sV * (V0[o] - r3 * V1[o]) + sV * (V0[o - g.P] + r3 * V1[o - g.P])  // V(i,j) a-end, V(i,j-1) b-end (ghost row for j = 0)
              + sD * (D0[oL] - r3 * D1[oL]) + sD * (D0[o - g.P] + r3 * D1[o - g.P]);  // D(i-1,j) a-end, D(i,j-1) b-end
-  rc[j * g.nx + i] = acc;
+  rc[(g.pj0 + j) * g.nx + i] = acc;
 }
 // periodic strip on one rank: the ghost rows are the owned rows of the opposite side (array rows: 0 ghost below,
 // 1..ny owned, ny+1 ghost above)

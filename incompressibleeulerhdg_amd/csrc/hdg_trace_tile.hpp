@@ -300,10 +300,10 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
     double z[NT];
     load_corner<NL>(z_in, g, c, z);
     if (c.exists && g.px) {
-      // periodic vertex grid: nx x ny vertices, both indices wrap (j, i within 3 of the strip)
-      const int n = g.nx, m = g.ny;
+      // periodic vertex grid: nx x nx vertices (square mesh), both indices wrap (j, i within 3 of the strip; global row pj0 + j)
+      const int n = g.nx, m = g.nx, jg = g.pj0 + j;
       const int iw = i < 0 ? i + n : (i >= n ? i - n : i), i1 = iw + 1 == n ? 0 : iw + 1;
-      const int jw = j < 0 ? j + m : (j >= m ? j - m : j), j1 = jw + 1 == m ? 0 : jw + 1;
+      const int jw = jg < 0 ? jg + m : (jg >= m ? jg - m : jg), j1 = jw + 1 == m ? 0 : jw + 1;
       const double v00 = xc[(long)jw * n + iw], v10 = xc[(long)jw * n + i1], v01 = xc[(long)j1 * n + iw];
       edge_prolong(v00, v10, sH, z);
       if (c.in_y) edge_prolong(v10, v01, sD, z + NL);

@@ -278,9 +278,9 @@ __global__ __launch_bounds__(TraceTile3<K>::NTHREADS) void k_trace_post_tile3(in
     if (ok) {
       double va, vb;  // the vertex values at the a- and the b-end of the edge
       if (g.px) {
-        const int n = g.nx, mm = g.ny;
+        const int n = g.nx, mm = g.nx, jg = g.pj0 + j;  // square mesh: nx x nx vertices, global row pj0 + j
         const int iw = i < 0 ? i + n : (i >= n ? i - n : i), i1 = iw + 1 == n ? 0 : iw + 1;
-        const int jw = j < 0 ? j + mm : (j >= mm ? j - mm : j), j1 = jw + 1 == mm ? 0 : jw + 1;
+        const int jw = jg < 0 ? jg + mm : (jg >= mm ? jg - mm : jg), j1 = jw + 1 == mm ? 0 : jw + 1;
         const double v00 = xc[(long)jw * n + iw];
         if (t == 0) { va = v00; vb = xc[(long)jw * n + i1]; }
         else if (t == 1) { va = v00; vb = xc[(long)j1 * n + iw]; }

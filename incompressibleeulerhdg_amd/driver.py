@@ -8,8 +8,17 @@ are built with the ``hdg`` discretisation and, with ``--timestepper implicit``, 
 driver.py:203-213); the ``conforming`` discretisation raises.  ``--animation`` (evolution.pvd with
 the CG vorticity, callbacks.py:30-85) and ``--tracer_advection`` (driver.py:340-344) work on every mesh.  The final fields are written to ``solution.pvd``
 (``--output``) like the reference does (driver.py:356-385).
+
+``--gpus N`` (N > 1) runs the two structured problems on N strips (one process per rank, include/hdg_mi355x.h:
+hdg_create_distributed): the driver starts ``python -m torch.distributed.run --nproc-per-node=N`` with the same arguments
+as a child process and returns its exit status.  Each rank chooses RCCL when every rank has a device of its own and the
+shared-memory transport when ranks share one; only rank 0 prints and writes files.
 """
 import argparse
+import contextlib
+import io
+import os
+import subprocess
 import sys
 import time
 
@@ -18,7 +27,7 @@ import numpy as np
 from ._lib import DIAGNOSTICS
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
-from .mesh import Function, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
+from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
 from .model_problems import DoubleLayerShearFlow, KelvinHelmholtz, TaylorGreen
 from .output import VTKFile
 from .timesteppers import (
@@ -69,7 +78,102 @@ def build_parser():
     parser.add_argument("--diagnostics", metavar="FILE", type=str, default=None,
                         help="record energy, enstrophy, divergence, jumps, integrals, maximum speed and CFL number of every "
                              "step on the device and write them to FILE (CSV); also prints the solver events")
+    parser.add_argument("--gpus", type=int, default=1,
+                        help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
+
+
+def check_multi_gpu(args):
+    """Refuse what the strip partition does not run, before any process is started or any engine is built."""
+    if args.gpus < 1:
+        raise RuntimeError(f"--gpus must be at least 1 (got {args.gpus})")
+    if args.gpus == 1:
+        return
+    refused = [
+        (args.tracer_advection, "--tracer_advection (the continuous space of the tracer is single-rank)"),
+        (args.animation, "--animation (the vorticity's continuous space is single-rank)"),
+        (args.test_pressure_solver, "--test_pressure_solver"),
+        (args.discretisation == "dg", "--discretisation dg (single-rank)"),
+        (args.problem == "kelvinhelmholtz", "--problem kelvinhelmholtz (general meshes are single-rank)"),
+        (args.nx % args.gpus != 0, f"--nx {args.nx} not divisible by --gpus {args.gpus} (strips of equal height)"),
+    ]
+    for bad, what in refused:
+        if bad:
+            raise RuntimeError(f"--gpus {args.gpus} does not support {what}")
+
+
+def launch_ranks(argv, nranks):
+    """Start the ranks as a fresh child process (torch.distributed.run) and wait for it; returns its exit status."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    import socket
+
+    with socket.socket() as so:  # a free rendezvous port: runs side by side do not meet
+        so.bind(("127.0.0.1", 0))
+        port = so.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nranks}", "--master-addr",
+           "127.0.0.1", "--master-port", str(port), "-m", "incompressibleeulerhdg_amd.driver", *argv]
+    return subprocess.call(cmd, env=env)
+
+
+class _Ranks:
+    """This process's place in a --gpus run: rendezvous (gloo), device, transport and the timestepper keyword arguments."""
+
+    def __init__(self, args):
+        self.size = args.gpus
+        self.rank = 0
+        self.dist = None
+        self.kwargs = {"device": args.device}
+        if self.size == 1:
+            return
+        import torch
+        import torch.distributed as dist
+
+        from .distributed import comm_kwargs, make_comm_token
+
+        self.rank = int(os.environ["RANK"])
+        if int(os.environ["WORLD_SIZE"]) != self.size:
+            raise RuntimeError(f"WORLD_SIZE {os.environ['WORLD_SIZE']} differs from --gpus {self.size}")
+        dist.init_process_group("gloo")
+        self.dist = dist
+        ndev = max(torch.cuda.device_count(), 1)
+        device = (args.device + int(os.environ.get("LOCAL_RANK", self.rank))) % ndev
+        devices = [None] * self.size
+        dist.all_gather_object(devices, device)
+        backend = "rccl" if len(set(devices)) == self.size else "shm"  # RCCL refuses two ranks on one device
+
+        def bcast(obj):
+            lst = [obj]
+            dist.broadcast_object_list(lst, src=0)
+            return lst[0]
+
+        token = make_comm_token(backend, self.rank, bcast)
+        self.backend = backend
+        self.kwargs = dict(device=device, **comm_kwargs(backend, self.rank, self.size, token))
+
+    def gather(self, functions):
+        """Rank 0: the given strip functions as functions on the global mesh (strips concatenate); None elsewhere."""
+        if self.size == 1:
+            return list(functions)
+        mine = [(f.function_space().coordinates, np.asarray(f.dat.data), f.name()) for f in functions]
+        got = [None] * self.size if self.rank == 0 else None
+        self.dist.gather_object(mine, got, dst=0)
+        if self.rank != 0:
+            return None
+        out = []
+        for n, f in enumerate(functions):
+            V = f.function_space()
+            xy = np.concatenate([g[n][0] for g in got])
+            Vg = FunctionSpace(V.mesh(), V.family, V.degree, xy, value_size=V.value_size)
+            out.append(Function(Vg, np.concatenate([g[n][1] for g in got]), got[0][n][2]))
+        return out
+
+    def close(self):
+        if self.dist is not None:
+            self.dist.barrier()
+            self.dist.destroy_process_group()
+            self.dist = None
 
 
 def report_solver_events(events):
@@ -100,9 +204,23 @@ def write_diagnostics(path, diag):
 
 
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
     if args.discretisation == "conforming":
         raise RuntimeError(f"discretisation '{args.discretisation}' is out of scope of the MI355X hot path")
+    check_multi_gpu(args)
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
+    ranks = _Ranks(args)
+    try:
+        # only rank 0 prints: the other ranks run the same (collective) calls with their output discarded
+        with contextlib.redirect_stdout(sys.stdout if ranks.rank == 0 else io.StringIO()):
+            return _run(args, ranks)
+    finally:
+        ranks.close()
+
+
+def _run(args, ranks):
     callbacks = [AnimationCallback("evolution.pvd")] if args.animation else None  # driver.py:187
     if args.problem == "shear":
         mesh = PeriodicSquareMesh(args.nx, args.nx, L=2 * np.pi, quadrilateral=False)  # driver.py:182-183
@@ -120,11 +238,11 @@ def main(argv=None):
     elif args.timestepper == "implicit":
         timestepper = IncompressibleEulerHDGImplicit(  # driver.py:220-228 (passes n_richardson: SURVEY C-1)
             mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, device=args.device)
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs)
     elif args.timestepper in TIMESTEPPERS:
         timestepper = TIMESTEPPERS[args.timestepper](
             mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, device=args.device)
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs)
     else:
         raise RuntimeError(f"Invalid timestepping method for HDG discretisation: '{args.timestepper}'")
 
@@ -193,7 +311,8 @@ def main(argv=None):
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
     if args.diagnostics:
         report_solver_events(eng.solver_events())
-        write_diagnostics(args.diagnostics, timestepper.diagnostics)
+        if ranks.rank == 0:
+            write_diagnostics(args.diagnostics, timestepper.diagnostics)
     log_summary()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here
@@ -202,7 +321,9 @@ def main(argv=None):
             Q.rename("velocity")
             p.rename("pressure")
             divQ = Function(timestepper._V_p, eng.apply_weak_divergence(Q.dat.data, broken=True), "divergence")
-            VTKFile(args.output).write(Q, p, divQ)
+            fields = ranks.gather([Q, p, divQ])
+            if fields is not None:
+                VTKFile(args.output).write(*fields)
         return 0
     if not args.warmup:
         Q.rename("velocity")
@@ -221,7 +342,9 @@ def main(argv=None):
             divQ = Function(timestepper._V_p, eng.apply_weak_divergence(Q.dat.data, broken=True), "divergence")
             Q_exact.rename("velocity_exact")
             p_exact.rename("pressure_exact")
-            VTKFile(args.output).write(Q, p, divQ, Q_exact, Q_error, p_exact, p_error)
+            fields = ranks.gather([Q, p, divQ, Q_exact, Q_error, p_exact, p_error])
+            if fields is not None:
+                VTKFile(args.output).write(*fields)
     return 0
 
 
