@@ -6,13 +6,20 @@ flux, Taylor-Green vortex with exponential forcing, dt = 0.25/nx; BASELINE.md se
 configuration named in ``config.workload`` -- by default C3: k = 2, 1024 x 1024 triangular mesh.
 All state is resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--nx 1024 --degree 2] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--nx 1024 --degree 2] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0) with the driver's contract plus ``roofline`` (dominant kernel, HIP
-events on the engine's stream) and ``cpu_baseline`` (the numpy/scipy oracle timed on a bounded
-sample of the same workload on this box's host cores, N = 1 only).  ``ms_per_step`` is the wall
-time of one of the K timed steps.  ``--dump-outputs DIR`` writes the fields the last timed step
-computed to DIR (see ``dump_outputs``), so that two builds can be compared output for output.
+Prints ONE JSON line (rank 0) with the driver's contract.  ``ms_per_step`` is the wall time of one
+of the K timed steps.  ``--dump-outputs DIR`` writes the fields the last timed step computed to DIR
+(see ``dump_outputs``), so that two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the dump
+and the line.  Besides the contract the line carries what the timed steps themselves recorded
+(Krylov iterations, solver events, section timers, and the whole-step roofline from the engine's
+launch census).  ``--full`` adds the measurements that take runs of their own: the dominant-kernel
+``roofline`` (HIP-event brackets around one extra step after the timed region, stand-alone launch
+loops), ``cpu_baseline`` (the C++/OpenMP CPU twin timed on a bounded sample of the same workload on
+the host's cores, N = 1 only; ``--no-cpu-baseline`` drops it) and, with BENCH_ALT_STOP=1, the
+``alt_stop_rule`` secondary number.
 
 ``--gpus N`` with N > 1 outside ``torch.distributed.run`` launches the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` started before anything touches
@@ -391,7 +398,7 @@ def alt_stop_rule(build, args, dt, kappa, mp, ssp2_scales, tol="1e-15"):
         del os.environ["HDG_TRACE_BACKWARD_TOL"]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults = the window the round driver uses; the first solves of a run still learn the Chebyshev check schedule
@@ -400,7 +407,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--nx", type=int, default=1024)
     ap.add_argument("--degree", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: kernel roofline, CPU baseline, BENCH_ALT_STOP")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--tent-precond", type=int, default=2)
     ap.add_argument("--trace-precond", type=int, default=1)
     ap.add_argument("--gmres-restart", type=int, default=8)
@@ -408,9 +417,14 @@ def main():
     ap.add_argument("--comm", choices=["rccl", "shm"], default="rccl", help="inter-rank transport for --gpus > 1")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the velocity and pressure of the last timed step to DIR/<name>.npy (dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])
@@ -529,9 +543,9 @@ def main():
     # engine's stream (hdg_set_kernel_timing: in place, with the operands and cache state of the solve); the roofline block
     # divides by these durations.  The brackets cost two event records per launch (about 1 % of a C3 step, 15 % at C2), so
     # by default they bracket ONE EXTRA step after the timed region: the headline does not pay for its own instrumentation.
-    # BENCH_KERNEL_TIMING=timed puts them into the timed steps instead.
+    # BENCH_KERNEL_TIMING=timed puts them into the timed steps instead.  Only --full times kernels at all.
     ktiming_extra = os.environ.get("BENCH_KERNEL_TIMING", "extra") == "extra"
-    eng.set_kernel_timing(not ktiming_extra)
+    eng.set_kernel_timing(args.full and not ktiming_extra)
     eng.launch_stats(reset=True)
     watchdog.arm("timed steps", float(os.environ.get("BENCH_STEP_TIMEOUT", "600")))
     sync_barrier()
@@ -547,7 +561,9 @@ def main():
     events = eng.solver_events()  # residual replacements / rounding-floor exits of the condensed solves in the timed steps
     launches = eng.launch_stats(reset=True)  # launch census of exactly the timed steps (this rank)
     timers_raw = eng.timers(reset=ktiming_extra, kernels=True)
-    if ktiming_extra:
+    if not args.full:
+        ktimers = None
+    elif ktiming_extra:
         eng.set_kernel_timing(True)
         eng.run_separable(ssp2_scales(1, dt, kappa, t0=(args.warmup + args.steps) * dt))
         ktimers = {lab: (n, tot) for lab, (n, tot, _) in eng.timers(reset=True, kernels=True).items() if lab.startswith("kernel_")}
@@ -565,7 +581,9 @@ def main():
         # device-side section timers of the timed steps (labels of the reference's PerformanceLog)
         timers = {lab: dict(ncall=n, total_ms=tot * 1e3, avg_ms=(tot / n * 1e3 if n else 0.0))
                   for lab, (n, tot, _) in timers_raw.items() if n}
-        roof = roofline_block(eng, args, nx, k, world, ktimers, "one extra step after the timed region" if ktiming_extra else "the timed steps")
+        # --full: the dominant kernel, from the brackets above and stand-alone launch loops
+        roof = roofline_block(eng, args, nx, k, world, ktimers, "one extra step after the timed region" if ktiming_extra
+                              else "the timed steps") if args.full else {}
         # Whole-step roofline (SURVEY.md section 8d / BASELINE.md section 2): sum_k calls_k * algorithmic_bytes_k / elapsed / peak,
         # from the engine's own launch census of the timed steps (every logical vector read or written once per launch,
         # 8 B per owned entry, shared operator tables free; this rank's strip x number of ranks).
@@ -592,12 +610,12 @@ def main():
             "roofline": roof,
             "timers": timers,
         }
-        if world == 1 and not os.environ.get("HDG_TRACE_BACKWARD_TOL") and os.environ.get("BENCH_ALT_STOP"):
-            # OPT-IN (BENCH_ALT_STOP=1) secondary number, never the headline: the same steps with the normwise backward-error stop
-            # of the condensed solves (Engine::pressure_solve) on a second engine.  It is a different
-            # stopping rule from the reference's rtol-only KSP (round-3 review): the default run does not spend time on it.
+        if args.full and world == 1 and not os.environ.get("HDG_TRACE_BACKWARD_TOL") and os.environ.get("BENCH_ALT_STOP"):
+            # OPT-IN (--full with BENCH_ALT_STOP=1) secondary number, never the headline: the same steps with the normwise
+            # backward-error stop of the condensed solves (Engine::pressure_solve) on a second engine.  It is
+            # a different stopping rule from the reference's rtol-only KSP (round-3 review): the default run does not spend time on it.
             line["alt_stop_rule"] = alt_stop_rule(build, args, dt, kappa, mp, ssp2_scales)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(k)
             # the GPU number at the CPU sample's size ("report DOF-updates/s at that size next to the
             # GPU number at the same size and at C3")

@@ -254,8 +254,8 @@ def test_section_timers_across_the_abi(hip_lib):
 
 
 def test_bench_line_contract(hip_lib):
-    """`python bench.py` prints ONE JSON line with the driver's keys, the roofline block (durations measured in place for
-    the two kernels of a tentative-velocity iteration) and, unless switched off, the CPU baseline with the reference's
+    """`python bench.py --full` prints ONE JSON line with the driver's keys, the roofline block (durations measured in place
+    for the two kernels of a tentative-velocity iteration) and, unless switched off, the CPU baseline with the reference's
     timer labels; run here on a small mesh (the schema does not depend on the size)."""
     import json
     import os
@@ -263,7 +263,7 @@ def test_bench_line_contract(hip_lib):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for k, extra in ((2, ["--no-cpu-baseline"]), (3, ["--no-cpu-baseline"])):
+    for k, extra in ((2, ["--full", "--no-cpu-baseline"]), (3, ["--full", "--no-cpu-baseline"])):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--nx", "64", "--degree", str(k), "--steps", "2", "--warmup", "1"] + extra,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -286,6 +286,32 @@ def test_bench_line_contract(hip_lib):
         assert ev["cg_residual_replacements"] == 0 and ev["cg_floor_exits"] == 0 and ev["sstep_gmres_fallbacks"] == 0 and ev["sstep_cycles"] >= 0
         assert d["config"]["kernel_forms"]["lift"] == (0 if k <= 2 else 2) and d["config"]["kernel_forms"]["trace_precond"] == 1
         assert "alt_stop_rule" not in d  # opt-in only (BENCH_ALT_STOP=1)
+
+
+def test_bench_plain_run_is_lean(hip_lib):
+    """A plain `python bench.py` (no --full) prints the same headline keys and what the timed steps recorded, and none of
+    the measurements that take runs of their own: no kernel roofline, no CPU baseline, no secondary stopping rule even when
+    BENCH_ALT_STOP asks for it."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--nx", "64", "--degree", "2", "--steps", "2", "--warmup", "1"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, BENCH_ALT_STOP="1"))
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "timers"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["unit"] == "million DOF-updates/s" and abs(d["value"] - d["config"]["n_dof"] * 2 / (d["ms_per_step"] * 2e-3) / 1e6) < 1e-6 * d["value"]
+    assert d["timers"]["timestep"]["ncall"] == 2 and not any(lab.startswith("kernel_") for lab in d["timers"])
+    assert set(d["roofline"]) == {"whole_step"} and d["roofline"]["whole_step"]["frac"] > 0
+    assert "cpu_baseline" not in d and "alt_stop_rule" not in d
 
 
 def test_bench_dump_outputs(hip_lib, tmp_path):

@@ -219,7 +219,7 @@ def test_bench_self_launch_reports_the_ranks_that_ran(hip_lib):
     root = os.path.dirname(HERE)
     ndev = torch.cuda.device_count()
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--nx", "64", "--degree", "1", "--steps", "1",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])

@@ -270,6 +270,22 @@ def test_bench_watchdog_ends_an_overrunning_phase():
     assert "stuck collective" in r.stderr.decode()
 
 
+def test_bench_runs_plain_unless_asked_for_full():
+    """bench.py measures only the headline by default; the kernel roofline, the CPU baseline and the secondary stopping rule
+    need --full.  The driver's window (20 timed steps after 5 warm-up steps) stays the default."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse_args([])
+    assert not a.full and not a.no_cpu_baseline and (a.steps, a.warmup, a.gpus, a.nx, a.degree) == (20, 5, 1, 1024, 2)
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
+    assert a.full and a.no_cpu_baseline and (a.steps, a.warmup) == (3, 1)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_bench_dump_outputs_samples_large_fields(tmp_path):
     """bench.dump_outputs on fields above its bound: float64 files of 64 MB at most, a sorted sample of distinct rows that is
     the same on every call, whole arrays when they fit, one file per array and rank."""

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"  # the kernel mix the committed profiles were taken on
 T="python3 $R/tools/time_kernels.py"
 # C3: kernel stats of the benchmark itself
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3_stats -o s -- $B --steps 5 --warmup 1 > $O/c3_stats.log 2>&1
@@ -35,7 +35,8 @@ rm -rf $O
 # the bench lines of the same build, with roofline.traffic from the file just written (same source hash)
 cp $S/pmc_traffic.json $R/profiles/pmc_traffic.json
 # (the driver's window: 20 timed steps after 5 warm-up steps -- the first solves of a run still learn their check schedule)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $S/${TAG}_bench_c3.json 2> $R/gpurun_out/bench_c3_$TAG.err
-python3 bench.py --degree 3 --nx 512 --steps 20 --warmup 5 --no-cpu-baseline > $S/${TAG}_bench_k3.json 2> $R/gpurun_out/bench_k3_$TAG.err
-python3 bench.py --degree 4 --nx 512 --steps 20 --warmup 5 --no-cpu-baseline > $S/${TAG}_bench_k4.json 2> $R/gpurun_out/bench_k4_$TAG.err
+L=$(dirname $S)  # their stderr next to the summaries
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $S/${TAG}_bench_c3.json 2> $L/bench_c3_$TAG.err
+python3 bench.py --degree 3 --nx 512 --steps 20 --warmup 5 --full --no-cpu-baseline > $S/${TAG}_bench_k3.json 2> $L/bench_k3_$TAG.err
+python3 bench.py --degree 4 --nx 512 --steps 20 --warmup 5 --full --no-cpu-baseline > $S/${TAG}_bench_k4.json 2> $L/bench_k4_$TAG.err
 ls $S

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pmcprobe_$TAG
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $O -o p -- python3 $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O.log 2>&1
+rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $O -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O.log 2>&1
 cd $R
 python3 - "$O" <<'PY'
 import csv, glob, sys, collections
