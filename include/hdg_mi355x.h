@@ -312,6 +312,35 @@ int hdg_compute_diagnostics(hdg_handle* h, const double* Q, const double* p, con
 int hdg_set_diagnostics(hdg_handle* h, int capacity);
 int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset);
 
+/* ---- point values.  Five columns per point (x, y):
+ *   0 ux  1 uy  2 p  3 q  4 omega = d_x uy - d_y ux, the curl of the broken velocity inside the cell that owns the point
+ *   (not the continuous vorticity of the animation callback).  A column whose field is not given is NaN (q without a tracer).
+ * Ownership (the fields are discontinuous across cell boundaries):
+ *   square meshes: i = min(floor(x / h), nx - 1), j = min(floor(y / h), ny - 1), fx = x / h - i, fy = y / h - j; the lower
+ *     triangle when fx + fy <= 1, the upper one otherwise.  Periodic square: x, y first wrapped into [0, L) (a value that
+ *     rounds to L becomes 0).  Unit square: a point more than 1e-12 L outside [0, L]^2 lies outside the domain, one within
+ *     that tolerance is clamped onto the boundary.
+ *   general meshes: the lowest-numbered cell whose barycentric coordinates are all >= -1e-12; none: outside the domain
+ *     (on the disk also the points inside the circle but outside the polygon).
+ *   strip partitions: the rank that owns the cell row of the rule above (a point on a cut goes to the upper rank); the
+ *     values do not depend on the number of ranks.
+ * hdg_evaluate_points: the n rows of nodal fields (layouts of hdg_set_state; any of Q, p, q may be NULL: NaN columns) at
+ *   xy[2 n] into out[5 n]; located[i] = 1, or 0 for a point outside the domain (a NaN row, not an error).  Strip partitions:
+ *   collective, every rank passes its own strip of the fields and the same points, and receives all n rows.
+ * hdg_set_probes: capacity > 0 switches per-step recording of the n points on into a device buffer of `capacity` rows of
+ *   5 n values and records the current state as the first row; every completed step then appends one row at the points where
+ *   hdg_set_diagnostics takes its rows (the two describe the same state).  n = 0 or capacity = 0 switches recording off.
+ *   A point outside the domain returns HDG_ERR_ARG (its index in the message) and leaves recording off, as does a buffer of
+ *   more than HDG_MAX_PROBE_VALUES values (n x capacity x 5).
+ * hdg_get_probes: copies min(*n_rows, max_rows) recorded rows (5 n doubles each, point-major) to `rows`, *n_rows = rows
+ *   recorded; reset != 0 empties the buffer.  Returns HDG_ERR_ARG (rows and *n_rows still filled) when rows were dropped. */
+#define HDG_N_POINT_COLUMNS 5
+#define HDG_MAX_PROBE_VALUES (1L << 27)
+int hdg_evaluate_points(hdg_handle* h, const double* Q, const double* p, const double* q, int n, const double* xy,
+                        double* out, int* located);
+int hdg_set_probes(hdg_handle* h, int n, const double* xy, int capacity);
+int hdg_get_probes(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset);
+
 /* kernel-level access for parity tests and micro-benchmarks (nodal in / nodal out) */
 int hdg_apply_advection(hdg_handle* h, const double* Qstar, const double* x, double gamma, double* y);
 int hdg_apply_trace_operator(hdg_handle* h, const double* lam, double* out);

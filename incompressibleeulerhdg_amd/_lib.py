@@ -33,6 +33,10 @@ HDG_COMM_SHM = 2
 DIAGNOSTICS = ("energy", "enstrophy", "div_l2", "jump_l2", "p_integral", "tracer_integral", "tracer_half_sq", "max_speed", "cfl")
 
 
+# columns of hdg_evaluate_points / hdg_get_probes
+POINT_COLUMNS = ("ux", "uy", "p", "q", "omega")
+
+
 class HDGError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERRORS.get(code, code)}: {msg}")
@@ -80,7 +84,7 @@ class hdg_config(C.Structure):
 
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
-    srcs = [SRC, HEADER] + [os.path.join(_HERE, "csrc", f) for f in ("hdg_kernels.hpp", "hdg_schur_mfma.hpp", "hdg_tables.hpp", "hdg_comm.hpp", "hdg_cg.hpp", "hdg_general.hpp", "hdg_general_kernels.hpp", "hdg_trace_tile.hpp", "hdg_trace_tile3.hpp", "hdg_side_rows.hpp", "hdg_amg.hpp", "hdg_diagnostics.hpp")]
+    srcs = [SRC, HEADER] + [os.path.join(_HERE, "csrc", f) for f in ("hdg_kernels.hpp", "hdg_schur_mfma.hpp", "hdg_tables.hpp", "hdg_comm.hpp", "hdg_cg.hpp", "hdg_general.hpp", "hdg_general_kernels.hpp", "hdg_trace_tile.hpp", "hdg_trace_tile3.hpp", "hdg_side_rows.hpp", "hdg_amg.hpp", "hdg_diagnostics.hpp", "hdg_points.hpp", "hdg_probes.hpp")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -159,6 +163,9 @@ SIGNATURES = {
     "hdg_compute_diagnostics": [_h, _dp, _dp, _dp, _dp],
     "hdg_set_diagnostics": [_h, C.c_int],
     "hdg_get_diagnostics": [_h, _dp, C.c_int, _ip, C.c_int],
+    "hdg_evaluate_points": [_h, _dp, _dp, _dp, C.c_int, _dp, _dp, _ip],
+    "hdg_set_probes": [_h, C.c_int, _dp, C.c_int],
+    "hdg_get_probes": [_h, _dp, C.c_int, _ip, C.c_int],
 }
 
 
@@ -581,6 +588,47 @@ class Engine:
         rows = np.empty((n.value, len(DIAGNOSTICS)))
         self._ck(self.lib.hdg_get_diagnostics(self.h, _ptr(rows) if n.value else None, n.value, C.byref(n),
                                               1 if reset else 0))
+        return rows
+
+    # --- point values (include/hdg_mi355x.h: hdg_evaluate_points / hdg_set_probes / hdg_get_probes)
+    @staticmethod
+    def _points(xy):
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+        return xy
+
+    def evaluate_points(self, xy, Q=None, p=None, q=None):
+        """Values at the points xy (n, 2) of nodal fields (any may be None: NaN columns): (values (n, 5) in POINT_COLUMNS
+        order, located (n,) bool).  A point outside the domain has a NaN row and located False.  Collective on strips."""
+        xy = self._points(xy)
+        Q = None if Q is None else _arr(Q, self.shape_Q)
+        p = None if p is None else _arr(p, self.shape_p)
+        q = None if q is None else _arr(q, self.shape_p)
+        n = len(xy)
+        out = np.empty((n, len(POINT_COLUMNS)))
+        located = np.zeros(n, dtype=np.int32)
+        self._ck(self.lib.hdg_evaluate_points(self.h, _ptr(Q), _ptr(p), _ptr(q), n, _ptr(xy), _ptr(out),
+                                              located.ctypes.data_as(_ip)))
+        return out, located.astype(bool)
+
+    def set_probes(self, xy, capacity):
+        """Record the values at the points xy (n, 2) after every completed step into a device buffer of `capacity` rows (the
+        current state is the first row); capacity 0 or no points switches recording off.  Raises HDGError (HDG_ERR_ARG) for
+        a point outside the domain."""
+        xy = self._points(xy) if xy is not None else np.zeros((0, 2))
+        self._n_probes = 0
+        self._ck(self.lib.hdg_set_probes(self.h, len(xy), _ptr(xy), int(capacity)))
+        self._n_probes = len(xy) if capacity > 0 else 0
+
+    def probes(self, reset=True):
+        """The recorded rows, (rows, n, 5) in POINT_COLUMNS order.  Raises HDGError when rows were dropped."""
+        npts = getattr(self, "_n_probes", 0)
+        n = C.c_int(0)
+        rc = self.lib.hdg_get_probes(self.h, None, 0, C.byref(n), 0)  # the row count (dropped rows: the call below)
+        if rc not in (0, -1):
+            self._ck(rc)
+        rows = np.empty((n.value, npts, len(POINT_COLUMNS)))
+        self._ck(self.lib.hdg_get_probes(self.h, _ptr(rows) if n.value and npts else None, n.value if npts else 0,
+                                         C.byref(n), 1 if reset else 0))
         return rows
 
     def time_kernel(self, kernel, reps):

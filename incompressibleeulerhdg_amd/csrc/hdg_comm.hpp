@@ -49,6 +49,7 @@ struct Comm {
   // into rlo (from lower()) and rhi (from upper()).  Missing neighbours are skipped.
   virtual void exchange(const double* slo, double* rlo, const double* shi, double* rhi, size_t n, hipStream_t st) {}
   virtual void allreduce_sum(double* dev, int n, hipStream_t st) {}
+  virtual int allreduce_max() const { return 1 << 30; }  // most scalars one allreduce_sum takes
   // every rank contributes n doubles; recv holds size*n doubles in rank order
   virtual void allgather(const double* send, double* recv, size_t n, hipStream_t st) {
     if (send != recv) (void)hipMemcpyAsync(recv, send, n * sizeof(double), hipMemcpyDeviceToDevice, st);
@@ -227,6 +228,7 @@ struct CommShm : Comm {
     (void)hipStreamSynchronize(st);
     hdr(rank)->halo_read.store(e, std::memory_order_release);
   }
+  int allreduce_max() const override { return 64; }
   void allreduce_sum(double* dev, int n, hipStream_t st) override {
     if (n > 64) throw CommError{"allreduce of more than 64 scalars"};
     const uint64_t e = ++e_red;

@@ -38,6 +38,7 @@
 #include "hdg_general_kernels.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
+#include "hdg_probes.hpp"
 
 namespace hdg {
 
@@ -587,6 +588,7 @@ struct Engine {
     delete gm; gm = nullptr;
     delete gtab; gtab = nullptr;
     delete gcg; gcg = nullptr;
+    delete glocator; glocator = nullptr;
   }
   void construct(const hdg_config& c) {
     K = c.degree;
@@ -4365,6 +4367,116 @@ struct Engine {
     HIPCHECK(hipStreamSynchronize(stream));
   }
 
+  // ------------------------------------------------------------------ point values (hdg_points.hpp, hdg_probes.hpp)
+  // A point set is located on the host once (every rank locates every point, the same way) into a device table; one launch
+  // per row evaluates it (strip partitions: one all-reduce sum of the row).  Probe recording (pt_cap > 0) appends one row per
+  // completed step at end_of_step, next to the diagnostics row; switched off, a step issues no launch more.
+  struct PointSet {
+    int n = 0, alloc = 0;
+    PointLoc* dev = nullptr;
+  };
+  PointSet pt_eval, pt_probe;
+  GLocator* glocator = nullptr;
+  double *pt_out = nullptr, *pt_rows = nullptr, *pt_Qw = nullptr, *pt_pw = nullptr, *pt_qw = nullptr;
+  long pt_out_alloc = 0, pt_rows_alloc = 0, pt_n = 0, pt_dropped = 0;
+  int pt_cap = 0;
+  // located[i] = 1 / 0; throws nothing for an outside point (PT_OUTSIDE)
+  void points_locate(int n, const double* xy, PointSet& ps, int* located) {
+    if (n < 0 || (n > 0 && !xy)) throw std::string("points: bad arguments");
+    std::vector<PointLoc> loc((size_t)n);
+    if (general && !glocator) { glocator = new GLocator(); glocator->build(*gm); }
+    for (int t = 0; t < n; t++) {
+      PointLoc& L = loc[(size_t)t];
+      L.xi = L.eta = 0.0; L.c = 0; L.s = PT_OUTSIDE; L.pad = 0;
+      const double x = xy[2 * (size_t)t], y = xy[2 * (size_t)t + 1];
+      if (general) {
+        const int c = glocator->locate(*gm, x, y, POINT_TOL, L.xi, L.eta);
+        if (c >= 0) { L.c = c; L.s = 0; }
+      } else {
+        int i, j, s;
+        if (square_locate(x, y, g.nx, cfg.ny, Ldom, periodic, i, j, s, L.xi, L.eta)) {
+          const int r = j / g.ny;  // the rank that owns cell row j
+          if (r == comm->rank) { L.c = ((long)s * g.R + (j - r * g.ny + GH)) * g.nx + i; L.s = s; }
+          else L.s = PT_OTHER_RANK;
+        }
+      }
+      if (located) located[t] = L.s == PT_OUTSIDE ? 0 : 1;
+    }
+    if (n > ps.alloc) {
+      ps.dev = (PointLoc*)dalloc(((long)n * sizeof(PointLoc) + 7) / 8);
+      ps.alloc = n;
+    }
+    ps.n = n;
+    if (n > 0) {
+      HIPCHECK(hipMemcpyAsync(ps.dev, loc.data(), sizeof(PointLoc) * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+    }
+  }
+  // one row (ps.n x POINT_NCOL) of the modal device fields Q, p, q (any may be null: NaN columns) into the device row `row`
+  void points_pass(const PointSet& ps, const double* Q, const double* p, const double* q, double* row) {
+    if (ps.n == 0) return;
+    const int nb = (ps.n + POINT_BLOCK - 1) / POINT_BLOCK;
+    tally(LC_OTHER, 0.0);
+    if (general) {
+      HDG_DISPATCH(k_g_point_eval<KK><<<nb, POINT_BLOCK, 0, stream>>>(ggeo, ps.n, ps.dev, Q, p, q, row));
+    } else {
+      HDG_DISPATCH(k_point_eval<KK><<<nb, POINT_BLOCK, 0, stream>>>(ps.n, ps.dev, g.Nc, g.h, Q, p, q, row));
+    }
+    if (comm->size > 1) {  // every entry has one non-zero contributor: the sum is the owner's value on every rank
+      const int total = POINT_NCOL * ps.n, chunk = comm->allreduce_max();  // the shared-memory transport: 64 per call
+      for (int off = 0; off < total; off += chunk) {
+        comm->allreduce_sum(row + off, std::min(chunk, total - off), stream);
+        n_reduce++;
+      }
+    }
+  }
+  void points_evaluate(const double* Q, const double* p, const double* q, int n, const double* xy, double* out, int* located) {
+    points_locate(n, xy, pt_eval, located);
+    if ((long)n * POINT_NCOL > pt_out_alloc) { pt_out = dalloc((long)n * POINT_NCOL); pt_out_alloc = (long)n * POINT_NCOL; }
+    if (Q) { if (!pt_Qw) pt_Qw = dalloc(NQ); put_Q(Q, pt_Qw); }
+    if (p) { if (!pt_pw) pt_pw = dalloc(NPv); put_P(p, pt_pw); }
+    if (q) { if (!pt_qw) pt_qw = dalloc(NPv); put_P(q, pt_qw); }
+    points_pass(pt_eval, Q ? pt_Qw : nullptr, p ? pt_pw : nullptr, q ? pt_qw : nullptr, pt_out);
+    if (n > 0) HIPCHECK(hipMemcpyAsync(out, pt_out, sizeof(double) * POINT_NCOL * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  void probe_record() {
+    if (pt_cap <= 0) return;
+    if (pt_n >= pt_cap) { pt_dropped++; return; }
+    points_pass(pt_probe, curQ, curP, tracer_on ? q_cur : nullptr, pt_rows + pt_n * POINT_NCOL * pt_probe.n);
+    pt_n++;
+  }
+  void probe_set(int n, const double* xy, int cap) {
+    if (n < 0 || cap < 0) throw std::string("probes: n and capacity must be >= 0");
+    pt_cap = 0; pt_n = 0; pt_dropped = 0;
+    if (n == 0 || cap == 0) { pt_probe.n = 0; return; }
+    if ((double)n * cap * POINT_NCOL > (double)HDG_MAX_PROBE_VALUES)
+      throw std::string("probes: ") + std::to_string(n) + " points x " + std::to_string(cap) + " rows x " +
+          std::to_string(POINT_NCOL) + " values exceed the limit of " + std::to_string((long)HDG_MAX_PROBE_VALUES) + " values";
+    std::vector<int> located((size_t)n);
+    points_locate(n, xy, pt_probe, located.data());
+    for (int t = 0; t < n; t++)
+      if (!located[(size_t)t]) {
+        pt_probe.n = 0;
+        throw std::string("probes: point ") + std::to_string(t) + " (" + std::to_string(xy[2 * (size_t)t]) + ", " +
+            std::to_string(xy[2 * (size_t)t + 1]) + ") lies outside the domain";
+      }
+    const long need = (long)n * cap * POINT_NCOL;
+    if (need > pt_rows_alloc) { pt_rows = dalloc(need); pt_rows_alloc = need; }
+    pt_cap = cap;
+    probe_record();  // row 0: the state as it is now
+  }
+  void probe_fetch(double* rows, long nrows) {
+    if (nrows > 0)
+      HIPCHECK(hipMemcpyAsync(rows, pt_rows, sizeof(double) * POINT_NCOL * pt_probe.n * nrows, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  // end of a completed step: the diagnostics row and the probe row of the same state
+  void end_of_step() {
+    diag_record();
+    probe_record();
+  }
+
   // ------------------------------------------------------------------ host <-> device fields
   long n_edges() const {
     if (general) return gm->ne;
@@ -4767,13 +4879,13 @@ int hdg_stage_update(hdg_handle* h, int stage) {
 int hdg_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.finish_step();
-  if (!E.tracer_on) E.diag_record();  // with a tracer the row is taken after hdg_tracer_finish_step
+  if (!E.tracer_on) E.end_of_step();  // with a tracer the rows are taken after hdg_tracer_finish_step
   HDG_API_END(h)
 }
 int hdg_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.step();
-  E.diag_record();
+  E.end_of_step();
   HDG_API_END(h)
 }
 int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
@@ -4782,7 +4894,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
   for (int n = 0; n < nsteps; n++) {
     for (int sl = 0; sl <= E.s; sl++) { E.bscale[sl] = scales[(long)n * (E.s + 1) + sl]; E.bsep[sl] = 1; }
     E.step();
-    E.diag_record();
+    E.end_of_step();
     E.harvest_completed();  // keeps the number of live timer events bounded over a long run
   }
   HDG_API_END(h)
@@ -4790,7 +4902,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
 int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure) {
   HDG_API_BEGIN(h)
   E.implicit_step(its_tentative, its_pressure);
-  E.diag_record();
+  E.end_of_step();
   HDG_API_END(h)
 }
 // ---- implicit DG discretisation (dg_implicit.py:10-136), single rank
@@ -4805,7 +4917,7 @@ int hdg_dg_implicit_step(hdg_handle* h, int* its) {
   if (int rc = dg_single_rank(h)) return rc;
   HDG_API_BEGIN(h)
   E.dg_implicit_step(its);
-  E.diag_record();
+  E.end_of_step();
   HDG_API_END(h)
 }
 int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
@@ -4923,7 +5035,7 @@ int hdg_tracer_stage(hdg_handle* h, int stage) {
 int hdg_tracer_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.tracer_finish_step();
-  if (E.tracer_on) E.diag_record();
+  if (E.tracer_on) E.end_of_step();
   HDG_API_END(h)
 }
 int hdg_cg_size(hdg_handle* h, long* n_cg) {
@@ -5052,6 +5164,32 @@ int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, 
   if (dropped > 0)
     throw std::string("diagnostics: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
         std::to_string(E.diag_cap) + " rows";
+  HDG_API_END(h)
+}
+int hdg_evaluate_points(hdg_handle* h, const double* Q, const double* p, const double* q, int n, const double* xy, double* out,
+                        int* located) {
+  HDG_API_BEGIN(h)
+  if (n < 0 || (n > 0 && (!xy || !out || !located))) throw std::string("null argument");
+  E.points_evaluate(Q, p, q, n, xy, out, located);
+  HDG_API_END(h)
+}
+int hdg_set_probes(hdg_handle* h, int n, const double* xy, int capacity) {
+  HDG_API_BEGIN(h)
+  if (n > 0 && capacity > 0 && !xy) throw std::string("null argument");
+  E.probe_set(n, xy, capacity);
+  HDG_API_END(h)
+}
+int hdg_get_probes(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset) {
+  HDG_API_BEGIN(h)
+  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
+  const long n = E.pt_n, dropped = E.pt_dropped;
+  const long ncopy = std::min<long>(n, max_rows);
+  E.probe_fetch(rows, ncopy);
+  if (n_rows) *n_rows = (int)n;
+  if (reset) { E.pt_n = 0; E.pt_dropped = 0; }
+  if (dropped > 0)
+    throw std::string("probes: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
+        std::to_string(E.pt_cap) + " rows";
   HDG_API_END(h)
 }
 int hdg_time_kernel(hdg_handle* h, int kernel, int reps, double* ms_per_launch) {

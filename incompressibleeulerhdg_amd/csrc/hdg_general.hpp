@@ -184,6 +184,84 @@ struct GMesh {
 };
 
 // ------------------------------------------------------------------------------------------
+// point location (hdg_evaluate_points / hdg_set_probes): a point belongs to the lowest-numbered cell
+// whose barycentric coordinates are all >= -tol (tol = 1e-12); none: outside the domain.  A uniform grid of about one bucket
+// per cell over the bounding box of the mesh lists, in ascending order, every cell whose bounding box (widened by a margin
+// far above what tol allows) meets the bucket, so the first cell of the point's bucket that passes the test is the lowest.
+// ------------------------------------------------------------------------------------------
+// reference coordinates of (x, y) in cell c (x = v0 + J (xi, eta)) and whether all barycentric coordinates are >= -tol
+inline bool gcell_contains(const GMesh& M, int c, double x, double y, double tol, double& xi, double& eta) {
+  const int v0 = M.C[3 * (size_t)c];
+  const double dx = x - M.X[2 * (size_t)v0], dy = y - M.X[2 * (size_t)v0 + 1];
+  const double* Ji = &M.Jinv[4 * (size_t)c];
+  xi = Ji[0] * dx + Ji[1] * dy;
+  eta = Ji[2] * dx + Ji[3] * dy;
+  return xi >= -tol && eta >= -tol && 1.0 - xi - eta >= -tol;
+}
+inline int gcell_brute_force(const GMesh& M, double x, double y, double tol, double& xi, double& eta) {
+  for (int c = 0; c < M.nc; c++)
+    if (gcell_contains(M, c, x, y, tol, xi, eta)) return c;
+  return -1;
+}
+struct GLocator {
+  double x0 = 0, y0 = 0, bw = 1, bh = 1;
+  int nbx = 1, nby = 1;
+  std::vector<int> start, items;  // bucket b lists items[start[b] .. start[b + 1] - 1]
+  void build(const GMesh& M) {
+    double x1 = M.X[0], y1 = M.X[1];
+    x0 = x1; y0 = y1;
+    for (int v = 0; v < M.nv; v++) {
+      x0 = std::min(x0, M.X[2 * (size_t)v]); x1 = std::max(x1, M.X[2 * (size_t)v]);
+      y0 = std::min(y0, M.X[2 * (size_t)v + 1]); y1 = std::max(y1, M.X[2 * (size_t)v + 1]);
+    }
+    const double w = std::max(x1 - x0, 1e-300), hgt = std::max(y1 - y0, 1e-300);
+    const double side = std::sqrt(w * hgt / std::max(M.nc, 1));
+    nbx = std::max(1, std::min(4096, (int)std::ceil(w / side)));
+    nby = std::max(1, std::min(4096, (int)std::ceil(hgt / side)));
+    bw = w / nbx; bh = hgt / nby;
+    const double margin = 1e-6 * std::max(w, hgt);
+    std::vector<int> cnt((size_t)nbx * nby + 1, 0);
+    auto range = [&](int c, int& i0, int& i1, int& j0, int& j1) {
+      double a0 = 1e300, a1 = -1e300, b0 = 1e300, b1 = -1e300;
+      for (int l = 0; l < 3; l++) {
+        const int v = M.C[3 * (size_t)c + l];
+        a0 = std::min(a0, M.X[2 * (size_t)v]); a1 = std::max(a1, M.X[2 * (size_t)v]);
+        b0 = std::min(b0, M.X[2 * (size_t)v + 1]); b1 = std::max(b1, M.X[2 * (size_t)v + 1]);
+      }
+      i0 = bucket(a0 - margin, x0, bw, nbx); i1 = bucket(a1 + margin, x0, bw, nbx);
+      j0 = bucket(b0 - margin, y0, bh, nby); j1 = bucket(b1 + margin, y0, bh, nby);
+    };
+    for (int c = 0; c < M.nc; c++) {
+      int i0, i1, j0, j1;
+      range(c, i0, i1, j0, j1);
+      for (int j = j0; j <= j1; j++)
+        for (int i = i0; i <= i1; i++) cnt[(size_t)j * nbx + i + 1]++;
+    }
+    for (size_t b = 1; b < cnt.size(); b++) cnt[b] += cnt[b - 1];
+    start = cnt;
+    items.assign((size_t)cnt.back(), 0);
+    for (int c = 0; c < M.nc; c++) {  // ascending cell numbers within every bucket
+      int i0, i1, j0, j1;
+      range(c, i0, i1, j0, j1);
+      for (int j = j0; j <= j1; j++)
+        for (int i = i0; i <= i1; i++) items[(size_t)cnt[(size_t)j * nbx + i]++] = c;
+    }
+  }
+  static int bucket(double x, double o, double w, int n) {
+    const double t = std::floor((x - o) / w);
+    return t < 0 ? 0 : (t > n - 1 ? n - 1 : (int)t);
+  }
+  // the owning cell (and the reference coordinates in it), -1 outside the domain
+  int locate(const GMesh& M, double x, double y, double tol, double& xi, double& eta) const {
+    if (!(std::isfinite(x) && std::isfinite(y))) return -1;
+    const size_t b = (size_t)bucket(y, y0, bh, nby) * nbx + bucket(x, x0, bw, nbx);
+    for (int q = start[b]; q < start[b + 1]; q++)
+      if (gcell_contains(M, items[(size_t)q], x, y, tol, xi, eta)) return items[(size_t)q];
+    return -1;
+  }
+};
+
+// ------------------------------------------------------------------------------------------
 // reference tabulations shared by all cells, and the per-cell local matrices built from them
 // ------------------------------------------------------------------------------------------
 struct GeneralTables {

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from ._lib import DIAGNOSTICS
+from ._lib import DIAGNOSTICS, POINT_COLUMNS
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
@@ -78,6 +78,11 @@ def build_parser():
     parser.add_argument("--diagnostics", metavar="FILE", type=str, default=None,
                         help="record energy, enstrophy, divergence, jumps, integrals, maximum speed and CFL number of every "
                              "step on the device and write them to FILE (CSV); also prints the solver events")
+    parser.add_argument("--probes", metavar="FILE", type=str, default=None,
+                        help="record velocity, pressure, tracer and cell-local vorticity at the points of FILE (one 'x y' per "
+                             "line, '#' starts a comment) after every step on the device")
+    parser.add_argument("--probe_output", metavar="CSV", type=str, default="probes.csv",
+                        help="CSV the --probes time series is written to")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -203,6 +208,39 @@ def write_diagnostics(path, diag):
     print()
 
 
+def read_probe_points(path):
+    """Points of a --probes file: one 'x y' per line, '#' starts a comment, blank lines are skipped.  Returns (xy (n, 2),
+    the line number of every point)."""
+    pts, lines = [], []
+    with open(path) as f:
+        for lineno, line in enumerate(f, start=1):
+            line = line.split("#", 1)[0].strip()
+            if not line:
+                continue
+            fields = line.replace(",", " ").split()
+            if len(fields) != 2:
+                raise RuntimeError(f"{path}:{lineno}: expected 'x y', got {line!r}")
+            pts.append((float(fields[0]), float(fields[1])))
+            lines.append(lineno)
+    if not pts:
+        raise RuntimeError(f"{path}: no points")
+    return np.array(pts, dtype=float), lines
+
+
+def write_probes(path, probes):
+    """CSV with one row per recorded state and point: step, t, point, x, y and the five point values."""
+    t, xy = probes["t"], probes["xy"]
+    with open(path, "w") as f:
+        f.write(",".join(["step", "t", "point", "x", "y"] + list(POINT_COLUMNS)) + "\n")
+        for i in range(len(t)):
+            for n in range(len(xy)):
+                vals = [probes["u"][i, n, 0], probes["u"][i, n, 1], probes["p"][i, n], probes["q"][i, n], probes["omega"][i, n]]
+                f.write(",".join([str(i), repr(float(t[i])), str(n), repr(float(xy[n, 0])), repr(float(xy[n, 1]))]
+                                 + [repr(float(v)) for v in vals]) + "\n")
+    print(f"probes ({len(t)} rows x {len(xy)} points) written to {path}")
+    print()
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
@@ -308,11 +346,20 @@ def _run(args, ranks):
     kw = {"fused": True} if (args.fused and args.timestepper != "implicit") else {}
     if args.diagnostics:
         kw["diagnostics"] = True
+    if args.probes:
+        xy, lines = read_probe_points(args.probes)
+        _, located = eng.evaluate_points(xy)  # collective on strips; stops the run before the first step
+        if not np.all(located):
+            bad = int(np.flatnonzero(~located)[0])
+            raise RuntimeError(f"{args.probes}:{lines[bad]}: probe point ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
+        kw["probes"] = xy
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
     if args.diagnostics:
         report_solver_events(eng.solver_events())
         if ranks.rank == 0:
             write_diagnostics(args.diagnostics, timestepper.diagnostics)
+    if args.probes and ranks.rank == 0:
+        write_probes(args.probe_output, timestepper.probes)
     log_summary()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here

@@ -7,7 +7,8 @@ to the timestepper constructors; ``driver.py`` and ``model_problems.py`` then re
 
 import numpy as np
 
-__all__ = ["UnitSquareMesh", "PeriodicSquareMesh", "TriangleMesh", "UnitDiskMesh", "FunctionSpace", "Function"]
+__all__ = ["UnitSquareMesh", "PeriodicSquareMesh", "TriangleMesh", "UnitDiskMesh", "FunctionSpace", "Function",
+           "PointNotInDomainError"]
 
 
 class UnitSquareMesh:
@@ -98,6 +99,14 @@ class UnitDiskMesh(TriangleMesh):
         self.refinement_level = int(refinement_level)
 
 
+class PointNotInDomainError(ValueError):
+    """A point given to ``Function.at`` lies outside the domain (Firedrake's exception of that name)."""
+
+    def __init__(self, points):
+        self.points = points
+        super().__init__(f"point(s) not in the domain: {points}")
+
+
 class _Dat:
     def __init__(self, data):
         self.data = data
@@ -148,3 +157,30 @@ class Function:
 
     def name(self):
         return self._name
+
+    def at(self, *args, dont_raise=False):
+        """Values at points, evaluated on the device (Firedrake: ``Function.at``).  ``f.at(x, y)``, ``f.at((x, y))`` and
+        ``f.at([[x, y], ...])`` are accepted.  A single point gives a float (scalar) or an array (2,) (velocity); several
+        points an array (n,) or (n, 2).  A point outside the domain raises PointNotInDomainError, or with ``dont_raise=True``
+        gives None in a list.  The velocity is the broken field inside the cell that owns the point.
+        On strip partitions the call is collective.  Only functions on a stepper's velocity and pressure / tracer spaces."""
+        eng = getattr(self._space, "_engine", None)
+        if eng is None:
+            raise NotImplementedError("Function.at: only functions on a timestepper's _V_Q, _V_p and _V_q")
+        pts = np.asarray(args[0] if len(args) == 1 else args, dtype=float)
+        single = pts.ndim == 1
+        if pts.shape[-1] != 2 or pts.ndim > 2:
+            raise ValueError(f"Function.at: points of two coordinates expected, got shape {pts.shape}")
+        xy = pts.reshape(-1, 2)
+        vec = self._space.value_size == 2
+        data = np.asarray(self.dat.data, dtype=float)
+        vals, located = eng.evaluate_points(xy, Q=data if vec else None, p=None if vec else data)
+        vals = vals[:, 0:2] if vec else vals[:, 2]
+        if not np.all(located):
+            if not dont_raise:
+                raise PointNotInDomainError([tuple(x) for x in xy[~located]])
+            out = [((v.copy() if vec else float(v)) if ok else None) for v, ok in zip(vals, located)]
+            return out[0] if single else out
+        if single:
+            return vals[0].copy() if vec else float(vals[0])
+        return vals.copy()

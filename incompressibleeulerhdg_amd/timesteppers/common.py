@@ -7,7 +7,7 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from .._lib import DIAGNOSTICS, Engine
+from .._lib import DIAGNOSTICS, POINT_COLUMNS, Engine
 from ..mesh import Function, FunctionSpace
 
 __all__ = ["IncompressibleEuler"]
@@ -31,6 +31,7 @@ class IncompressibleEuler(ABC):
         # common.py:72-73
         self.domain_volume = float(mesh.volume) if getattr(mesh, "general", False) else float(getattr(mesh, "L", 1.0)) ** 2
         self.diagnostics = None  # solve(..., diagnostics=True): dict of the recorded series
+        self.probes = None  # solve(..., probes=xy): dict of the recorded point values
 
     # -- engine and function spaces ------------------------------------------------------------
     def _create_engine(self, **kw):
@@ -131,6 +132,34 @@ class IncompressibleEuler(ABC):
         for i, name in enumerate(DIAGNOSTICS):
             self.diagnostics[name] = rows[:, i].copy()
 
+    # -- point values (include/hdg_mi355x.h: hdg_evaluate_points / hdg_set_probes) ------------------
+    def evaluate_points(self, xy, Q=None, p=None, q=None):
+        """Values of the given fields (what _as_nodal_* accepts, None: NaN) at the points xy (n, 2), computed on the device:
+        (values (n, 5) in ``_lib.POINT_COLUMNS`` order, located (n,) bool)."""
+        return self._engine.evaluate_points(xy, None if Q is None else self._as_nodal_velocity(Q),
+                                            None if p is None else self._as_nodal_pressure(p),
+                                            None if q is None else self._as_nodal_pressure(q))
+
+    def _start_probes(self, probes, nt):
+        """Record nt + 1 rows of point values on the device: the current state (row 0) and the state after every step."""
+        self.probes = None
+        if probes is not None:
+            self._engine.set_probes(np.asarray(probes, dtype=float).reshape(-1, 2), nt + 1)
+
+    def _finish_probes(self, probes):
+        """Fetch the recorded rows once (self.probes: t, xy, u (nt+1, n, 2), p, q, omega (nt+1, n)) and switch recording
+        off."""
+        if probes is None:
+            return
+        try:
+            rows = self._engine.probes(reset=True)
+        finally:
+            self._engine.set_probes(None, 0)
+        c = {name: i for i, name in enumerate(POINT_COLUMNS)}
+        self.probes = {"t": np.arange(rows.shape[0]) * self._dt, "xy": np.asarray(probes, dtype=float).reshape(-1, 2).copy(),
+                       "u": rows[:, :, [c["ux"], c["uy"]]].copy(), "p": rows[:, :, c["p"]].copy(),
+                       "q": rows[:, :, c["q"]].copy(), "omega": rows[:, :, c["omega"]].copy()}
+
     @abstractmethod
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""

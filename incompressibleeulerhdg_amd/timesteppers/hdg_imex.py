@@ -122,13 +122,15 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
             self._engine.set_forcing_nodal(slot, self._as_nodal_velocity(f_rhs(t)))
 
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None):
         """Propagate the solution to T_final with nt timesteps; returns (Q, p).
 
         ``fused=True`` runs each step as one device-resident ``hdg_step`` call instead of the
         per-solve calls that mirror the reference's loop (identical results, no per-solve timers).
         ``diagnostics=True`` records the flow diagnostics of the initial state and of every step on the device and
         stores them as ``self.diagnostics`` (dict of arrays: ``t`` and the names of ``_lib.DIAGNOSTICS``).
+        ``probes=xy`` ((n, 2) points) records the point values of the initial state and of every step on the device and
+        stores them as ``self.probes`` (dict: ``t``, ``xy``, ``u`` (nt+1, n, 2), ``p``, ``q``, ``omega`` (nt+1, n)).
         """
         eng = self._engine
         tracer = self._init_tracer(q_initial)  # hdg_imex.py:523-529
@@ -143,6 +145,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         eng.iteration_stats(reset=True)
         eng.timers(reset=True)
         self._start_diagnostics(diagnostics, nt)
+        self._start_probes(probes, nt)
         for callback in self.callbacks:
             callback.reset()
             Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
@@ -190,6 +193,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
                 for callback in self.callbacks:
                     callback(Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p"), tn + self._dt, q_tracer=qt)
         self._finish_diagnostics(diagnostics)
+        self._finish_probes(probes)
         if fused:
             # per-solve breakdown of the fused steps from the engine's device-side timers (same labels as the
             # host timers of the per-solve path; "timestep" is already timed on the host)
