@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/hdg_mi355x.h"
+#include "hdg_options.hpp"
 #include "hdg_comm.hpp"
 #include "hdg_kernels.hpp"
 #include "hdg_schur_mfma.hpp"
@@ -41,11 +42,6 @@
 #include "hdg_probes.hpp"
 
 namespace hdg {
-
-// diagnostics switches, read once per process: HDG_DEBUG (solver decisions, communication census),
-// HDG_DEBUG_CG (per-iteration residuals of the trace CG)
-static bool debug_on() { static const bool v = std::getenv("HDG_DEBUG") != nullptr; return v; }
-static bool debug_cg() { static const bool v = std::getenv("HDG_DEBUG_CG") != nullptr; return v; }
 
 struct HipError {
   std::string msg;
@@ -67,6 +63,7 @@ struct NotConverged {
 static constexpr int MAXV = 32;  // vectors per multi-dot launch
 
 struct Engine {
+  const Options opt = options_from_env();  // every HDG_* switch, read when the engine is built (hdg_options.hpp)
   hdg_config cfg;
   Geo g;
   int K, NU, NP, NL, NE, NX, s;
@@ -101,14 +98,6 @@ struct Engine {
   std::vector<double*> gm_V;  // GMRES basis (restart+1)
   const double** d_ptrs = nullptr;
   const double** d_gmV = nullptr;  // device array of the GMRES basis pointers
-  // single-precision COPY of the GMRES basis (experiment, HDG_KRYLOV_FP32=1): the Gram-Schmidt passes and the solution update
-  // read these (half the bytes); gm_V[j] holds the same rounded values as doubles for the operator kernels.  MEASURED AND
-  // REJECTED as the default: the smooth benchmark fields make the Krylov spaces nearly invariant
-  // (h_{j+1,j} / |w| ~ 3e-4 in the first steps of a cycle), the 6e-8 rounding of v_j then enters v_{j+1} at 2e-4 relative
-  // and every solve needs about one iteration more (C3: 22.4 instead of 21.4; k = 4 at 512^2: 34.4 instead of 29.8)
-  std::vector<float*> gm_Vf;
-  const float** d_gmVf = nullptr;
-  bool basis_f32 = false;
   double* d_part = nullptr;
   double* d_res = nullptr;
   double* h_res = nullptr;  // pinned host mirror of d_res
@@ -276,7 +265,6 @@ struct Engine {
   std::vector<DevCsr> gdinv;  // element block-Jacobi per stage
   // matrix-free lift on general meshes (k_g_lift, round 4): reference moment tables, per-cell lifting tables of the BDM
   // projection and (per stage) of the hybrid preconditioner; HDG_GENERAL_CSR_LIFT keeps the assembled operators
-  const bool g_csr_lift = std::getenv("HDG_GENERAL_CSR_LIFT") != nullptr;  // read when an engine is built
   const double* g_nref = nullptr;
   const double* g_lift = nullptr;
   std::vector<const double*> g_hyb;
@@ -360,11 +348,7 @@ struct Engine {
     const Csr P0 = p1_to_trace_matrix(*gtab, *gm);
     const Csr R0 = csr_transpose(P0);
     const Csr A0 = csr_multiply(R0, csr_multiply(S_host, P0));
-    // coarsening stops at <= 2000 vertices (round 3: 400), where the dense pseudo-inverse takes over: on the level-6 disk the
-    // hierarchy is 16 641 -> 1 893 (dense) instead of -> 1 893 -> 149 (dense) -- one smoothed level (18 launches of ~5 us per
-    // V-cycle) fewer for a 29 MB matrix-vector product; HDG_AMG_MAX_COARSE overrides
-    static const int amg_max_coarse = std::getenv("HDG_AMG_MAX_COARSE") ? std::atoi(std::getenv("HDG_AMG_MAX_COARSE")) : 2000;
-    amg_build(A0, amg_host, amg_max_coarse);
+    amg_build(A0, amg_host, opt.amg_max_coarse);
     amg.P0 = upload_csr(P0); amg.R0 = upload_csr(R0);
     for (size_t l = 0; l < amg_host.lev.size(); l++) {
       const AmgLevel& L = amg_host.lev[l];
@@ -401,8 +385,7 @@ struct Engine {
     const double rn = 1.0 / (2.0 * sigma1 - rho);
     double* r = amg.r[l];
     double* d = amg.d[l];
-    static const bool unfused = std::getenv("HDG_AMG_UNFUSED") != nullptr;
-    if (!unfused) {  // two launches (k_amg_cheb) instead of six or seven
+    if (!opt.amg_unfused) {  // two launches (k_amg_cheb) instead of six or seven
       const DevCsr& A = amg.A[l];
       const long nthr = (long)A.nrows * A.tpr;
       const int nblk = (int)((nthr + 255) / 256);
@@ -474,10 +457,10 @@ struct Engine {
     // tentative velocity: GMRES(30) with the hybrid preconditioner Pi + Dinv (I - Pi) (HDG_GENERAL_BLOCK_JACOBI: Dinv alone)
     // round 4: the Chebyshev iteration + s-step tail of the structured engine here as well (preconditioner and Chebyshev step as
     // separate launches: the assembled operators have no fused form); HDG_GENERAL_GMRES restores GMRES(30)
-    cfg.tent_precond = std::getenv("HDG_GENERAL_BLOCK_JACOBI") ? 0 : 2; cfg.periodic = 0;
+    cfg.tent_precond = opt.general_block_jacobi ? 0 : 2; cfg.periodic = 0;
     // (k = 1: GMRES -- with assembled operators an iteration is dear, and the Chebyshev iteration needs 41 where GMRES needs 33)
-    cfg.tent_solver = (std::getenv("HDG_GENERAL_GMRES") || cfg.tent_precond != 2 || K < 2) ? 0 : 1;
-    cfg.trace_precond = std::getenv("HDG_GENERAL_NO_COARSE") ? 0 : 1;
+    cfg.tent_solver = (opt.general_gmres || cfg.tent_precond != 2 || K < 2) ? 0 : 1;
+    cfg.trace_precond = opt.general_coarse ? 1 : 0;
     cfg.gmres_restart = std::max(cfg.gmres_restart, 30);
     gm = new GMesh();
     gm->build(nv, coords, nc, cells);
@@ -506,7 +489,7 @@ struct Engine {
     d_one_p = upload(gops.one_p); d_int_p = upload(gops.int_p); d_one_l = upload(gops.one_l);
     gdinv.assign((size_t)s, DevCsr());
     g_hyb.assign((size_t)s, nullptr);
-    if (!g_csr_lift) {
+    if (!opt.general_csr_lift) {
       dvec nr(gtab->Nref.size());
       for (size_t q = 0; q < nr.size(); q++) nr[q] = (double)gtab->Nref[q];
       g_nref = upload(nr);
@@ -579,9 +562,6 @@ struct Engine {
     if (cstream) { (void)hipStreamDestroy(cstream); cstream = nullptr; }
     if (h_cgm) { (void)hipHostFree(h_cgm); h_cgm = nullptr; }
     for (int q = 0; q < 2; q++) if (cgm_ev[q]) { (void)hipEventDestroy(cgm_ev[q]); cgm_ev[q] = nullptr; }
-    if (ev_x0) { (void)hipEventDestroy(ev_x0); ev_x0 = nullptr; }
-    if (ev_x1) { (void)hipEventDestroy(ev_x1); ev_x1 = nullptr; }
-    if (xstream) { (void)hipStreamDestroy(xstream); xstream = nullptr; }
     if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
     delete tab;
     tab = nullptr;
@@ -604,7 +584,7 @@ struct Engine {
     // interior / boundary split around halo exchanges on a second stream: OPT-IN (HDG_OVERLAP=1) since round 4 -- the logic is
     // tested on every multi-rank test over the shared-memory transport, but ncclSend / ncclRecv on a second stream beside
     // kernels has never run on two devices (round-3 advisor finding): the first multi-GPU run uses the plain single-stream order
-    overlap_on = !std::getenv("HDG_NO_OVERLAP") && std::getenv("HDG_OVERLAP") != nullptr;
+    overlap_on = opt.overlap;
     if (periodic && (c.nx % 2 != 0)) throw std::string("the periodic mesh needs an even nx (red-black coarse-grid sweeps)");
     if (periodic && c.ny < 4) throw std::string("the periodic mesh needs at least 4 cell rows");
     if (periodic && comm->size > 1 && g.ny < PERIODIC_MIN_ROWS)
@@ -624,7 +604,7 @@ struct Engine {
     g.P = ((c.nx + 1 + 15) / 16) * 16;
     g.G = (long)(g.ny + 2 * GH) * g.P;
     g.R = g.ny + 2 * GH;
-    if (std::getenv("HDG_ROW_PAD")) g.R += std::atoi(std::getenv("HDG_ROW_PAD"));
+    if (opt.row_pad >= 0) g.R += opt.row_pad;
     else {
       // Padding rows: the element kernels stream 2 (k+2)(k+3)/2 dof planes at once, and on MI355X planes whose stride is
       // close to a multiple of 2^15 B times 0, 1, 2, 4, 8 or 9 (mod 16) share memory channels.  Measured at C3, stride =
@@ -642,7 +622,7 @@ struct Engine {
     g.rows_xcd = (g.ny + 7) / 8;
     g.rows_xcdc = (g.nyc + 7) / 8;
     g.wskip = 0; g.wgap0 = 0; g.wgapn = 0; g.wrows = g.ny; g.wrowsc = g.nyc;
-    g.dbg_nonbr = std::getenv("HDG_DBG_NONBR") ? 1 : 0;
+    g.dbg_nonbr = opt.dbg_nonbr ? 1 : 0;
     g_all = g;
     g_all.nyc = g.ny + (periodic ? 0 : 1);
     g_all.rows_xcdc = (g_all.nyc + 7) / 8;
@@ -665,7 +645,7 @@ struct Engine {
     if (debug_on() && comm && comm->rank == 0)
       fprintf(stderr, "[comm] halo exchanges: velocity %ld, pressure %ld, trace %ld, vertex rows %ld (%ld of them beside an interior launch); all-reduces %ld; all-gathers %ld; tiled trace preconditioner applications %ld\n",
               n_halo[0], n_halo[1], n_halo[2], n_halo_mg, n_overlapped, n_reduce, n_gather, n_tile_precond);
-    if (flow_check && comm && comm->rank == 0)
+    if (opt.flow_check && comm && comm->rank == 0)
       fprintf(stderr, "[flow check] %ld skipped exchanges verified, worst relative deviation %.3e\n", fc_count, fc_worst);
     release();
     delete comm;
@@ -726,25 +706,6 @@ struct Engine {
       pv.push_back(nullptr);
       pv.push_back(nullptr);
       d_gmV = upload_ptrs(pv);
-    }
-    basis_f32 = std::getenv("HDG_KRYLOV_FP32") != nullptr;
-    if (basis_f32) {
-      std::vector<const float*> pf;
-      for (int i = 0; i <= m; i++) {
-        void* q = nullptr;
-        HIPCHECK(hipMalloc(&q, sizeof(float) * (size_t)std::max<long>(NQ, 1)));
-        HIPCHECK(hipMemsetAsync(q, 0, sizeof(float) * (size_t)std::max<long>(NQ, 1), stream));
-        allocs.push_back(q);
-        gm_Vf.push_back((float*)q);
-        pf.push_back((const float*)q);
-      }
-      pf.push_back(nullptr);
-      pf.push_back(nullptr);
-      void* q = nullptr;
-      HIPCHECK(hipMalloc(&q, sizeof(float*) * pf.size()));
-      allocs.push_back(q);
-      HIPCHECK(hipMemcpy(q, pf.data(), sizeof(float*) * pf.size(), hipMemcpyHostToDevice));
-      d_gmVf = (const float**)q;
     }
     void* p = nullptr;
     HIPCHECK(hipMalloc(&p, sizeof(double*) * (std::max(m, MAXV) + 2)));
@@ -834,7 +795,6 @@ struct Engine {
   // the bookkeeping calls its ghost rows valid, exchange anyway into the receive buffers and compare with what is there.
   // The worst relative deviation of a solve is checked when its FlowScope closes (redundantly computed rows agree to
   // rounding); a stale validity shows up as an O(1) deviation and fails the call.
-  bool flow_check = std::getenv("HDG_FLOW_CHECK") != nullptr;
   unsigned long long* d_fc = nullptr;
   long fc_count = 0;
   double fc_worst = 0.0;
@@ -856,7 +816,7 @@ struct Engine {
     else halo_rows_compare(in, g.G, g.P, 3 * NL, depth);
   }
   void flow_check_close() {  // end of a solver scope: read the result back, fail on a stale ghost row
-    if (!flow_check || !d_fc || comm->size == 1) return;
+    if (!opt.flow_check || !d_fc || comm->size == 1) return;
     unsigned long long h[2] = {0, 0};
     HIPCHECK(hipMemcpyAsync(h, d_fc, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
@@ -906,16 +866,15 @@ struct Engine {
   struct FlowScope {
     Engine& E;
     explicit FlowScope(Engine& e) : E(e) {
-      static const bool off = std::getenv("HDG_NO_EXT") != nullptr;
       if (E.fl.nest++ == 0) {
         E.fl.v.clear();
-        E.fl.Dx = (off || E.comm->size == 1 || !E.halo_on) ? 1 : std::min(DX_DEFAULT, E.g.ny);
+        E.fl.Dx = (!E.opt.ext || E.comm->size == 1 || !E.halo_on) ? 1 : std::min(DX_DEFAULT, E.g.ny);
       }
     }
     ~FlowScope() noexcept(false) {
       if (--E.fl.nest == 0) {
         E.fl.v.clear();
-        if (E.flow_check && !std::uncaught_exceptions()) E.flow_check_close();
+        if (E.opt.flow_check && !std::uncaught_exceptions()) E.flow_check_close();
       }
     }
   };
@@ -931,7 +890,7 @@ struct Engine {
         if (kind == FQ) halo_Q(in, depth); else if (kind == FP) halo_P(in); else halo_L(in, depth);
       }
       fl.set(in, kind == FP ? 1 : depth);
-    } else if (flow_check) {
+    } else if (opt.flow_check) {
       flow_check_input(in, kind, fl.get(in));  // no exchange needed, says the bookkeeping: verify
     }
     return fl.active() ? fl.get(in) - 1 : 0;
@@ -1233,8 +1192,7 @@ struct Engine {
   const double *pgm[2] = {nullptr, nullptr}, *wdm[2] = {nullptr, nullptr}, *wdbm[2] = {nullptr, nullptr};
   // HDG_NO_MFMA_SCHUR: the per-thread kernels at every degree (A/B timing, parity of the two formulations)
   bool use_mfma_schur() const {
-    static const bool off = std::getenv("HDG_NO_MFMA_SCHUR") != nullptr;
-    return !off && cfg.degree >= mfma_min_degree() && !periodic && !general;  // the matrix-core kernels do not wrap column indices
+    return opt.mfma_schur && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general;  // the matrix-core kernels do not wrap column indices
   }
   void ensure_schur_tables(PSet& ps) {
     if (ps.bsm[0]) return;
@@ -1247,32 +1205,21 @@ struct Engine {
     }
   }
   dvec schur_Y0;
-  bool mfma_condense = std::getenv("HDG_MFMA_CONDENSE") != nullptr;  // per engine, not per process: tests build both
   dim3 schur_cell_grid() const { return dim3(8 * g.rows_xcd * 2); }
   dim3 schur_corner_grid() const { return dim3(8 * g.rows_xcdc); }
   const double* advm[2] = {nullptr, nullptr};
   const double* liftm_plain[2] = {nullptr, nullptr};  // packed tables of the plain BDM projection
   std::vector<double*> liftm_hyb0, liftm_hyb1;         // per stage: hybrid preconditioner
   bool use_mfma_lift() const {
-    static const bool off = std::getenv("HDG_NO_MFMA_LIFT") != nullptr;
-    return !off && cfg.degree >= mfma_min_degree() && !periodic && !general;  // the matrix-core kernels do not wrap column indices
+    return opt.mfma_lift && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general;  // the matrix-core kernels do not wrap column indices
   }
-  // HDG_MFMA_K2 (experiment): the matrix-core kernels at k = 2 as well (north_star: "MFMA at k >= 2")
-  static int mfma_min_degree() { static const int d = std::getenv("HDG_MFMA_K2") ? 2 : 3; return d; }
-  const bool lift_pair_off = std::getenv("HDG_LIFT_NO_PAIR") != nullptr;  // read when an engine is built (tests compare the two forms)
-  bool lift_pair() const { return !lift_pair_off && K <= 2 && bs() == 128 && !general; }
-  // paired form of the advection kernel (round 4; HDG_ADV_PAIR=1 / 0 switches it, read when an engine is built)
-  const int adv_pair_env = std::getenv("HDG_ADV_PAIR") ? std::atoi(std::getenv("HDG_ADV_PAIR")) : -1;
-  bool adv_pair() const {
-    const bool dflt = false;  // measured: see DESIGN.md section 9
-    return (adv_pair_env >= 0 ? adv_pair_env != 0 : dflt) && K <= 2 && bs() == 128 && !general && dt.nqe == (3 * K + 5) / 2;
-  }
+  static constexpr int MFMA_MIN_DEGREE = 3;  // the matrix-core kernels at k = 2 were 1.8-2 x slower
+  bool lift_pair() const { return opt.lift_pair && K <= 2 && bs() == 128 && !general; }
   void lift_mfma(const Geo& gx, const double* t0, const double* t1, const double* in, double* out, double* chd_ = nullptr,
                  const double* chx_ = nullptr, double c1 = 0.0, double c2 = 0.0) {
     const dim3 grid(8 * gx.rows_xcd * 2);
     if (chd_) {  // with the fused Chebyshev step
       switch (cfg.degree) {
-        case 2: k_edge_lift_mfma<2, true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2); break;
         case 3: k_edge_lift_mfma<3, true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2); break;
         case 4: k_edge_lift_mfma<4, true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2); break;
         default: throw std::string("MFMA lift: degree out of range");
@@ -1280,7 +1227,6 @@ struct Engine {
       return;
     }
     switch (cfg.degree) {
-      case 2: k_edge_lift_mfma<2><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out); break;
       case 3: k_edge_lift_mfma<3><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out); break;
       case 4: k_edge_lift_mfma<4><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out); break;
       default: throw std::string("MFMA lift: degree out of range");
@@ -1374,6 +1320,8 @@ struct Engine {
     HDG_DISPATCH(k_edge_lift<KK, true, 0, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr));
     fl.set(out, ext);
   }
+  // k >= 3: the whole operator on the matrix cores (k_adv_mfma); HDG_NO_MFMA_ADV falls back to the per-thread kernels
+  bool use_mfma_adv() const { return opt.mfma_adv && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general; }
   void adv_apply(const double* x, const double* qstar, double* out, double gamma, const double* bsub = nullptr) {
     KTimed kt_(*this, bsub != nullptr ? T_KADV : T_KADV_PLAIN, fl.active());
     const double up = cfg.flux_upwind ? 1.0 : 0.0;
@@ -1383,21 +1331,14 @@ struct Engine {
       fl.set(out, 0);
       return;
     }
-    // k >= 3: the whole operator on the matrix cores (k_adv_mfma); HDG_NO_MFMA_ADV falls back to the per-thread kernels
-    static const bool no_mfma_adv = std::getenv("HDG_NO_MFMA_ADV") != nullptr;
-    const bool mfma = !no_mfma_adv && cfg.degree >= mfma_min_degree() && !periodic;
+    const bool mfma = use_mfma_adv();
     if (mfma && !advm[0]) {
-      if (dt.nqc != (cfg.degree == 2 ? 16 : (cfg.degree == 3 ? 36 : 64))) throw std::string("cell quadrature size does not match the matrix-core advection kernel");
+      if (dt.nqc != (cfg.degree == 3 ? 36 : 64)) throw std::string("cell quadrature size does not match the matrix-core advection kernel");
       if (dt.nqe != (3 * cfg.degree + 5) / 2) throw std::string("edge quadrature size does not match the matrix-core advection kernel");
       for (int sh = 0; sh < 2; sh++) advm[sh] = upload(pack_adv_mfma(sh));
     }
-    // k = 3 without the matrix-core kernel: two lanes per cell, one velocity component each (k_adv_apply2).  Measured at
-    // nx = 512, one-lane vs two-lane kernel: k=1 181 / 205 us (nx 1024), k=2 353 / 370 us (nx 1024), k=3 407 / 334 us,
-    // k=4 719 / 1488 us (254 VGPRs, still 1 wave/SIMD, twice the waves).  HDG_ADV_SPLIT=lo:hi overrides the degree range.
-    static const char* split_env = std::getenv("HDG_ADV_SPLIT");
-    int split_lo = 3, split_hi = 3;
-    if (split_env) std::sscanf(split_env, "%d:%d", &split_lo, &split_hi);
-    const bool two_lane = cfg.degree >= split_lo && cfg.degree <= split_hi;
+    // without the matrix-core kernel: two lanes per cell, one velocity component each (k_adv_apply2), at the degrees of opt.adv_split_*
+    const bool two_lane = cfg.degree >= opt.adv_split_lo && cfg.degree <= opt.adv_split_hi;
     int ext = 0;
     // the launch of one row window (the whole extended strip, or interior / boundary rows around the exchange of x)
     stencil_launch(x, FQ, GH, false, {qstar, bsub}, [&](const Geo& g) {  // shadows the member on purpose
@@ -1409,21 +1350,11 @@ struct Engine {
           k_adv_mfma<KK, RS><<<gridc, 512, 0, stream>>>(g, dt, advm[0], advm[1], x, qstar, out, gamma, up, bsub);
         };
         auto by_form = [&](auto kk) { if (bsub) launch(kk, std::true_type{}); else launch(kk, std::false_type{}); };
-        if (cfg.degree == 2) by_form(std::integral_constant<int, 2>{});
-        else if (cfg.degree == 3) by_form(std::integral_constant<int, 3>{});
+        if (cfg.degree == 3) by_form(std::integral_constant<int, 3>{});
         else by_form(std::integral_constant<int, 4>{});
       } else if (two_lane) {
         const int cpb = bs() / 2, nbx2 = (g.nx + cpb - 1) / cpb;
         HDG_DISPATCH(k_adv_apply2<KK><<<dim3(8 * g.rows_xcd * 2 * nbx2), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub));
-      } else if (adv_pair()) {
-        // k <= 2, 128-thread workgroups: both triangles of 64 squares per workgroup, neighbour traces through LDS
-        if (K == 1) {
-          if (bsub) k_adv_pair<1, true><<<cell_grid_of(g), 128, 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub);
-          else k_adv_pair<1, false><<<cell_grid_of(g), 128, 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub);
-        } else {
-          if (bsub) k_adv_pair<2, true><<<cell_grid_of(g), 128, 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub);
-          else k_adv_pair<2, false><<<cell_grid_of(g), 128, 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub);
-        }
       } else if (bsub) {
         HDG_DISPATCH(k_adv_apply<KK, true><<<cell_grid_of(g), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub));
       } else {
@@ -1450,7 +1381,6 @@ struct Engine {
     if (use_mfma_schur()) {
       if (!pgm[0]) for (int sh = 0; sh < 2; sh++) pgm[sh] = upload(pack_pgrad_mfma(sh));
       switch (K) {
-        case 2: k_pgrad_mfma<2><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); break;
         case 3: k_pgrad_mfma<3><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); break;
         default: k_pgrad_mfma<4><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); break;
       }
@@ -1470,8 +1400,7 @@ struct Engine {
         if (broken) k_weak_div_mfma<KK, true><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, tb[0], tb[1], q, sc, out);
         else k_weak_div_mfma<KK, false><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, tb[0], tb[1], q, sc, out);
       };
-      if (K == 2) launch(std::integral_constant<int, 2>{});
-      else if (K == 3) launch(std::integral_constant<int, 3>{});
+      if (K == 3) launch(std::integral_constant<int, 3>{});
       else launch(std::integral_constant<int, 4>{});
       return;
     }
@@ -1554,7 +1483,7 @@ struct Engine {
     // Condensation stays with the per-thread kernel by default: it is a gather over four cells per corner that already runs at
     // 3.4-4.5 TB/s (512^2, us per launch, per-thread | matrix-core: pressure-row form k = 3 / 4: 15 / 21 | 31 / 46, velocity-row
     // form 40 / 61 | 48 / 61).  HDG_MFMA_CONDENSE=1 (read when the engine is built) selects the matrix-core kernel.
-    if (mfma_condense && use_mfma_schur() && (rw || rp)) {
+    if (opt.mfma_condense && use_mfma_schur() && (rw || rp)) {
       PSet& ps = psets[cur_pset];
       ensure_schur_tables(ps);
       auto launch = [&](auto kk, auto hw, auto hp) {
@@ -1566,8 +1495,7 @@ struct Engine {
         else if (!rw && rp) launch(kk, std::false_type{}, std::true_type{});
         else launch(kk, std::true_type{}, std::true_type{});
       };
-      if (K == 2) by_form(std::integral_constant<int, 2>{});
-      else if (K == 3) by_form(std::integral_constant<int, 3>{});
+      if (K == 3) by_form(std::integral_constant<int, 3>{});
       else by_form(std::integral_constant<int, 4>{});
       return;
     }
@@ -1597,8 +1525,7 @@ struct Engine {
         else if (!rw && rp) launch(kk, std::false_type{}, std::true_type{});
         else launch(kk, std::true_type{}, std::true_type{});
       };
-      if (K == 2) by_form(std::integral_constant<int, 2>{});
-      else if (K == 3) by_form(std::integral_constant<int, 3>{});
+      if (K == 3) by_form(std::integral_constant<int, 3>{});
       else by_form(std::integral_constant<int, 4>{});
       return;
     }
@@ -1686,27 +1613,13 @@ struct Engine {
   }
   // out = scale * (w - sum_{l < nv} h_l V_l)   (V_l: the GMRES basis gm_V)
   void gs_update(const double* w, const Coefs& h, int nv, double scale, double* out) {
-    if (basis_f32) {
-      int slot = -1;
-      for (size_t q = 0; q < gm_V.size() && slot < 0; q++) if (gm_V[q] == out) slot = (int)q;
-      if (slot < 0) throw std::string("gs_update: the result is not a basis vector");
-      tally(LC_VEC, bQ() * (0.5 * nv + 2.5));
-      if (big(NQ)) k_gs_update<MAXV, true, float><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmVf, h, nv, scale, out, gm_Vf[slot]);
-      else k_gs_update<MAXV, false, float><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmVf, h, nv, scale, out, gm_Vf[slot]);
-    } else {
-      tally(LC_VEC, bQ() * (nv + 2));
-      if (big(NQ)) k_gs_update<MAXV, true><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmV, h, nv, scale, out);
-      else k_gs_update<MAXV, false><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmV, h, nv, scale, out);
-    }
-    // ghost rows: the single-precision copies are never exchanged, so they keep the depth they were created with (an
-    // exchange may have deepened the double-precision twin since): tracked under their own addresses
+    tally(LC_VEC, bQ() * (nv + 2));
+    if (big(NQ)) k_gs_update<MAXV, true><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmV, h, nv, scale, out);
+    else k_gs_update<MAXV, false><<<vec_blocks(NQ), 256, 0, stream>>>(NQ, w, d_gmV, h, nv, scale, out);
     int d = fl.get(w);
-    for (int l = 0; l < nv; l++) d = std::min(d, fl.get(basis_key(l)));
+    for (int l = 0; l < nv; l++) d = std::min(d, fl.get(gm_V[l]));
     fl.set(out, d);
-    if (basis_f32)
-      for (size_t q = 0; q < gm_V.size(); q++) if (gm_V[q] == out) fl.set(basis_key((int)q), d);
   }
-  const double* basis_key(int l) const { return basis_f32 ? reinterpret_cast<const double*>(gm_Vf[l]) : gm_V[l]; }
   void lincomb(long n, const std::vector<std::pair<const double*, double>>& terms, double* out) {
     // merge duplicate pointers, drop zeros, chunks of 8
     std::vector<std::pair<const double*, double>> t;
@@ -1746,10 +1659,7 @@ struct Engine {
   // dots of w against nv vectors over the OWNED entries, summed over ranks (host result); one sync
   // cross: res[nv] additionally receives (V[0], V[1]) from the same pass (nv >= 2, single chunk)
   // res == nullptr: the results stay in d_res on the device (single chunk), no host copy, no synchronisation
-  static bool direct_host() {
-    static const bool on = std::getenv("HDG_NO_DIRECT_HOST") == nullptr;
-    return on;
-  }
+  bool direct_host() const { return opt.direct_host; }
   void multidot(long n, const double* w, const std::vector<const double*>& V, double* res, int kind, bool cross = false) {
     int nv = (int)V.size();
     if (!res && nv > MAXV) throw std::string("multidot: device-resident result needs a single chunk");
@@ -1801,38 +1711,11 @@ struct Engine {
     return r;
   }
   // Gram-Schmidt pass of the tentative-velocity GMRES: res[l] = (w, V_l), l < nb, and res[nb] = (w, w) in one pass over w
-  // and the basis (its single-precision copy when there is one)
+  // and the basis
   void multidot_basis(const double* w, int nb_, double* res) {
-    if (!basis_f32) {
-      std::vector<const double*> ptrs(gm_V.begin(), gm_V.begin() + nb_);
-      ptrs.push_back(w);
-      multidot(NQ, w, ptrs, res, KQ);
-      return;
-    }
-    const int cnt = nb_ + 1;
-    if (cnt > MAXV) throw std::string("multidot_basis: too many vectors");
-    const int nb = std::min(dot_blocks, vec_blocks(NQ));
-    const RowMask mk = mask_for(KQ);
-    tally(LC_DOT, bvec(NQ) * (0.5 * nb_ + 1));
-    tally(LC_OTHER, 0.0);  // k_reduce_parts
-    auto launch = [&](auto tag) {
-      constexpr int MV = decltype(tag)::value;
-      VecList<MV, float> vl;
-      for (int q = 0; q < MV; q++) vl.p[q] = q < nb_ ? gm_Vf[q] : nullptr;
-      if (big(NQ)) k_multidot<MV, true, float><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, w, vl, cnt, d_part, mk, 0, nb_);
-      else k_multidot<MV, false, float><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, w, vl, cnt, d_part, mk, 0, nb_);
-    };
-    if (cnt <= 4) launch(std::integral_constant<int, 4>{});
-    else if (cnt <= 6) launch(std::integral_constant<int, 6>{});
-    else if (cnt <= 12) launch(std::integral_constant<int, 12>{});
-    else launch(std::integral_constant<int, MAXV>{});
-    const bool direct = comm->size == 1 && direct_host();
-    k_reduce_parts<<<cnt, 256, 0, stream>>>(nb, cnt, d_part, d_res, direct ? h_res : nullptr);
-    comm->allreduce_sum(d_res, cnt, stream);
-    n_reduce++;
-    if (!direct) HIPCHECK(hipMemcpyAsync(h_res, d_res, sizeof(double) * cnt, hipMemcpyDeviceToHost, stream));  // pinned
-    HIPCHECK(hipStreamSynchronize(stream));
-    for (int q = 0; q < cnt; q++) res[q] = h_res[q];
+    std::vector<const double*> ptrs(gm_V.begin(), gm_V.begin() + nb_);
+    ptrs.push_back(w);
+    multidot(NQ, w, ptrs, res, KQ);
   }
   // ------------------------------------------------------------------ pressure mean shift
   void shift(double* p, double* l) {
@@ -1907,7 +1790,7 @@ struct Engine {
   void ensure_dinv(int idx, double gamma) {
     if (general) {
       if (dinv_gamma[idx] == gamma && (gdinv[(size_t)idx].nrows || g_hyb[(size_t)idx])) return;
-      if (!g_csr_lift && cfg.tent_precond == 2) g_hyb[(size_t)idx] = upload(assemble_lift_tables(*gtab, *gm, gloc, gamma));
+      if (!opt.general_csr_lift && cfg.tent_precond == 2) g_hyb[(size_t)idx] = upload(assemble_lift_tables(*gtab, *gm, gloc, gamma));
       else gdinv[(size_t)idx] = upload_csr(assemble_block_jacobi(*gtab, *gm, gloc, gamma));
       dinv_gamma[idx] = gamma;
       return;
@@ -1949,10 +1832,6 @@ struct Engine {
     HIPCHECK(hipMemcpyAsync(hybg1[idx], G[1].data(), sizeof(double) * G[1].size(), hipMemcpyHostToDevice, stream));
     HIPCHECK(hipStreamSynchronize(stream));
     dinv_gamma[idx] = gamma;
-  }
-  static bool mfma_cheb_unfused() {
-    static const bool v = std::getenv("HDG_MFMA_CHEB_UNFUSED") != nullptr;
-    return v;
   }
   // z = M r  (tentative-velocity preconditioner)
   void tent_precond(int didx, const double* r, double* z) {
@@ -2000,11 +1879,6 @@ struct Engine {
     } else if (cfg.tent_precond == 1) {
       bdm_T(r, wQ3);
       bdm_plus_bj(wQ3, zout, r, dinv0[didx], dinv1[didx], d_, x_, c1, c2);
-    } else if (use_mfma_lift() && mfma_cheb_unfused()) {
-      // k >= 3, round-2 form (HDG_MFMA_CHEB_UNFUSED): matrix-core lift, then the Chebyshev step as one vector kernel
-      bdm_hybrid(r, wQ4, hybg0[didx], hybg1[didx]);
-      if (zout) copy(zout, wQ4, NQ);
-      cheb_update(d_, wQ4, x_, c1, c2);
     } else if (use_mfma_lift()) {
       // k >= 3: matrix-core lift with the Chebyshev step in its store epilogue (z is stored at check points only)
       bdm_hybrid(r, zout, hybg0[didx], hybg1[didx], d_, x_, c1, c2, nullptr);
@@ -2025,9 +1899,8 @@ struct Engine {
     // declines, general meshes at k = 1) runs as s-step minimal-residual cycles -- the same Krylov spaces as GMRES(6) without the
     // Gram-Schmidt passes, which cost more than the operator (sstep_mr; two weak cycles come back here in Arnoldi form).  The
     // Arnoldi form stays for the Ritz estimate, the inexact inner solves of the monolithic preconditioner, the fall-backs after a
-    // growing / stalled Chebyshev iteration, single-precision basis storage; HDG_GMRES_ARNOLDI restores it everywhere.
-    static const bool arnoldi_env = std::getenv("HDG_GMRES_ARNOLDI") != nullptr;
-    if (!arnoldi_env && !arnoldi_only && !ritz && strict && !basis_f32 && m_cycle == 0 && first_cycle == 4 && gm_V.size() >= 4)
+    // growing / stalled Chebyshev iteration; HDG_GMRES_ARNOLDI restores it everywhere.
+    if (!opt.gmres_arnoldi && !arnoldi_only && !ritz && strict && m_cycle == 0 && first_cycle == 4 && gm_V.size() >= 4)
       return sstep_mr(qstar, gamma, didx, b, x, rtol < 0 ? cfg.tent_rtol : rtol, beta0_given, -1.0);
     FlowScope flow_(*this);
     flow_fixed_Q(qstar);
@@ -2120,15 +1993,12 @@ struct Engine {
         y[l] = acc / H[(size_t)l * m + l];
       }
       for (int l = 0; l < j; l++) yc.c[l] = y[l];
-      tally(LC_VEC, bQ() * ((basis_f32 ? 0.5 : 1.0) * j + 2));
-      if (basis_f32) {
-        if (big(NQ)) k_basis_axpy<MAXV, true, float><<<nvb, 256, 0, stream>>>(NQ, x, d_gmVf, yc, j);
-        else k_basis_axpy<MAXV, false, float><<<nvb, 256, 0, stream>>>(NQ, x, d_gmVf, yc, j);
-      } else if (big(NQ)) k_basis_axpy<MAXV, true><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
+      tally(LC_VEC, bQ() * (j + 2));
+      if (big(NQ)) k_basis_axpy<MAXV, true><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
       else k_basis_axpy<MAXV, false><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
       {
         int d = fl.get(x);
-        for (int l = 0; l < j; l++) d = std::min(d, fl.get(basis_key(l)));
+        for (int l = 0; l < j; l++) d = std::min(d, fl.get(gm_V[l]));
         fl.set(x, d);
       }
       if (ritz) {
@@ -2248,32 +2118,23 @@ struct Engine {
     rho = std::sqrt((double)std::max(r2, 0.0L));
     return rank;
   }
-  std::vector<double*> aug_u, aug_c;  // augmentation pairs (u, B u) of the s-step cycles (allocated on first use)
   int sstep_mr(const double* qstar, double gamma, int didx, const double* b, double* x, double rtol, double beta0, double cur0) {
     FlowScope flow_(*this);
     flow_fixed_Q(qstar);
     flow_fixed_Q(b);
-    static const int smax_env = std::getenv("HDG_SSTEP_MAX") ? std::atoi(std::getenv("HDG_SSTEP_MAX")) : 6;
-    static const double per_decade = std::getenv("HDG_SSTEP_PER_DECADE") ? std::atof(std::getenv("HDG_SSTEP_PER_DECADE")) : 1.7;
-    // LGMRES-type augmentation: the next cycle's least-squares space also holds the last NA corrections u_j = x_{j+1} - x_j,
-    // whose images B u_j = r_j - r_{j+1} are known without an operator application (by-products of the update pass)
-    // (measured: no gain -- C3 15.55 -> 15.57 iterations, k = 4 at 512^2 25.2 -> 24.7, each cycle two vector passes dearer: off by
-    //  default, HDG_SSTEP_AUG = 1 | 2 switches it on)
-    static const int NA = std::max(0, std::min(2, std::getenv("HDG_SSTEP_AUG") ? std::atoi(std::getenv("HDG_SSTEP_AUG")) : 0));
-    const int smax = std::max(2, std::min(std::min(smax_env, HDG_SSTEP_MAXV - 1 - NA), (int)gm_V.size() - 1));
+    const int smax = std::max(2, std::min(std::min(opt.sstep_max, HDG_SSTEP_MAXV - 1), (int)gm_V.size() - 1));
     if (!d_gram) {
       d_gram = dalloc(64);
       HIPCHECK(hipHostMalloc((void**)&h_gram, sizeof(double) * 64));
     }
-    while ((int)aug_u.size() < NA) { aug_u.push_back(dalloc(NQ)); aug_c.push_back(dalloc(NQ)); }
     double* t = wQ2;
     const RowMask mk = mask_for(KQ);
     double target = rtol * beta0;  // beta0 <= 0: the norm of the first residual of this call (a whole solve by s-step cycles)
     const bool direct = comm->size == 1 && direct_host();
     auto length_for = [&](double from) {  // iterations for the reduction from -> target at GMRES's observed tail rate
-      return (int)std::ceil(per_decade * std::log10(std::max(from / target, 1.0)));
+      return (int)std::ceil(opt.sstep_per_decade * std::log10(std::max(from / target, 1.0)));
     };
-    int its = 0, weak = 0, na = 0, newest = -1;  // na pairs in use; `newest`: slot of the most recent one
+    int its = 0, weak = 0;
     double cur = cur0;
     bool have_r = false;
     while (true) {
@@ -2286,8 +2147,6 @@ struct Engine {
       std::vector<long double> G, yv;
       int nv = 0, rank = 0;
       double k0n = 0.0, rho = 0.0;
-      // order of the augmentation pairs in the least-squares problem: newest first (the truncation keeps a prefix)
-      int aslot[2] = {newest, 1 - newest};
       while (true) {
         for (int i = built + 1; i <= want; i++) {
           adv_apply(gm_V[i - 1], qstar, t, gamma);
@@ -2295,7 +2154,7 @@ struct Engine {
           its++;
         }
         built = want;
-        nv = built + 1 + na;  // K_0 .. K_built, then the images c_j of the augmentation vectors
+        nv = built + 1;  // K_0 .. K_built
         const int npair = nv * (nv + 1) / 2;
         const int nb = std::min(std::min(dot_blocks, vec_blocks(NQ)), (dot_blocks * MAXV) / npair);
         tally(LC_DOT, bQ() * nv);
@@ -2304,7 +2163,7 @@ struct Engine {
         auto gram = [&](auto tag) {
           constexpr int NV = decltype(tag)::value;
           VecList<NV> vl;
-          for (int q = 0; q < NV; q++) vl.p[q] = q <= built ? gm_V[q] : (q < nv ? aug_c[aslot[q - built - 1]] : nullptr);
+          for (int q = 0; q < NV; q++) vl.p[q] = q <= built ? gm_V[q] : nullptr;
           if (big(NQ)) k_gram<NV, true><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, vl, nv, d_part, mk);
           else k_gram<NV, false><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, vl, nv, d_part, mk);
         };
@@ -2326,46 +2185,31 @@ struct Engine {
         if (beta0 <= 0.0) { beta0 = k0n; target = rtol * beta0; if (beta0 == 0.0) return its; }
         if (k0n <= target || k0n == 0.0) return its;  // the iterate the cycle started from had converged already
         rank = sstep_ls(G, nv, nv - 1, yv, rho);
-        if (debug_on()) fprintf(stderr, "[sstep]   basis of %d + %d (rank %d): |Mr|/|Mr0| %.3e, predicted %.3e\n", built, na, rank, k0n / beta0, rho / beta0);
+        if (debug_on()) fprintf(stderr, "[sstep]   basis of %d (rank %d): |Mr|/|Mr0| %.3e, predicted %.3e\n", built, rank, k0n / beta0, rho / beta0);
         // enough (with a margin for the accuracy of the prediction), rank deficient, or no room left: take the step
         if (rho <= 0.7 * target || rank < built || built >= smax) break;
         want = std::min(smax, built + std::max(1, length_for(rho / 0.7)));
       }
       n_sstep_cycles++;
-      // update list: K_0 .. K_built, c_1 .. c_na, u_1 .. u_na
-      const int nvu = built + 1 + 2 * na;
+      const int nvu = built + 1;  // update list: K_0 .. K_built
       Coefs cx, cr;
       for (int i = 0; i < 32; i++) cx.c[i] = cr.c[i] = 0.0;
       cr.c[0] = 1.0;
       for (int i = 0; i < std::min(rank, built); i++) { cx.c[i] = (double)yv[i]; cr.c[i + 1] = -(double)yv[i]; }
-      for (int j = 0; j < na; j++)
-        if (built + j < rank) { cr.c[built + 1 + j] = -(double)yv[built + j]; cx.c[built + 1 + na + j] = (double)yv[built + j]; }
-      tally(LC_VEC, bQ() * (nvu + 3 + (NA > 0 ? 2 : 0)));
+      tally(LC_VEC, bQ() * (nvu + 3));
       tally(LC_OTHER, 0.0);
-      // the new pair goes to a free slot, or replaces the oldest one (elementwise in place: a thread reads before it writes)
-      int slot = -1;
-      if (NA > 0) slot = na < NA ? na : aslot[na - 1];
       {
         const int nb = std::min(dot_blocks, vec_blocks(NQ));
         VecList<HDG_SSTEP_MAXU> vl;
-        for (int q = 0; q < HDG_SSTEP_MAXU; q++) {
-          if (q <= built) vl.p[q] = gm_V[q];
-          else if (q < built + 1 + na) vl.p[q] = aug_c[aslot[q - built - 1]];
-          else if (q < nvu) vl.p[q] = aug_u[aslot[q - built - 1 - na]];
-          else vl.p[q] = nullptr;
-        }
-        double* uo = slot >= 0 ? aug_u[slot] : nullptr;
-        double* co = slot >= 0 ? aug_c[slot] : nullptr;
-        if (big(NQ)) k_sstep_update<HDG_SSTEP_MAXU, true><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, x, gm_V[0], vl, nvu, cx, cr, d_part, mk, uo, co);
-        else k_sstep_update<HDG_SSTEP_MAXU, false><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, x, gm_V[0], vl, nvu, cx, cr, d_part, mk, uo, co);
+        for (int q = 0; q < HDG_SSTEP_MAXU; q++) vl.p[q] = q <= built ? gm_V[q] : nullptr;
+        if (big(NQ)) k_sstep_update<HDG_SSTEP_MAXU, true><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, x, gm_V[0], vl, nvu, cx, cr, d_part, mk);
+        else k_sstep_update<HDG_SSTEP_MAXU, false><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, x, gm_V[0], vl, nvu, cx, cr, d_part, mk);
         int dmin = fl.get(x);
-        for (int l = 0; l <= built; l++) dmin = std::min(dmin, fl.get(basis_key(l)));
-        if (na > 0) dmin = 0;
+        for (int l = 0; l <= built; l++) dmin = std::min(dmin, fl.get(gm_V[l]));
         fl.set(x, dmin);
-        fl.set(basis_key(0), dmin);
+        fl.set(gm_V[0], dmin);
         k_reduce_parts<<<1, 256, 0, stream>>>(nb, 1, d_part, d_gram, direct ? h_gram : nullptr);
       }
-      if (slot >= 0) { newest = slot; na = std::min(na + 1, NA); }
       comm->allreduce_sum(d_gram, 1, stream);
       n_reduce++;
       if (!direct) HIPCHECK(hipMemcpyAsync(h_gram, d_gram, sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -2373,7 +2217,7 @@ struct Engine {
       const double rn = std::sqrt(std::max(h_gram[0], 0.0));
       if (!(rn == rn)) throw NotConverged{"s-step cycle: NaN residual"};
       if (debug_on())
-        fprintf(stderr, "[sstep] cycle of %d + %d (rank %d): |Mr|/|Mr0| %.3e -> %.3e (predicted %.3e)\n", built, nv - built - 1, rank, k0n / beta0, rn / beta0, rho / beta0);
+        fprintf(stderr, "[sstep] cycle of %d (rank %d): |Mr|/|Mr0| %.3e -> %.3e (predicted %.3e)\n", built, rank, k0n / beta0, rn / beta0, rho / beta0);
       if (rn <= target) return its;
       if (its >= cfg.tent_maxit) throw NotConverged{"tentative-velocity s-step iteration reached max iterations"};
       weak = (rn > 0.5 * k0n) ? weak + 1 : 0;
@@ -2418,16 +2262,12 @@ struct Engine {
     std::vector<std::complex<double>> ritz;
     double beta0 = 0.0, beta = 0.0, lo, hi;
     int its = 0;
-    // re-estimate period: 64 solves of a stage (round 3: 16).  The bounds of the preconditioned operator barely move between
-    // time steps and a wrong interval is caught by the growth guard below, which re-estimates at once; every estimate costs an
-    // Arnoldi cycle and a re-learnt hand-over point (C3, 20 + 5 steps: 85.45 -> 82.71 ms/step, 15.55 -> 14.55 iterations)
-    static const int est_every = std::getenv("HDG_CHEB_EVERY") ? std::atoi(std::getenv("HDG_CHEB_EVERY")) : 64;
-    static const int head_m = std::getenv("HDG_CHEB_M") ? std::atoi(std::getenv("HDG_CHEB_M")) : 6;
-    const bool estimate = ch_lmin[didx] <= 0 || (ch_count[didx] % est_every) == 0;
+    // re-estimate period opt.cheb_every: a wrong interval is caught by the growth guard below, which re-estimates at once
+    const bool estimate = ch_lmin[didx] <= 0 || (ch_count[didx] % opt.cheb_every) == 0;
     ch_count[didx]++;
     if (estimate) {
       ch_hand[didx] = 0;  // the hand-over point is learnt anew with the bounds
-      its = gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, &ritz, head_m, &beta0, &beta);
+      its = gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, &ritz, opt.cheb_m, &beta0, &beta);
       if (beta <= rtol * beta0 || beta0 == 0.0) return its;
       lo = 1e300; hi = -1e300;
       for (auto v : ritz) { lo = std::min(lo, v.real()); hi = std::max(hi, v.real()); }
@@ -2438,21 +2278,12 @@ struct Engine {
       //  convergence is larger than the interval, so 1.3 is enough for k >= 2 (1.5 for k = 1), and a stage whose Chebyshev
       //  iteration had to fall back to GMRES widens its own factor for all later solves: ch_widen)
       const bool hyb = cfg.tent_precond == 2;
-      static const double e_lo = std::getenv("HDG_CHEB_FLO") ? std::atof(std::getenv("HDG_CHEB_FLO")) : -1.0;
-      static const double e_hi = std::getenv("HDG_CHEB_FHI") ? std::atof(std::getenv("HDG_CHEB_FHI")) : -1.0;
+      const double e_lo = opt.cheb_flo, e_hi = opt.cheb_fhi;
       const double f_lo = e_lo > 0 ? e_lo : (hyb ? 0.9 : 0.8);
       const double f_hi = (e_hi > 0 ? e_hi : (hyb ? (cfg.degree == 1 ? 1.5 : 1.3) : 1.15)) * ch_widen[didx];
       lo *= f_lo; hi *= f_hi;
       if (ch_lmin[didx] > 0) { lo = std::min(lo, ch_lmin[didx]); hi = std::max(hi, ch_lmax[didx]); }
-      // HDG_CHEB_PROVISIONAL = t (experiment, off): bounds from an opening cycle that reduced the residual below t serve this
-      // solve only.  Idea: such a cycle spans a nearly invariant subspace and its extreme Ritz values react to perturbations of
-      // 1e-12 of the data (k = 2, 128^2, first solve of a run: smallest Ritz value 0.70 or 0.21).  Measured with t = 1e-6
-      // (tools/robustness_sweep.py, 8 steps): nothing gains, k = 4 / 256^2 centred flux 25.3 -> 43.5 iterations, CFL 0.1 at k = 2
-      // 13.1 -> 16.8 -- the Ritz values of a nearly invariant subspace are GOOD eigenvalue estimates; the odd outlier is caught
-      // by the growth guard below.
-      static const double prov = std::getenv("HDG_CHEB_PROVISIONAL") ? std::atof(std::getenv("HDG_CHEB_PROVISIONAL")) : 0.0;
-      if (beta <= prov * beta0) { ch_lmin[didx] = ch_lmax[didx] = -1.0; }
-      else { ch_lmin[didx] = lo; ch_lmax[didx] = hi; }
+      ch_lmin[didx] = lo; ch_lmax[didx] = hi;
       if (debug_on()) {
         fprintf(stderr, "[cheb] stage %d ritz:", didx);
         for (auto v : ritz) fprintf(stderr, " %.3f%+.3fi", v.real(), v.imag());
@@ -2460,14 +2291,6 @@ struct Engine {
       }
     } else {
       // bounds of this stage are known (refreshed every 16th solve): start the Chebyshev iteration at once
-      static const bool sstep_only = std::getenv("HDG_TENT_SSTEP_ONLY") != nullptr;  // experiment: no Chebyshev phase at all
-      if (sstep_only && !basis_f32) {
-        adv_apply(x, qstar, wQ2, gamma, b);
-        tent_precond(didx, wQ2, wQ1);
-        beta0 = std::sqrt(dot(NQ, wQ1, wQ1, KQ));
-        if (beta0 == 0.0) return 0;
-        return sstep_mr(qstar, gamma, didx, b, x, rtol, beta0, beta0);
-      }
       lo = ch_lmin[didx]; hi = ch_lmax[didx];
       adv_apply(x, qstar, wQ2, gamma, b);
       tent_precond(didx, wQ2, wQ1);
@@ -2481,7 +2304,7 @@ struct Engine {
     // a fat ellipse (at 128^2: real [1, 4.8] / [1, 4.2] / [1, 5.5], |imag| <= 1.2 / 1.4 / 2.2 for k = 1 / 2 / 3):
     // bim = 0.5 a is within a few iterations of the best value for k = 1, 2 (measured scan), while
     // bim = 0 loses 10+ iterations.
-    static const double ell = std::getenv("HDG_CHEB_ELL") ? std::atof(std::getenv("HDG_CHEB_ELL")) : -1.0;
+    const double ell = opt.cheb_ell;
     // k = 2: a THIN ellipse (0.3) for the bulk, then the hand-over to GMRES below; k = 1 (operator so cheap that a GMRES
     // iteration costs 3-4 Chebyshev iterations): the wider ellipse that converges on its own (scans: DESIGN.md section 9)
     const double frac = ell >= 0 ? ell : (cfg.tent_precond == 2 ? (cfg.degree >= 2 ? 0.3 : 0.5) : 0.0);
@@ -2498,7 +2321,7 @@ struct Engine {
     // Method selection: a wide / fat ellipse (large implicit weight or CFL: ARS3(4,4,3), the implicit tableau,
     // dt > 0.25/nx) predicts a slow Chebyshev iteration; GMRES then needs 40-80 iterations where Chebyshev
     // needs 100-160 and is as fast or faster in wall time (tools/robustness_sweep.py) and has no parameters.
-    static const int cheb_max_expected = std::getenv("HDG_CHEB_MAX_EXPECTED") ? std::atoi(std::getenv("HDG_CHEB_MAX_EXPECTED")) : 64;
+    const int cheb_max_expected = opt.cheb_max_expected;
     if (expected > cheb_max_expected || (!estimate && ch_slow[didx])) {
       if (debug_on()) fprintf(stderr, "[cheb] stage %d: %d iterations predicted on [%.3f, %.3f] -> GMRES\n", didx, expected, lo, hi);
       return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0);
@@ -2527,12 +2350,11 @@ struct Engine {
       // of the previous solve of this stage known: every 8th iteration up to 4 before it (enough to catch
       // growth), every 2nd from there on; without history every 4th.
       const int kfine = ch_last[didx] > 0 ? std::max(4, (ch_last[didx] - ch_head - 4) & ~1) : 0;
-      static const int fine_step = std::getenv("HDG_CHEB_FINE_STEP") ? std::atoi(std::getenv("HDG_CHEB_FINE_STEP")) : 2;
-      static const double handover_env = std::getenv("HDG_CHEB_HANDOVER") ? std::atof(std::getenv("HDG_CHEB_HANDOVER")) : -1.0;
+      const int fine_step = opt.cheb_fine_step;
+      const double handover_env = opt.cheb_handover;
       // k = 2: 0.3 with the s-step tail of round 4 (scan at C3, ms/step: 0.1-0.3: 85.5-85.8, 0.35: 91.2, 0.45: 95.6, 0.6: 95.1, 0.8:
       // 100.8; with the GMRES(8) tail of round 3 the optimum was 0.6); k >= 3: 0.4 (no sensitivity between 0.25 and 0.6); k = 1: off
-      static const bool tail_gm = std::getenv("HDG_TAIL_GMRES") != nullptr;
-      const double handover = handover_env >= 0.0 ? handover_env : (cfg.tent_precond == 2 ? (cfg.degree >= 3 ? 0.4 : (cfg.degree == 2 ? (tail_gm ? 0.6 : 0.3) : 0.0)) : 0.0);
+      const double handover = handover_env >= 0.0 ? handover_env : (cfg.tent_precond == 2 ? (cfg.degree >= 3 ? 0.4 : (cfg.degree == 2 ? (opt.tail_gmres ? 0.6 : 0.3) : 0.0)) : 0.0);
       const bool check = kfine > 0 ? (k < kfine ? (k % 8 == 0) : ((k - kfine) % fine_step == 0)) : (k % 4 == 0);
       const double rn = 1.0 / (2.0 * sigma - rho);
       adv_apply(cur, qstar, t, gamma, b);
@@ -2575,15 +2397,12 @@ struct Engine {
           // imaginary parts that the ellipse leaves out; a GMRES iteration costs 2-3 Chebyshev iterations (Krylov basis
           // traffic) but removes exactly those.  Hand over as soon as the observed rate is worse than what GMRES buys per
           // unit of cost, unless the end is a few iterations away anyway.
-          static const int hand_min_k = std::getenv("HDG_CHEB_MIN_K") ? std::atoi(std::getenv("HDG_CHEB_MIN_K")) : 6;
-          if (handover > 0.0 && k >= hand_min_k && obs > handover && remaining > 6.0) tail = true;
+          if (handover > 0.0 && k >= opt.cheb_min_k && obs > handover && remaining > 6.0) tail = true;
           if (tail) ch_hand[didx] = k_prev;  // the segment (k_prev, k] was the slow one: hand over at k_prev next time
         }
         // round 4: with the s-step tail (an iteration of which costs what a Chebyshev iteration costs) the solves that follow
         // hand over AT the learnt point instead of spending two more iterations on confirming the slow rate again
-        static const bool tail_gmres_ = std::getenv("HDG_TAIL_GMRES") != nullptr;
-        static const bool no_learn = std::getenv("HDG_CHEB_NO_LEARNT_HANDOVER") != nullptr;
-        if (!tail && !tail_gmres_ && !no_learn && !basis_f32 && handover > 0.0 && ch_hand[didx] > 0 && k >= ch_hand[didx] &&
+        if (!tail && !opt.tail_gmres && handover > 0.0 && ch_hand[didx] > 0 && k >= ch_hand[didx] &&
             nz > rtol * beta0)
           tail = true;
         k_prev = k; nz_prev = nz;
@@ -2602,13 +2421,11 @@ struct Engine {
                     growing ? "growing" : (tail ? "slow tail" : "stalled"), nz, last);
           finish_in_x();
           // the tail after a hand-over is 3-4 decades = 5-7 GMRES iterations: one cycle of 8, no restart in between
-          static const int hand_cycle = std::getenv("HDG_CHEB_HAND_CYCLE") ? std::atoi(std::getenv("HDG_CHEB_HAND_CYCLE")) : 8;
           // round 4: the tail as s-step minimal-residual cycles (no Gram-Schmidt passes); HDG_TAIL_GMRES restores the GMRES cycle
-          static const bool tail_gmres = std::getenv("HDG_TAIL_GMRES") != nullptr;
-          if (tail && !tail_gmres && !basis_f32) return its + sstep_mr(qstar, gamma, didx, b, x, rtol, beta0, nz);
+          if (tail && !opt.tail_gmres) return its + sstep_mr(qstar, gamma, didx, b, x, rtol, beta0, nz);
           struct Guard { bool& f; bool old; ~Guard() { f = old; } } guard_{arnoldi_only, arnoldi_only};
           arnoldi_only = true;  // robustness path after a growing / stalled iteration: the Arnoldi form
-          return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0, tail ? hand_cycle : 4);
+          return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0, tail ? opt.cheb_hand_cycle : 4);
         }
         last = std::min(last, nz);
       }
@@ -2646,10 +2463,9 @@ struct Engine {
     const double theta = 0.5 * (cheb_lmax + cheb_lmin), delta = 0.5 * (cheb_lmax - cheb_lmin);
     const double sigma1 = theta / delta;
     double rho = 1.0 / sigma1;
-    static const bool fuse = !std::getenv("HDG_TRACE_NO_FUSE");
     // round 3: the first step of the zero-start smoother and the prolongation folded into the stencil launches that consume
     // them (HDG_TRACE_NO_FOLD: the separate launches of round 2)
-    static const bool fold = !std::getenv("HDG_TRACE_NO_FOLD");
+    const bool fuse = opt.trace_fuse, fold = opt.trace_fold;
     if (general) {
       if (xc) { csr(gs().amg.P0, xc, 1.0, 1.0, x); xc = nullptr; }
     } else if (xc && !(its == 2 && fuse && fold && !periodic)) { p1_to_trace(xc, x, 1.0); xc = nullptr; }
@@ -2697,11 +2513,8 @@ struct Engine {
   void vcycle(int lev) {
     int n = mg_n[lev];
     long nv = (long)(n + 1) * (n + 1);
-    static const int nsw = std::getenv("HDG_MG_SWEEPS") ? std::atoi(std::getenv("HDG_MG_SWEEPS")) : 2;
-    // coarsest-level sweeps: 6 -> 2 leaves every CG iteration count unchanged (C2: 15.57 -> 15.05 ms/step, C3 neutral)
-    static const int ncoarse = std::getenv("HDG_MG_COARSE") ? std::atoi(std::getenv("HDG_MG_COARSE")) : 2;
-    static const bool use_tail = !std::getenv("HDG_MG_NO_TAIL");
-    if (use_tail && n <= 32) {
+    const int nsw = opt.mg_sweeps, ncoarse = opt.mg_coarse;
+    if (opt.mg_tail && n <= 32) {
       // all remaining levels fit one workgroup's LDS: run the tail of the V-cycle in a single kernel
       P1Tail tl;
       tl.nlev = 0;
@@ -2724,8 +2537,7 @@ struct Engine {
       p1_smooth(lev, ncoarse, true);
       return;
     }
-    static const bool fuse_legs = !std::getenv("HDG_MG_NO_FUSE");
-    if (fuse_legs && nsw >= 1 && nsw <= HDG_P1_MAXSW && (n & 1) == 0) {
+    if (opt.mg_fuse && nsw >= 1 && nsw <= HDG_P1_MAXSW && (n & 1) == 0) {
       // one kernel per leg (LDS tiles with recomputed halos), bit-identical to the launches below
       const int nt = (n + 1 + HDG_P1_TS - 1) / HDG_P1_TS;
       auto down = [&](auto tag) {
@@ -2745,7 +2557,6 @@ struct Engine {
       if (nsw == 1) down(std::integral_constant<int, 1>{});
       else if (nsw == 2) down(std::integral_constant<int, 2>{});
       else down(std::integral_constant<int, 3>{});
-      if (lev == 0 && xp_at == 2 && !xp_riding) xp_launch(true);
       vcycle(lev + 1);
       if (nsw == 1) up(std::integral_constant<int, 1>{});
       else if (nsw == 2) up(std::integral_constant<int, 2>{});
@@ -2769,8 +2580,7 @@ struct Engine {
   double* tail_M = nullptr;
   int tail_lev = -1, tail_pitch = 0;
   void build_dense_tail() {
-    static const bool off = std::getenv("HDG_MG_NO_DENSE_TAIL") != nullptr || std::getenv("HDG_MG_NO_TAIL") != nullptr;
-    if (off || periodic || general || mg_n.empty()) return;
+    if (!opt.mg_dense_tail || periodic || general || mg_n.empty()) return;
     int lev = 0;
     while (lev < (int)mg_n.size() && mg_n[lev] > 32) lev++;
     if (lev >= (int)mg_n.size() - 1) return;  // no tail, or a single level: nothing to gain
@@ -2782,12 +2592,10 @@ struct Engine {
     double* M = dalloc((long)N * pitch);
     {
       // every column in one launch: workgroup c applies the tail kernel to the c-th unit vector
-      static const int nsw = std::getenv("HDG_MG_SWEEPS") ? std::atoi(std::getenv("HDG_MG_SWEEPS")) : 2;
-      static const int ncoarse = std::getenv("HDG_MG_COARSE") ? std::atoi(std::getenv("HDG_MG_COARSE")) : 2;
       P1Tail tl;
       tl.nlev = 0;
       for (int l = lev; l < (int)mg_n.size(); l++) tl.n[tl.nlev++] = mg_n[l];
-      k_p1_vcycle_tail<<<N, 1024, 0, stream>>>(tl, nullptr, MT, nsw, ncoarse, pitch);
+      k_p1_vcycle_tail<<<N, 1024, 0, stream>>>(tl, nullptr, MT, opt.mg_sweeps, opt.mg_coarse, pitch);
     }
     k_transpose_sq<<<dim3((N + 255) / 256, N), 256, 0, stream>>>(N, pitch, MT, M);
     HIPCHECK(hipStreamSynchronize(stream));
@@ -2799,8 +2607,7 @@ struct Engine {
   // c-th unit vector (n^2 <= 1024 columns of ~45 small launches each, once per engine: a few tenths of a second)
   bool building_tail = false;
   void build_dense_tail_periodic() {
-    static const bool off = std::getenv("HDG_MG_NO_DENSE_TAIL") != nullptr || std::getenv("HDG_MG_NO_TAIL") != nullptr || std::getenv("HDG_MG_NO_FUSE") != nullptr;
-    if (off || !periodic || mg_n.empty()) return;
+    if (!opt.mg_dense_tail_periodic || !periodic || mg_n.empty()) return;
     int lev = 0;
     while (lev < (int)mg_n.size() && mg_n[lev] > 32) lev++;
     if (lev == 0 || lev >= (int)mg_n.size() - 1) return;  // no level above the tail (nothing fused), or a single level: nothing to gain
@@ -2836,10 +2643,7 @@ struct Engine {
   // Needs ny a multiple of 32 and >= 64 (C3 on 8 ranks: 128); otherwise the replicated cycle is used.
   static constexpr int MG_HALO = 40;
   bool mg_distributed() const {
-    static const bool off = std::getenv("HDG_MG_REPLICATED") != nullptr;
-    static const bool fuse_legs = !std::getenv("HDG_MG_NO_FUSE");
-    static const int nsw = std::getenv("HDG_MG_SWEEPS") ? std::atoi(std::getenv("HDG_MG_SWEEPS")) : 2;
-    return !off && fuse_legs && nsw == 2 && mg_gather && comm->size > 1 && !periodic && halo_on && mg_n.size() >= 2 &&
+    return !opt.mg_replicated && opt.mg_fuse && opt.mg_sweeps == 2 && mg_gather && comm->size > 1 && !periodic && halo_on && mg_n.size() >= 2 &&
            mg_n[0] > 32 && (g.ny % HDG_P1_TS) == 0 && g.ny >= 2 * HDG_P1_TS && (g.nx & 1) == 0 &&
            (size_t)(MG_HALO + 1) * (g.nx + 1) <= cap_halo;
   }
@@ -2870,8 +2674,7 @@ struct Engine {
   void vcycle_periodic(int lev) {
     const int n = mg_n[lev];
     const long nv = (long)n * n;
-    static const int nsw = std::getenv("HDG_MG_SWEEPS") ? std::atoi(std::getenv("HDG_MG_SWEEPS")) : 2;
-    static const int ncoarse = std::getenv("HDG_MG_COARSE") ? std::atoi(std::getenv("HDG_MG_COARSE")) : 2;
+    const int nsw = opt.mg_sweeps, ncoarse = opt.mg_coarse;
     const dim3 grid((n + 63) / 64, n);
     auto sweeps = [&](int cnt, bool reverse) {
       for (int sw = 0; sw < cnt; sw++) {
@@ -2882,14 +2685,13 @@ struct Engine {
     // second half of round 4: the fused LDS-tile legs (k_p1_down / k_p1_up, PER = true: wrapped loads, every vertex interior) for
     // n > 32 and the tail n <= 32 as one dense product (build_dense_tail_periodic), as on the unit square; the legs carry the
     // p / x half of the CG update as side jobs there too.  HDG_MG_NO_FUSE / HDG_MG_NO_DENSE_TAIL: the per-level kernels below.
-    static const bool fuse_legs = !std::getenv("HDG_MG_NO_FUSE");
     if (tail_M && lev == tail_lev) {
       const int N = n * n;
       tally(LC_MG, 16.0 * N);
       k_p1_dense_tail<<<(N + 3) / 4, 256, 0, stream>>>(N, tail_pitch, tail_M, mg_b[lev], mg_x[lev]);
       return;
     }
-    if (fuse_legs && nsw == 2 && n > 32 && lev + 1 < (int)mg_n.size() && !building_tail) {
+    if (opt.mg_fuse && nsw == 2 && n > 32 && lev + 1 < (int)mg_n.size() && !building_tail) {
       const int nt = (n + HDG_P1_TS - 1) / HDG_P1_TS;
       int extra = 0;
       SideXP sj = xp_side_slice(lev, nt, extra);
@@ -2914,12 +2716,9 @@ struct Engine {
   // z = M r for the condensed system
   // LDS-tiled form of the two smoother applications (hdg_trace_tile.hpp): single rank, non-periodic structured mesh,
   // two Chebyshev steps.  HDG_TRACE_NO_TILE: the five row-stencil launches of before.
-  // form of the tile kernels: one thread per edge (hdg_trace_tile3.hpp) or one per corner (hdg_trace_tile.hpp); read per engine
-  // Measured (pressure solve, ms; corner form -> edge form): C3 6.24 -> 6.92, k = 3 at 512^2 3.16 -> 3.42, C2 1.03 -> 1.10 -- six
-  // instead of three waves per SIMD buy nothing where the corner form fits, the three-fold index arithmetic and the wider
-  // barriers cost; k = 4 at 512^2 (row-stencil kernels -> edge form) 5.32 -> 4.60.  Default: the edge form at k = 4 only.
-  int trace_tile3_env = std::getenv("HDG_TRACE_TILE3") ? std::atoi(std::getenv("HDG_TRACE_TILE3")) : -1;
-  bool tile3() const { return trace_tile3_env >= 0 ? trace_tile3_env != 0 : K >= 4; }
+  // form of the tile kernels: one thread per edge (hdg_trace_tile3.hpp) or one per corner (hdg_trace_tile.hpp); default: the edge
+  // form at k = 4 only (measurements beside Options::trace_tile3)
+  bool tile3() const { return opt.trace_tile3 >= 0 ? opt.trace_tile3 != 0 : K >= 4; }
   static constexpr int TILE_HALO_R = 5;
   // Periodic strips: the shortest strip that is accepted.  Every exchange sends at most the strip's own rows (the solvers'
   // depth is Dx = min(DX_DEFAULT, ny), the tiled preconditioner's TILE_HALO_R only runs on strips of >= 8 rows), so one row
@@ -2927,16 +2726,11 @@ struct Engine {
   // a case nothing else exercises.  Two rows is the shortest strip the unit-square partition is tested at as well.
   static constexpr int PERIODIC_MIN_ROWS = 2;  // ghost rows of r the tiled preconditioner reads on a strip (pre: 3 computed + 2 halo)
   bool use_trace_tile() const {
-    static const bool off = std::getenv("HDG_TRACE_NO_TILE") != nullptr;
-    static const int nsm = std::getenv("HDG_TRACE_SMOOTH_ITS") ? std::atoi(std::getenv("HDG_TRACE_SMOOTH_ITS")) : 2;
-    static const bool fuse = !std::getenv("HDG_TRACE_NO_FUSE");
-    static const bool strips = !std::getenv("HDG_TRACE_NO_TILE_STRIPS");  // round 4: the tile kernels on a strip partition too
     // k = 4: the post kernel needs 274 VGPRs (15 trace values per corner and stage): 5.88 instead of 5.65 ms per solve at 512^2
     // periodic square: the wrapped ghost rows play the neighbours' part (every tile reaches at most 3 columns / 5 rows beyond)
-    static const bool per_ok = !std::getenv("HDG_TRACE_NO_TILE_PERIODIC");
-    if (periodic && !(per_ok && g.nx >= 16 && g.ny >= 8)) return false;
-    return !off && fuse && nsm == 2 && cfg.trace_precond == 1 && !general && halo_on && (K <= 3 || tile3()) &&
-           (comm->size == 1 || (strips && g.ny >= TILE_HALO_R));
+    if (periodic && !(opt.trace_tile_periodic && g.nx >= 16 && g.ny >= 8)) return false;
+    return opt.trace_tile && opt.trace_fuse && opt.trace_smooth_its == 2 && cfg.trace_precond == 1 && !general && halo_on &&
+           (K <= 3 || tile3()) && (comm->size == 1 || (opt.trace_tile_strips && g.ny >= TILE_HALO_R));
   }
   // periodic strips: the vertex grid has exactly ny rows and every rank restricts onto its own ny/P of them (k_trace_to_p1p at
   // rows pj0 ..), so the rank blocks are disjoint and lie in rank order: ONE all-gather, in place, assembles the global
@@ -2978,47 +2772,22 @@ struct Engine {
   // instead of k_reduce_parts + k_cg_sr_scalars)
   bool defer_tile_reduce = false;
   int tile_nblk_deferred = 0;
-  // Experiment (HDG_CG_FUSED_RUPDATE=1, off; trace_cg_sr, one rank, corner-form tiles, non-periodic): the residual half of the
-  // update (s, r) inside the next pre tile kernel (k_trace_pre_tile<K, true>), which writes into second buffers; ru_flush() runs
-  // it as its own launch instead.  Measured (pressure solve, ms; own launch -> fused): C3 6.17 -> 6.47, k = 3 at 512^2
-  // 3.15 -> 3.30, C2 0.99 -> 1.05: the tile kernel loads r, w and s with its halo (1.9 x) at a third of the streaming rate --
-  // dearer than the 54 us launch it saves.
-  bool cg_no_fused_r = std::getenv("HDG_CG_FUSED_RUPDATE") == nullptr;  // read per engine
-  double *cg_r2 = nullptr, *cg_s2 = nullptr;
-  bool ru_pending = false, ru_fused = false;
-  double *ru_r = nullptr, *ru_s = nullptr, *ru_r_alt = nullptr, *ru_s_alt = nullptr;
-  void ru_flush() {
-    if (!ru_pending) return;
-    ru_pending = false;
-    k_cg_sr_update_r<<<vec_blocks(NLv), 256, 0, stream>>>(NLv, d_cgs, cg_Ap, ru_s, ru_r);
-  }
-  bool ru_fusable() const { return comm->size == 1 && !periodic && !general && !tile3() && use_trace_tile(); }
-  // trace_cg_sr with the tile preconditioner: the half of the update nothing reads before the next update (p, x) runs on
-  // a second stream underneath the vertex-grid V-cycle, whose launches are latency-bound and leave HBM idle
-  hipStream_t xstream = nullptr;
-  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;
-  bool xp_pending = false, xp_inflight = false;
-  int xp_at = std::getenv("HDG_CG_XP_AT") ? std::atoi(std::getenv("HDG_CG_XP_AT")) : 1;  // experiment: where the second stream starts
-  // below this vector size the two cross-stream dependencies cost more than the overlap gains (C2: +14 us per iteration)
-  long split_min_bytes = std::getenv("HDG_CG_SPLIT_MIN_MB") ? std::atol(std::getenv("HDG_CG_SPLIT_MIN_MB")) << 20 : 0L;
+  // trace_cg_sr with the tile preconditioner: the half of the update nothing reads before the next update (p, x) rides on the
+  // leg launches of the V-cycle (k_p1_down / k_p1_up side jobs, hdg_kernels.hpp: SideXP), a share of the pairs per leg by
+  // weight (opt.cg_xp_w0); what the legs did not take (no fused legs, odd tail entry) is done by
+  // xp_launch() as a launch of its own.  (A second stream underneath the cycle was measured and removed: DESIGN.md section 9.)
+  bool xp_pending = false;
   double* xp_x = nullptr;
-  // xp_mode 1 (default): the update rides on the leg launches of the V-cycle (k_p1_down / k_p1_up side jobs, hdg_kernels.hpp:
-  // SideXP), a share of the pairs per leg by weight (the finest level's legs run 18 us, the others 6-8); what the legs did
-  // not take (no fused legs, odd tail entry) is done by xp_launch() behind the cycle.  xp_mode 0: second stream.
-  int xp_mode = std::getenv("HDG_CG_XP_MODE") ? std::atoi(std::getenv("HDG_CG_XP_MODE")) : 1;
-  double xp_w0 = std::getenv("HDG_CG_XP_W0") ? std::atof(std::getenv("HDG_CG_XP_W0")) : 1.6;
   long xp_done = 0;      // pairs already handed to side jobs
   double xp_wsum = 0.0;  // sum of the leg weights of one cycle
   bool xp_riding = false;
   void xp_ride_begin() {
     xp_done = 0; xp_riding = false;
-    if (!xp_pending || xp_mode != 1 || general || mg_n.empty()) return;
-    static const bool fuse_legs = !std::getenv("HDG_MG_NO_FUSE");
-    if (!fuse_legs) return;
+    if (!xp_pending || general || mg_n.empty() || !opt.mg_fuse) return;
     // strips: the finest level is distributed (vcycle_distributed_top launches its legs itself); the replicated levels carry the update
     const size_t l0 = mg_distributed() ? 1 : 0;
     xp_wsum = 0.0;
-    for (size_t l = l0; l + 1 < mg_n.size() && mg_n[l] > 32 && (mg_n[l] & 1) == 0; l++) xp_wsum += 2.0 * (l == 0 ? xp_w0 : 1.0);
+    for (size_t l = l0; l + 1 < mg_n.size() && mg_n[l] > 32 && (mg_n[l] & 1) == 0; l++) xp_wsum += 2.0 * (l == 0 ? opt.cg_xp_w0 : 1.0);
     xp_riding = xp_wsum > 0.0;
   }
   SideXP xp_side_slice(int lev, int nt, int& extra_rows) {
@@ -3026,7 +2795,7 @@ struct Engine {
     SideXP sj{};
     if (!xp_riding) return sj;
     const long total = NLv >> 1;
-    long cnt = (long)std::ceil((double)total * (lev == 0 ? xp_w0 : 1.0) / xp_wsum);
+    long cnt = (long)std::ceil((double)total * (lev == 0 ? opt.cg_xp_w0 : 1.0) / xp_wsum);
     cnt = std::min(cnt, total - xp_done);
     if (cnt <= 0) return sj;
     sj = SideXP{d_cgs, cg_z, tr_one, cg_p, xp_x, xp_done, xp_done + cnt};
@@ -3036,46 +2805,22 @@ struct Engine {
     return sj;
   }
   static int xp_period(int nt, int extra) { return side_row_period(nt, extra); }  // hdg_side_rows.hpp
-  void xp_launch(bool overlap) {
+  void xp_launch() {
     if (!xp_pending) return;
     xp_pending = false;
     const long done = xp_riding ? xp_done : 0;
     xp_riding = false; xp_done = 0;
     const int nvb = vec_blocks(NLv - 2 * done);
-    if (!overlap || done > 0) {
-      if (done < (NLv >> 1) || (NLv & 1)) k_cg_sr_update_xp<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_p, xp_x, done);
-      return;
-    }
-    if (!xstream) {
-      // lowest priority: the workgroups of the V-cycle legs are dispatched ahead of the (short-lived) blocks of the update
-      int pr_least = 0, pr_greatest = 0;
-      HIPCHECK(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-      static const bool no_prio = std::getenv("HDG_CG_XP_NO_PRIORITY") != nullptr;
-      if (no_prio) HIPCHECK(hipStreamCreateWithFlags(&xstream, hipStreamNonBlocking));
-      else HIPCHECK(hipStreamCreateWithPriority(&xstream, hipStreamNonBlocking, pr_least));
-      HIPCHECK(hipEventCreateWithFlags(&ev_x0, hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_x1, hipEventDisableTiming));
-    }
-    HIPCHECK(hipEventRecord(ev_x0, stream));
-    HIPCHECK(hipStreamWaitEvent(xstream, ev_x0, 0));
-    k_cg_sr_update_xp<<<nvb, 256, 0, xstream>>>(NLv, d_cgs, cg_z, tr_one, cg_p, xp_x);
-    HIPCHECK(hipEventRecord(ev_x1, xstream));
-    xp_inflight = true;
-  }
-  void xp_join() {
-    if (!xp_inflight) return;
-    xp_inflight = false;
-    HIPCHECK(hipStreamWaitEvent(stream, ev_x1, 0));
+    if (done < (NLv >> 1) || (NLv & 1)) k_cg_sr_update_xp<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_p, xp_x, done);
   }
   bool trace_precond(const double* r, double* z, double* w_out = nullptr, bool* dots_out = nullptr) {
     if (dots_out) *dots_out = false;
-    if (ru_pending && !ru_fusable()) ru_flush();
     if (cfg.trace_precond == 0) {
       zero(z, NLv);
       trace_cheb(r, ch_d, z, 0.0, 1.0);
       return false;
     }
-    static const int nsm = std::getenv("HDG_TRACE_SMOOTH_ITS") ? std::atoi(std::getenv("HDG_TRACE_SMOOTH_ITS")) : 2;
+    const int nsm = opt.trace_smooth_its;
     if (use_trace_tile()) {
       const double theta = 0.5 * (cheb_lmax + cheb_lmin), delta = 0.5 * (cheb_lmax - cheb_lmin), sigma1 = theta / delta;
       const double rho = 1.0 / sigma1, rn = 1.0 / (2.0 * sigma1 - rho), c0 = 1.0 / theta, c1 = rn * rho, c2 = 2.0 * rn / delta;
@@ -3086,7 +2831,7 @@ struct Engine {
       if (periodic && comm->size == 1) halo_L(r, TILE_HALO_R);  // (k_wrap_rows: every ghost row from the opposite side)
       else if (comm->size > 1) {
         if (fl.get(r) < TILE_HALO_R) { halo_L(r, TILE_HALO_R); fl.set(r, TILE_HALO_R); }
-        else if (flow_check) flow_check_input(r, FL, TILE_HALO_R);
+        else if (opt.flow_check) flow_check_input(r, FL, TILE_HALO_R);
       }
       auto launch = [&](auto kk) {
         constexpr int KK = decltype(kk)::value;
@@ -3099,22 +2844,15 @@ struct Engine {
         tally(LC_TRACE_SMOOTH, 3 * bL());
         typedef TraceTile3<KK> T3;
         if (tile3()) k_trace_pre_tile3<KK><<<grid_pre, T3::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
-        else if (ru_pending) {  // (ru_fusable(): checked on entry) with the residual half of the CG update; r' lands in the second buffer
-          k_trace_pre_tile<KK, true><<<grid_pre, TT::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), ru_r, c0, c1, c2, ch_d, wL2, d_cgs, cg_Ap, ru_s,
-                                                                            ru_s_alt, ru_r_alt);
-          r = ru_r_alt;
-          ru_pending = false; ru_fused = true;
-        } else k_trace_pre_tile<KK><<<grid_pre, TT::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
+        else k_trace_pre_tile<KK><<<grid_pre, TT::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
         xp_ride_begin();  // the deferred half of the CG update: on the legs of the vertex-grid cycle ...
-        if (!xp_riding && xp_at == 1) xp_launch(true);  // ... or underneath it on its own stream
+        if (!xp_riding) xp_launch();  // ... or, where no leg can carry it, as a launch of its own
         coarse_correction(wL2);
-        xp_launch(true);  // (not started by now: a cycle without the hook)
-        xp_join();        // the post kernel overwrites z
+        xp_launch();  // what the legs did not take; the post kernel overwrites z
         tally(LC_TRACE_SMOOTH, (w_out ? 4 : 3) * bL() + nvtx);
         const long nblk = (long)ntx * nty;
         double* part = nullptr;
-        static const bool no_fused_dots = getenv("HDG_TRACE_NO_FUSED_DOTS") != nullptr;
-        if (w_out && dots_out && !no_fused_dots) {
+        if (w_out && dots_out && opt.trace_fused_dots) {
           if (tile_part_cap < nblk * 5) { tile_part = dalloc(nblk * 5); tile_part_cap = nblk * 5; }
           part = tile_part;
         }
@@ -3185,7 +2923,7 @@ struct Engine {
     // multigrid hierarchy on the vertex grid (general meshes: algebraic hierarchy of the P1 space)
     if (cfg.trace_precond == 1 && general) setup_general_amg(gops.S, gsets[0].amg);
     else if (cfg.trace_precond == 1) {
-      if (comm->size > 1 || std::getenv("HDG_FORCE_RCCL")) mg_gather = dalloc((long)comm->size * (g.ny + 1) * (g.nx + 1));
+      if (comm->size > 1 || opt.force_rccl) mg_gather = dalloc((long)comm->size * (g.ny + 1) * (g.nx + 1));
       int n = g.nx;
       while (true) {
         mg_n.push_back(n);
@@ -3199,7 +2937,7 @@ struct Engine {
     psets.push_back(PSet{dt, 0.0, 0.0, cfg.tau});
     estimate_cheb(0);
     use_pset(0);
-    if (const char* e = std::getenv("HDG_TRACE_BACKWARD_TOL")) bwd_tol = std::atof(e);
+    bwd_tol = opt.trace_backward_tol;
   }
   // largest eigenvalue of Dinv * (-S) by power iteration (PETSc estimates it with a few GMRES
   // steps and uses [0.1, 1.1] * lambda_max as Chebyshev interval)
@@ -3222,9 +2960,8 @@ struct Engine {
       lam = std::sqrt(dot(NLv, cg_z, cg_z, KL));
       copy(cg_p, cg_z, NLv);
     }
-    static const double flo = std::getenv("HDG_TRACE_CHEB_LO") ? std::atof(std::getenv("HDG_TRACE_CHEB_LO")) : 0.1;
     psets[idx].lmax = 1.1 * lam;
-    psets[idx].lmin = flo * lam;
+    psets[idx].lmin = opt.trace_cheb_lo * lam;
     cur_pset = saved;
   }
   // operator set for a stabilisation parameter tau' (created on first use)
@@ -3336,15 +3073,13 @@ struct Engine {
   // already taken the step to x_{k+1}, which is harmless (a further CG step) and keeps the host off the critical path.
   // Returns the number of iterations the convergence test needed (the extra step is not counted).
   int trace_cg_sr(double* b, double* x, double rtol, int maxit, bool strict) {
-    const bool no_split = cg_no_split, no_fused = cg_no_fused_scalars;
     auto leave = [&]() {  // a deferred p / x update left over at the exit is the step beyond the tested iterate: dropped
-      xp_pending = false; ru_pending = false; ru_fused = false;
+      xp_pending = false;
       defer_tile_reduce = false; tile_nblk_deferred = 0;
-      if (xp_inflight) { xp_inflight = false; (void)hipStreamWaitEvent(stream, ev_x1, 0); }
     };
     try {
-      defer_tile_reduce = comm->size == 1 && !no_fused;
-      const int its = trace_cg_sr_body(b, x, rtol, maxit, strict, !no_split && use_trace_tile() && NLv * 8L >= split_min_bytes);
+      defer_tile_reduce = comm->size == 1 && opt.cg_fused_scalars;
+      const int its = trace_cg_sr_body(b, x, rtol, maxit, strict, opt.cg_split_update && use_trace_tile());
       leave();
       return its;
     } catch (...) {
@@ -3359,9 +3094,7 @@ struct Engine {
     trace_apply(x, b, 1.0, -1.0, cg_r);  // r = b - T x
     if (tr_one_nn < 0) tr_one_nn = dot(NLv, tr_one, tr_one, KL);
     if (!cg_s) cg_s = dalloc(NLv);
-    const bool fuse_r = split && !cg_no_fused_r && ru_fusable();
-    if (fuse_r && !cg_r2) { cg_r2 = dalloc(NLv); cg_s2 = dalloc(NLv); }
-    double *r_cur = cg_r, *s_cur = cg_s, *r_alt = cg_r2, *s_alt = cg_s2;  // (r_cur == cg_r on entry: r = b - T x above)
+    double *const r_cur = cg_r, *const s_cur = cg_s;
     const int nvb = vec_blocks(NLv);
     HIPCHECK(hipMemsetAsync(d_cgs, 0, sizeof(double) * 8, stream));
     double norm0 = -1.0;
@@ -3387,10 +3120,9 @@ struct Engine {
     int since_best = 0, replaced = 0, drifts = 0, patience = 5;
     bool trigger_breakdown = false;
     bool restart = true, true_residual = true;  // the first pass starts from r = b - T x as well
-    static const double floor_c = std::getenv("HDG_CG_FLOOR_C") ? std::atof(std::getenv("HDG_CG_FLOOR_C")) : 32.0;
+    const double floor_c = opt.cg_floor_c;
     auto replace_residual = [&](const char* why, double at, bool is_breakdown) {
-      xp_launch(false);  // the true residual needs the current iterate
-      ru_pending = false;  // (the pending residual update is overwritten; the restart needs no s)
+      xp_launch();  // the true residual needs the current iterate
       if (drifts >= 2) throw NotConverged{std::string("trace CG: ") + why + " after two residual replacements that confirmed a drifted recurrence"};
       replaced++;
       trigger_nrm = at; trigger_breakdown = is_breakdown;
@@ -3403,9 +3135,7 @@ struct Engine {
     };
     while (true) {
       bool have_dots = false;
-      ru_fused = false;
       const bool have_w = trace_precond(r_cur, cg_z, cg_Ap, &have_dots);
-      if (ru_fused) { std::swap(r_cur, r_alt); std::swap(s_cur, s_alt); ru_fused = false; }  // the pre kernel left r', s' in the second buffers
       if (!have_w) trace_apply(cg_z, nullptr, 0.0, 1.0, cg_Ap);  // w = T z
       if (!have_dots) multidot(NLv, cg_z, {tr_one, r_cur, cg_z, cg_Ap}, nullptr, KL, true);  // (z,n), (z,r), (z,z), (z,w), (n,r) -> d_res
       tally(LC_OTHER, 0.0);
@@ -3420,10 +3150,8 @@ struct Engine {
       HIPCHECK(hipEventRecord(cg_ev, stream));
       if (split) {
         // r first (the next preconditioner application waits for it); p and x when that application reaches its V-cycle
-        if (fuse_r) { ru_pending = true; ru_r = r_cur; ru_s = s_cur; ru_r_alt = r_alt; ru_s_alt = s_alt; }  // inside the next pre kernel
-        else k_cg_sr_update_r<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_Ap, s_cur, r_cur);
+        k_cg_sr_update_r<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_Ap, s_cur, r_cur);
         xp_pending = true; xp_x = x;
-        if (xp_at == 0 && xp_mode != 1) xp_launch(true);
       } else
         k_cg_sr_update<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_Ap, cg_p, s_cur, x, r_cur);
       fl.set(s_cur, restart ? fl.get(cg_Ap) : std::min(fl.get(s_cur), fl.get(cg_Ap)));
@@ -3436,7 +3164,7 @@ struct Engine {
       const bool breakdown = h_cgs[6] == 1.0;  // alpha was set to 0: the update just queued leaves x alone
       double zz = h_cgs[4];
       if (h_cgs[6] == 2.0) {  // z almost parallel to the null vector: measure the projected norm explicitly
-        xp_launch(false);  // (the deferred update reads the unprojected z)
+        xp_launch();  // (the deferred update reads the unprojected z)
         axpby(NLv, -h_cgs[3], tr_one, 1.0, cg_z);
         fl.set(cg_z, 0);
         zz = dot(NLv, cg_z, cg_z, KL);
@@ -3450,7 +3178,7 @@ struct Engine {
       if (cg_floor > 0.0 && nrm <= cg_floor) return its;  // backward-error stop (experiment, see pressure_solve)
       if (was_true && replaced > 0) {
         // the true preconditioned residual after a replacement: at its rounding floor?
-        xp_launch(false);
+        xp_launch();
         const double xn = std::sqrt(std::max(dot(NLv, x, x, KL), 0.0));
         if (debug_cg()) fprintf(stderr, "[cg] it %d: true |z| %.3e, floor %.3e (|x| %.3e)\n", its, nrm, floor_c * 2.220446049250313e-16 * xn, xn);
         if (nrm <= floor_c * 2.220446049250313e-16 * xn) { ev_cg_floor_exits++; return its; }
@@ -3462,7 +3190,7 @@ struct Engine {
         replace_residual("p.Ap <= 0", nrm, true);
       } else {
         if (nrm < best) { best = nrm; since_best = 0; } else since_best++;
-        const bool forced = cg_force_replace > 0 && its == cg_force_replace && replaced == 0;  // test hook
+        const bool forced = opt.cg_force_replace > 0 && its == opt.cg_force_replace && replaced == 0;  // test hook
         if (forced || (its > 0 && since_best >= patience && nrm <= 1e3 * rtol * norm0)) replace_residual(forced ? "forced (test hook)" : "stall", nrm, false);
       }
       if (its >= maxit) {
@@ -3474,13 +3202,10 @@ struct Engine {
   }
   // residual replacements / floor exits of the condensed solves since the last reset (hdg_get_solver_events)
   long ev_cg_replacements = 0, ev_cg_floor_exits = 0;
-  bool cg_no_split = std::getenv("HDG_CG_NO_SPLIT_UPDATE") != nullptr, cg_no_fused_scalars = std::getenv("HDG_CG_NO_FUSED_SCALARS") != nullptr;  // read per engine
-  int cg_force_replace = std::getenv("HDG_CG_FORCE_REPLACE") ? std::atoi(std::getenv("HDG_CG_FORCE_REPLACE")) : 0;  // test hook, read per engine
   int trace_cg(double* b, double* x, double rtol = -1.0, int maxit = -1, bool strict = true) {
     if (rtol < 0) rtol = cfg.trace_rtol;
     if (maxit < 0) maxit = cfg.trace_maxit;
-    static const bool host_scalars = std::getenv("HDG_CG_HOST_SCALARS") != nullptr;
-    static const bool two_red = std::getenv("HDG_CG_TWO_REDUCTIONS") != nullptr;
+    const bool host_scalars = opt.cg_host_scalars, two_red = opt.cg_two_reductions;
     if (!host_scalars && !two_red) return trace_cg_sr(b, x, rtol, maxit, strict);
     if (!host_scalars) return trace_cg_dev(b, x, rtol, maxit, strict);
     project_const(b);
@@ -3840,9 +3565,6 @@ struct Engine {
   V2 dg_r{nullptr, nullptr}, dg_w{nullptr, nullptr}, dg_b{nullptr, nullptr}, dg_x{nullptr, nullptr};
   double *dg_lam = nullptr, *dg_lam2 = nullptr, *dg_rp = nullptr, *dg_du = nullptr;
   const int* dg_ecl = nullptr;  // general meshes: (3 c + l) of the cells of every edge (k_g_dg_avg_trace)
-  // EXPERIMENT (HDG_DG_CC = c, read when an engine is built; default 0 = off): Cahouet-Chabard-type term of the Schur
-  // approximation, S^-1 ~ P_HDG^-1 + c dt alpha / h M_p^-1 (M_p = I in the orthonormal basis), structured meshes
-  const double dg_cc = std::getenv("HDG_DG_CC") ? std::atof(std::getenv("HDG_DG_CC")) : 0.0;
   void alloc_block(V2& v) { v = V2{dalloc(NQ), dalloc(NPv)}; }
   double dot_block(const V2& a, const V2& b) { return dot(NQ, a.u, b.u, KQ) + dot(NPv, a.p, b.p, KC); }
   void axpby_block(double a, const V2& x, double b, V2& y) { axpby(NQ, a, x.u, b, y.u); axpby(NPv, a, x.p, b, y.p); }
@@ -3892,7 +3614,6 @@ struct Engine {
     backsub(nullptr, dg_rp, dg_lam2, dg_du, z.p);
     use_pset(0);
     axpby(NQ, 1.0, dg_du, 1.0, z.u);
-    if (dg_cc != 0.0 && !general) axpby(NPv, dg_cc * dtt * cfg.alpha_penalty / g.h, dg_rp, 1.0, z.p);
   }
   // K_dg (u, y) = b; x holds the initial guess
   int dg_solve(const double* qstar, double dtt, const V2& b, V2& x) {
@@ -4158,8 +3879,7 @@ struct Engine {
       }
       return;
     }
-    static const bool one_by_one = std::getenv("HDG_CG_MASS_ONE_BY_ONE") != nullptr;
-    if (!one_by_one) {  // both components in one solve
+    if (!opt.cg_mass_one_by_one) {  // both components in one solve
       if (!cg_b2) for (double** v : {&cg_b2, &cg_x2, &cg_pp2, &cg_Ap3}) *v = dalloc(cgt.ncg);
       for (int d = 0; d < 2; d++) {
         HDG_DISPATCH(k_cg_cell<KK, 1><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
@@ -4703,7 +4423,7 @@ static int create_impl(const hdg_config* cfg, int rank, int nranks, int backend,
   try {
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed (no GPU?)"; return HDG_ERR_HIP; }
     std::unique_ptr<hdg::Comm> comm;  // owned here until the engine has been built
-    if (nranks == 1 && std::getenv("HDG_FORCE_RCCL")) {
+    if (nranks == 1 && hdg::options_from_env().force_rccl) {
       // smoke path: exercise RCCL initialisation, all-reduce and all-gather with a 1-rank communicator
       ncclUniqueId id;
       if (ncclGetUniqueId(&id) != ncclSuccess) { g_create_error = "ncclGetUniqueId failed"; return HDG_ERR_COMM; }
@@ -4963,7 +4683,7 @@ int hdg_get_kernel_forms(hdg_handle* h, int* forms) {
   HDG_API_BEGIN(h)
   if (!forms) throw std::string("forms is NULL");
   forms[0] = E.general ? 3 : (E.use_mfma_lift() ? 2 : (E.lift_pair() ? 1 : 0));
-  forms[1] = E.general ? 3 : ((E.cfg.degree >= hdg::Engine::mfma_min_degree() && !E.periodic && !std::getenv("HDG_NO_MFMA_ADV")) ? 2 : 0);
+  forms[1] = E.general ? 3 : (E.use_mfma_adv() ? 2 : 0);
   forms[2] = E.general ? 3 : (E.use_trace_tile() ? (E.tile3() ? 2 : 1) : 0);
   forms[3] = E.general ? 3 : (E.use_mfma_schur() ? 2 : 0);
   HDG_API_END(h)

@@ -176,16 +176,9 @@ __device__ __forceinline__ void corner_dinv(const DevTables& T, const CornerInfo
 template <int NL>
 __device__ __forceinline__ int plane_of(int q) { return q < NL ? q : (q < 2 * NL ? 2 * NL + (q - NL) : NL + (q - 2 * NL)); }
 
-// UPD (one rank, Engine::trace_cg_sr): the residual half of the preceding CG update rides along -- the kernel reads r, w and s of
-// the previous iteration, forms s' = w + beta s and r' = r - alpha s' (k_cg_sr_update_r; alpha = sc[1], beta = sc[2]) on every
-// corner it loads, smooths r', and stores r' and s' of its own corners into SECOND buffers (a neighbouring tile still reads the
-// old values as its halo).  One launch and 1.9 of 6.9 vector passes fewer per CG iteration.
-template <int K, bool UPD = false>
+template <int K>
 __global__ __launch_bounds__(TraceTile<K>::NTHREADS) void k_trace_pre_tile(int ntx, int nty, Geo g, TileRows tr, DevTables T, const double* __restrict__ r, double c0, double c1,
-                                                         double c2, double* __restrict__ z_out, double* __restrict__ res_out,
-                                                         const double* __restrict__ sc = nullptr, const double* __restrict__ w_in = nullptr,
-                                                         const double* __restrict__ s_in = nullptr, double* __restrict__ s_out = nullptr,
-                                                         double* __restrict__ r_out = nullptr) {
+                                                         double c2, double* __restrict__ z_out, double* __restrict__ res_out) {
   typedef TraceTile<K> TT;
   constexpr int NL = TT::NL, NT = TT::NT, TW = TT::TW, TH = TT::TH, W2 = TT::W2, H2 = TT::H2, W1 = TT::W1, H1 = TT::H1, KMAX = TT::KMAX;
   __shared__ double Ds[NT * TT::N2];  // d0 on the halo-2 region
@@ -202,21 +195,6 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) void k_trace_pre_tile(int n
       const int jc = j0 - 2 + lj;
       const CornerInfo c = corner_info(g, tr, i0 - 2 + li, jc);
       load_corner<NL>(r, g, c, rr[k]);
-      if (UPD) {
-        const double alpha = sc[1], beta = sc[2];
-        double ww[NT], ss[NT];
-        load_corner<NL>(w_in, g, c, ww);
-        load_corner<NL>(s_in, g, c, ss);
-#pragma unroll
-        for (int q = 0; q < NT; q++) {
-          ss[q] = (beta == 0.0) ? ww[q] : fma(beta, ss[q], ww[q]);
-          rr[k][q] = fma(-alpha, ss[q], rr[k][q]);
-        }
-        if (c.exists && c.own_x && li >= 2 && li < W2 - 2 && lj >= 2 && lj < H2 - 2 && jc < tr.jhi) {
-          store_corner<NL>(s_out, g, c, ss);
-          store_corner<NL>(r_out, g, c, rr[k]);
-        }
-      }
       corner_dinv<NL>(T, c, c0, rr[k], dd[k]);
 #pragma unroll
       for (int q = 0; q < NT; q++) Ds[(plane_of<NL>(q) * H2 + lj) * W2 + li] = dd[k][q];

@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_general_mesh_scale.py: Kelvin-Helmholtz runs on the unit disk in a process of its own (the engine
-reads HDG_AMG_MAX_COARSE / HDG_AMG_UNFUSED once per process).  usage: general_scale_worker.py LEVEL RUNS OUTFILE, RUNS a
+reads HDG_AMG_MAX_COARSE / HDG_AMG_UNFUSED when an engine is built; a process of its own keeps the cases apart).  usage: general_scale_worker.py LEVEL RUNS OUTFILE, RUNS a
 comma-separated list of run names of tests/general_mesh_checks.py kh_runs: ssp2_k<K>_<fused|solve>, implicit_k<K>_<proj|mono>"""
 import os
 import sys

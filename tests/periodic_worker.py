@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_periodic.py: a few HDG-IMEX steps of the double-layer shear flow on the periodic square in a process of
-its own (environment switches that the engine reads once per process).  usage: periodic_worker.py K NX NSTEPS OUTFILE"""
+its own (environment switches that the engine reads when it is built).  usage: periodic_worker.py K NX NSTEPS OUTFILE"""
 import os
 import sys
 

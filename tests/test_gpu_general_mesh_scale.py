@@ -8,8 +8,8 @@ meshes used here against the level-6 disk's).
 (a) level-4 disk (2048 cells) against the oracle: every operator at k = 1, 2, 3; the continuous space, tracer and DG
     operators at k = 1, 2; two SSP2(3,3,2) steps of the Kelvin-Helmholtz data with the tracer (fused and per solve, k = 1, 2)
     and one implicit step (both branches, k = 1).
-(b) the same steps with a forced algebraic hierarchy (HDG_AMG_MAX_COARSE=40, in a worker process: the engine reads the switch
-    once per process): the [amg] line of HDG_DEBUG reports 1 089 -> 133 -> 13 vertices for the projection
+(b) the same steps with a forced algebraic hierarchy (HDG_AMG_MAX_COARSE=40, in a worker process of its own; the engine reads the
+    switch when it is built): the [amg] line of HDG_DEBUG reports 1 089 -> 133 -> 13 vertices for the projection
     method's operator, two smoothed levels before the dense solve; the
     unfused smoother (HDG_AMG_UNFUSED) gives the same fields and, iteration by iteration, the same preconditioned CG
     residuals (HDG_DEBUG_CG); once more fused / unfused on the level-5 disk with the default hierarchy (4 225 -> 493, dense).

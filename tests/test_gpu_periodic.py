@@ -120,7 +120,7 @@ def test_periodic_steps_through_the_tiled_trace_preconditioner(hip_lib, k, nx):
 def test_periodic_fused_vcycle_legs_equal_the_per_level_kernels(hip_lib, tmp_path, k, nx):
     """The vertex-grid V-cycle of the periodic square with the fused LDS-tile legs (k_p1_down / k_p1_up, PER = true: wrapped
     loads, every vertex interior) for n > 32 and the tail n <= 32 as one dense product, carrying the p / x half of the CG update
-    as side jobs -- against the per-level kernels (HDG_MG_NO_FUSE, read once per process: two worker processes).  The legs form
+    as side jobs -- against the per-level kernels (HDG_MG_NO_FUSE, read when an engine is built; two worker processes keep the runs apart).  The legs form
     every vertex value by the same expression in the same order, the dense tail is the same linear map to rounding: fields at
     1e-9, same CG counts.  64: one leg level above the tail; 128: two; 80: tiles that wrap inside their halo (80 = 2.5 tiles)."""
     import os

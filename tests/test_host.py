@@ -470,6 +470,48 @@ def test_side_rows_of_a_leg_launch_cover_every_row_once(tmp_path):
     assert out.startswith("ok 28070"), out
 
 
+def test_options_table_defaults_kinds_and_implied_switches(tmp_path):
+    """csrc/hdg_options.hpp (plain C++, compiled here with g++): with an empty environment every field has the default
+    DESIGN.md section 14 states, each kind of value (flag, negated flag, integer, real, lo:hi range) parses, and the switches
+    that imply others (no tail -> no dense tail; periodic dense tail needs the fused legs; NO_OVERLAP wins) resolve there."""
+    import shutil
+    import subprocess
+
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "options_check"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "options_check.cpp")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), src], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
+def test_every_switch_is_read_in_one_place_and_every_switch_a_test_sets_exists():
+    """The environment is read in csrc/hdg_options.hpp only (one table, one lifetime: when an engine is built), and every
+    HDG_* variable a file under tests/ or tools/ puts into an environment is a name of that table (or one the Python loader
+    reads): a test or a scan cannot set a switch that silently does nothing."""
+    csrc = os.path.join(ROOT, "incompressibleeulerhdg_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f != "hdg_options.hpp":
+            assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+    table = open(os.path.join(csrc, "hdg_options.hpp")).read()
+    known = set(re.findall(r'"(HDG_[A-Z0-9_]+)"', table))
+    assert len(known) > 50 and all(table.count(f'"{n}"') == 1 for n in known)  # every name listed exactly once
+    known.add("HDG_" + "LIB_PATH")  # incompressibleeulerhdg_amd/_lib.py: an alternative build of the library
+    # NAME=value (shell, dict(os.environ, NAME=...); not a -D compile-time knob), or "NAME" as a key / argument
+    sets = re.compile(r"""(?<!-D)\b(HDG_[A-Z0-9_]+)(?:=(?!=)|["']\s*[:,\])])""")
+    unknown = {}
+    for top in ("tests", "tools"):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith((".py", ".sh")):
+                    for n in sets.findall(open(os.path.join(d, f)).read()):
+                        if n not in known:
+                            unknown.setdefault(n, []).append(os.path.join(d, f))
+    assert not unknown, unknown
+
+
 def test_unit_disk_mesh_numbering_independent_invariants():
     """UnitDiskMesh (driver.py:184-185) is restated from memory of Firedrake's utility mesh on both the product and the
     oracle side -- no reference fixture covers its numbering or coordinates (parity unpinned).  What any correct

@@ -1,5 +1,5 @@
 """Reads a rocprofv3 kernel trace (CSV) and prints, for the condensed CG, the gap between the end of k_trace_pre_tile and the
-start of the following k_trace_post_tile, and how the deferred p / x update (k_cg_sr_update_xp, second stream) sits in it."""
+start of the following k_trace_post_tile, and how the deferred p / x update (k_cg_sr_update_xp, where no V-cycle leg carries it) sits in it."""
 import csv, sys
 rows = []
 for r in csv.DictReader(open(sys.argv[1])):
