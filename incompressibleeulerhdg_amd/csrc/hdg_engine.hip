@@ -28,6 +28,7 @@
 
 #include "../../include/hdg_mi355x.h"
 #include "hdg_options.hpp"
+#include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
 #include "hdg_kernels.hpp"
 #include "hdg_schur_mfma.hpp"
@@ -35,6 +36,9 @@
 #include "hdg_trace_tile3.hpp"
 #include "hdg_cg.hpp"
 #include "hdg_tables.hpp"
+#include "hdg_mfma_pack.hpp"
+#include "hdg_small_dense.hpp"
+#include "hdg_stage_coeffs.hpp"
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
 #include "hdg_amg.hpp"
@@ -232,12 +236,6 @@ struct Engine {
     HIPCHECK(hipMemcpy(p, v.data(), sizeof(double*) * v.size(), hipMemcpyHostToDevice));
     return (const double**)p;
   }
-  static dvec transpose(const dvec& a, int r, int c) {
-    dvec t(a.size());
-    for (int i = 0; i < r; i++)
-      for (int j = 0; j < c; j++) t[(size_t)j * r + i] = a[(size_t)i * c + j];
-    return t;
-  }
 
   dim3 cell_grid() const { return dim3(8 * g.rows_xcd * 2 * g.nbx, 1, 1); }
   dim3 corner_grid() const { return dim3(8 * g.rows_xcdc * g.nbxc, 1, 1); }
@@ -288,20 +286,14 @@ struct Engine {
     d.tpr = avg <= 3.0 ? 1 : (avg <= 6.0 ? 2 : (avg <= 12.0 ? 4 : (avg <= 24.0 ? 8 : (avg <= 48.0 ? 16 : (avg <= 96.0 ? 32 : 64)))));
     return d;
   }
+  // threads per row of a CSR kernel (DevCsr::tpr, chosen by upload_csr)
+  template <class F> static void by_tpr(const DevCsr& A, F&& f) { with_int<1, 2, 4, 8, 16, 32, 64>(A.tpr, "CSR threads per row", f); }
   // y = beta y + alpha A x
   void csr(const DevCsr& A, const double* x, double alpha, double beta, double* y) {
     tally(LC_OTHER, 12.0 * A.nnz + 8.0 * (A.ncols + A.nrows * (beta != 0.0 ? 2 : 1)));
     const long nthr = (long)A.nrows * A.tpr;
     const int nblk = (int)((nthr + 255) / 256);
-    switch (A.tpr) {
-      case 1: k_csr_apply<1><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      case 2: k_csr_apply<2><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      case 4: k_csr_apply<4><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      case 8: k_csr_apply<8><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      case 16: k_csr_apply<16><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      case 32: k_csr_apply<32><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-      default: k_csr_apply<64><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); break;
-    }
+    by_tpr(A, [&](auto t) { k_csr_apply<t()><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, y); });
     fl.set(y, 0);
   }
   // y = alpha A x + beta z
@@ -309,15 +301,7 @@ struct Engine {
     tally(LC_OTHER, 12.0 * A.nnz + 8.0 * (A.ncols + 2.0 * A.nrows));
     const long nthr = (long)A.nrows * A.tpr;
     const int nblk = (int)((nthr + 255) / 256);
-    switch (A.tpr) {
-      case 1: k_csr_apply3<1><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      case 2: k_csr_apply3<2><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      case 4: k_csr_apply3<4><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      case 8: k_csr_apply3<8><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      case 16: k_csr_apply3<16><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      case 32: k_csr_apply3<32><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-      default: k_csr_apply3<64><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); break;
-    }
+    by_tpr(A, [&](auto t) { k_csr_apply3<t()><<<nblk, 256, 0, stream>>>(A, x, alpha, beta, z, y); });
     fl.set(y, 0);
   }
   // P1 coarse space of the trace preconditioner on a general mesh and its algebraic hierarchy (hdg_amg.hpp)
@@ -392,20 +376,10 @@ struct Engine {
       const double* xin = zero_init ? nullptr : amg.x[l];
       tally(LC_OTHER, 2.0 * (12.0 * A.nnz + 8.0 * 5.0 * n));
       tally(LC_OTHER, 0.0);
-      auto run = [&](auto tt) {
-        constexpr int TT = decltype(tt)::value;
-        k_amg_cheb<TT, true><<<nblk, 256, 0, stream>>>(A, amg.dinv[l], amg.b[l], xin, r, d, nullptr, 1.0 / theta, 0.0, 0.0);
-        k_amg_cheb<TT, false><<<nblk, 256, 0, stream>>>(A, amg.dinv[l], amg.b[l], xin, r, d, amg.x[l], 0.0, rn * rho, 2.0 * rn / delta);
-      };
-      switch (A.tpr) {
-        case 1: run(std::integral_constant<int, 1>{}); break;
-        case 2: run(std::integral_constant<int, 2>{}); break;
-        case 4: run(std::integral_constant<int, 4>{}); break;
-        case 8: run(std::integral_constant<int, 8>{}); break;
-        case 16: run(std::integral_constant<int, 16>{}); break;
-        case 32: run(std::integral_constant<int, 32>{}); break;
-        default: run(std::integral_constant<int, 64>{}); break;
-      }
+      by_tpr(A, [&](auto t) {
+        k_amg_cheb<t(), true><<<nblk, 256, 0, stream>>>(A, amg.dinv[l], amg.b[l], xin, r, d, nullptr, 1.0 / theta, 0.0, 0.0);
+        k_amg_cheb<t(), false><<<nblk, 256, 0, stream>>>(A, amg.dinv[l], amg.b[l], xin, r, d, amg.x[l], 0.0, rn * rho, 2.0 * rn / delta);
+      });
       return;
     }
     copy(r, amg.b[l], n);
@@ -729,12 +703,15 @@ struct Engine {
   }
 
   // ------------------------------------------------------------------ kernel dispatch on K
-#define HDG_DISPATCH(...)             \
-  switch (K) {                        \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
+  // (hdg_dispatch.hpp; f receives the degree as a type: k_name<k()>)
+  template <class F> void by_degree(F&& f) const { with_int<1, 2, 3, 4>(K, "degree", f); }
+  template <class F> void by_mfma_degree(F&& f) const { with_int<3, 4>(K, "degree of a matrix-core kernel", f); }
+  template <class F> void by_pair_degree(F&& f) const { with_int<1, 2>(K, "degree of a pair kernel", f); }
+  // condense / backsub <K, HAS_W, HAS_P>: which of the right-hand sides r_w, r_p is there.  Three instantiations, not four:
+  // a call with neither runs the one for both (the kernels test the pointers they are given)
+  enum { RHS_W = 0, RHS_P = 1, RHS_BOTH = 2 };
+  template <class F> static void by_rhs(const double* rw, const double* rp, F&& f) {
+    with_int<RHS_W, RHS_P, RHS_BOTH>((rw && !rp) ? RHS_W : ((!rw && rp) ? RHS_P : RHS_BOTH), "right-hand sides", f);
   }
 
   // ------------------------------------------------------------------ halo rows (strip partition)
@@ -1005,190 +982,7 @@ struct Engine {
   dim3 cell_grid_of(const Geo& c) const { return dim3(8 * c.rows_xcd * 2 * c.nbx, 1, 1); }
   static dim3 corner_grid_of(const Geo& c) { return dim3(8 * c.rows_xcdc * c.nbxc, 1, 1); }
 
-  // ---- MFMA lift (k >= 3): tables in A-operand lane order for k_edge_lift_mfma.  Tile (mt, ks) of a matrix M:
-  // 64 doubles, entry l = M[16 mt + l % 16][4 ks + l / 16] (zero outside M).  Order: W (2 M-tiles), N'_0..2, G.
-  // Out[e]: 2nu x ne row-major lifting tables of shape s (Lift_e for the projection, (I - Dinv) Lift_e for the
-  // hybrid preconditioner).
-  std::vector<double> pack_lift_mfma(int s_, const dvec* Out) const {
-    const int n2 = 2 * tab->nu, ne = tab->ne, KS = 2 * ((tab->nu + 3) / 4), MT = (tab->nu + 7) / 8, KD = 5;
-    auto tile = [&](std::vector<double>& dstv, int rows, int cols, const std::vector<double>& M, int mt, int ks) {
-      for (int l = 0; l < 64; l++) {
-        const int r = 16 * mt + l % 16, c = 4 * ks + l / 16;
-        dstv.push_back((r < rows && c < cols) ? M[(size_t)r * cols + c] : 0.0);
-      }
-    };
-    std::vector<double> packed;
-    // The kernel assigns the velocity dofs to K slots / result rows so that a lane moves whole 16-byte component pairs
-    // (k_edge_lift_mfma); the tables are indexed n = d*nu + m: kcol[n] / krow[n] are the positions of table column / row n.
-    std::vector<int> kcol(n2), krow(n2);
-    for (int n = 0; n < n2; n++) { kcol[n] = scol(n); krow[n] = srow(n); }
-    // W: rows (e, a) packed as tile 0 = edges 0, 1, tile 1 = edge 2;  W = -N[s][e]
-    const int nc = 4 * KS;  // padded column count of the coefficient side
-    std::vector<double> W((size_t)32 * nc, 0.0);
-    for (int e = 0; e < 3; e++)
-      for (int a = 0; a < ne; a++)
-        for (int n = 0; n < n2; n++) W[(size_t)((e < 2 ? e * ne + a : 16 + a)) * nc + kcol[n]] = -tab->N[s_][e][a * n2 + n];
-    for (int mt = 0; mt < 2; mt++) for (int ks = 0; ks < KS; ks++) tile(packed, 32, nc, W, mt, ks);
-    // N'_e = N[1 - s][e], rows at their position inside the tile
-    for (int e = 0; e < 3; e++) {
-      std::vector<double> Np((size_t)16 * nc, 0.0);
-      for (int a = 0; a < ne; a++)
-        for (int n = 0; n < n2; n++) Np[(size_t)((e == 1 ? ne : 0) + a) * nc + kcol[n]] = tab->N[1 - s_][e][a * n2 + n];
-      for (int ks = 0; ks < KS; ks++) tile(packed, 16, nc, Np, 0, ks);
-    }
-    // G: columns = packed moments, K index q: q < 12 -> tile 0 row q, q >= 12 -> tile 1 row q - 12
-    std::vector<double> Gm((size_t)(16 * MT) * 20, 0.0);
-    for (int e = 0; e < 3; e++)
-      for (int a = 0; a < ne; a++) {
-        const int q = e < 2 ? e * ne + a : 12 + a;
-        for (int n = 0; n < n2; n++) Gm[(size_t)krow[n] * 20 + q] = Out[e][(size_t)n * ne + a];
-      }
-    for (int mt = 0; mt < MT; mt++) for (int kd = 0; kd < KD; kd++) tile(packed, 16 * MT, 20, Gm, mt, kd);
-    return packed;
-  }
-  // tables of k_adv_mfma in A-operand lane order: Phi, Gx, Gy (rows = quadrature points, columns = basis
-  // functions), then A2[m][q] = -w_q Phi[q][m] (rows = basis functions, columns = quadrature points)
-  std::vector<double> pack_adv_mfma(int s_) const {
-    const int nu = tab->nu, nq = tab->nqc, MTQ = (nq + 15) / 16, KSU = (nu + 3) / 4, MTU = (nu + 15) / 16;
-    std::vector<double> packed;
-    auto tile = [&](int rows, int cols, const std::vector<double>& M, int mt, int ks) {
-      for (int l = 0; l < 64; l++) {
-        const int r = 16 * mt + l % 16, c = 4 * ks + l / 16;
-        packed.push_back((r < rows && c < cols) ? M[(size_t)r * cols + c] : 0.0);
-      }
-    };
-    const dvec* T3[3] = {&tab->cPhi[s_], &tab->cGx[s_], &tab->cGy[s_]};
-    for (int t = 0; t < 3; t++) {
-      std::vector<double> M(T3[t]->begin(), T3[t]->end());  // nq x nu
-      for (int mt = 0; mt < MTQ; mt++) for (int ks = 0; ks < KSU; ks++) tile(nq, nu, M, mt, ks);
-    }
-    std::vector<double> A2((size_t)nu * nq);
-    for (int m = 0; m < nu; m++) for (int q = 0; q < nq; q++) A2[(size_t)m * nq + q] = -tab->cw[q] * tab->cPhi[s_][(size_t)q * nu + m];
-    for (int mu = 0; mu < MTU; mu++) for (int ks = 0; ks < 4 * MTQ; ks++) tile(nu, nq, A2, mu, ks);
-    // facet tables (k_adv_mfma): edge-point rows packed 8 per edge, tile 0 = edges 0, 1, tile 1 = edge 2
-    const int nqe = tab->nqe;
-    auto erow = [&](int e, int q) { return (e < 2 ? 8 * e : 16) + q; };
-    std::vector<double> EO((size_t)32 * nu, 0.0), EQX(EO), EQY(EO);
-    for (int e = 0; e < 3; e++)
-      for (int q = 0; q < nqe; q++)
-        for (int m = 0; m < nu; m++) {
-          const double po = tab->ePhi[s_][e][(size_t)q * nu + m];
-          EO[(size_t)erow(e, q) * nu + m] = po;
-          EQX[(size_t)erow(e, q) * nu + m] = tab->enx[e] * po;
-          EQY[(size_t)erow(e, q) * nu + m] = tab->eny[e] * po;
-        }
-    for (const std::vector<double>* M : {&EO, &EQX, &EQY})
-      for (int t = 0; t < 2; t++) for (int ks = 0; ks < KSU; ks++) tile(32, nu, *M, t, ks);
-    for (int e = 0; e < 3; e++) {  // neighbour trace rows of edge e inside its tile, zero elsewhere
-      std::vector<double> EN((size_t)16 * nu, 0.0);
-      for (int q = 0; q < nqe; q++)
-        for (int m = 0; m < nu; m++) EN[(size_t)((e == 1 ? 8 : 0) + q) * nu + m] = tab->ePhi[1 - s_][e][(size_t)q * nu + m];
-      for (int ks = 0; ks < KSU; ks++) tile(16, nu, EN, 0, ks);
-    }
-    std::vector<double> ET((size_t)nu * 24, 0.0);  // test: rows m, columns (e, q) packed: 8 e + q
-    for (int e = 0; e < 3; e++)
-      for (int q = 0; q < nqe; q++)
-        for (int m = 0; m < nu; m++) ET[(size_t)m * 24 + 8 * e + q] = tab->ePhi[s_][e][(size_t)q * nu + m];
-    for (int mu = 0; mu < MTU; mu++) for (int kd = 0; kd < 6; kd++) tile(nu, 24, ET, mu, kd);
-    return packed;
-  }
-  // ---- matrix-core Schur kernels (hdg_schur_mfma.hpp, k >= 3): local maps in A-operand lane order.
-  // tiles of a dense rows x cols matrix, order [mt][ks]; tile entry l = M[16 mt + l % 16][4 ks + l / 16] (zero outside)
-  static void pack_tiles(std::vector<double>& dst, const std::vector<double>& M, int rows, int cols, int MT, int KS) {
-    for (int mt = 0; mt < MT; mt++)
-      for (int ks = 0; ks < KS; ks++)
-        for (int l = 0; l < 64; l++) {
-          const int r = 16 * mt + l % 16, c = 4 * ks + l / 16;
-          dst.push_back((r < rows && c < cols) ? M[(size_t)r * cols + c] : 0.0);
-        }
-  }
-  int kap(int n) const { return 2 * (n % NU) + n / NU; }  // memory position (component-pair layout) of table dof n = d*NU + m
-  // K slot / result row of table dof n = d*NU + m in the matrix-core Schur kernels (16-byte accesses, hdg_schur_mfma.hpp)
-  int scol(int n) const { const int m = n % NU, d = n / NU; return 8 * (m / 4) + 4 * d + m % 4; }
-  int srow(int n) const { const int m = n % NU, d = n / NU; return 16 * (m / 8) + m % 4 + 4 * (2 * ((m % 8) / 4) + d); }
-  int sKSU() const { return 2 * ((NU + 3) / 4); }
-  int sMTU() const { return (NU + 7) / 8; }
-  // back-substitution  (u, phi) = Ainv (r_w, r_p) - W lambda:  rows [u in memory order, padded to 16 MTU | phi],
-  // columns [r_w in memory order, padded to 4 KSU | r_p padded to 4 KSP | lambda padded to 4 KST]
-  std::vector<double> pack_backsub_mfma(const dvec& Ai, const dvec& W_) const {
-    const int N2 = 2 * NU, NT = 3 * NL, KSU = sKSU(), KSP = (NP + 3) / 4, KST = (NT + 3) / 4, MTU = sMTU();
-    const int rows = 16 * (MTU + 1), cols = 4 * (KSU + KSP + KST);
-    std::vector<double> M((size_t)rows * cols, 0.0);
-    for (int n = 0; n < NX; n++) {
-      const int r = n < N2 ? srow(n) : 16 * MTU + (n - N2);
-      for (int c = 0; c < N2; c++) M[(size_t)r * cols + scol(c)] = Ai[(size_t)n * NX + c];
-      for (int m = 0; m < NP; m++) M[(size_t)r * cols + 4 * KSU + m] = Ai[(size_t)n * NX + N2 + m];
-      for (int q = 0; q < NT; q++) M[(size_t)r * cols + 4 * (KSU + KSP) + q] = -W_[(size_t)n * NT + q];
-    }
-    std::vector<double> out;
-    pack_tiles(out, M, rows, cols, MTU + 1, KSU + KSP + KST);
-    return out;
-  }
-  // condensation: one M-tile with rows (H, D, V) x NL; block 0 = Y_L (local edges 0, 1, 2 -> H, D, V), blocks 1, 2, 3 = the
-  // rows of Y_U that belong to D (local edge 1), H (0), V (2); columns [r_w in memory order | r_p] per block
-  std::vector<double> pack_condense_mfma(const dvec& Y0, const dvec& Y1) const {
-    const int N2 = 2 * NU, NT = 3 * NL, KSU = sKSU(), KSP = (NP + 3) / 4, KSA = KSU + KSP, cols = 4 * KSA;
-    std::vector<double> out;
-    for (int q = 0; q < 4; q++) {
-      std::vector<double> M((size_t)16 * cols, 0.0);
-      const dvec& Y = q == 0 ? Y0 : Y1;
-      for (int e = 0; e < 3; e++) {
-        if (q == 1 && e != 1) continue;
-        if (q == 2 && e != 0) continue;
-        if (q == 3 && e != 2) continue;
-        for (int a = 0; a < NL; a++) {
-          const int r = e * NL + a;  // local-edge order (0, 1, 2) = (H, D, V): the row order of the result tile
-          for (int c = 0; c < N2; c++) M[(size_t)r * cols + scol(c)] = Y[(size_t)r * NX + c];
-          for (int m = 0; m < NP; m++) M[(size_t)r * cols + 4 * KSU + m] = Y[(size_t)r * NX + N2 + m];
-        }
-      }
-      pack_tiles(out, M, 16, cols, 1, KSA);
-    }
-    (void)NT;
-    return out;
-  }
-  // pressure gradient: rows = velocity dofs in memory order, columns [p | lambda (e, m)]:  B^T p - sum_e sigma_e N_e^T lambda_e
-  std::vector<double> pack_pgrad_mfma(int sh) const {
-    const int N2 = 2 * NU, NT = 3 * NL, KSP = (NP + 3) / 4, KST = (NT + 3) / 4, MTU = sMTU(), cols = 4 * (KSP + KST);
-    std::vector<double> M((size_t)16 * MTU * cols, 0.0);
-    for (int n = 0; n < N2; n++) {
-      for (int m = 0; m < NP; m++) M[(size_t)srow(n) * cols + m] = tab->B[sh][(size_t)m * N2 + n];
-      for (int e = 0; e < 3; e++)
-        for (int m = 0; m < NL; m++) M[(size_t)srow(n) * cols + 4 * KSP + e * NL + m] = -tab->sig[sh][e] * tab->N[sh][e][(size_t)m * N2 + n];
-    }
-    std::vector<double> out;
-    pack_tiles(out, M, 16 * MTU, cols, MTU, KSP + KST);
-    return out;
-  }
-  // weak divergence: six NP x 2NU blocks (see k_weak_div_mfma); broken != 0: the single block B
-  std::vector<double> pack_weakdiv_mfma(int sh, bool broken) const {
-    const int N2 = 2 * NU, KSU = sKSU(), cols = 4 * KSU;
-    auto E = [&](int e, int from) {  // (sigma_e / 2) Pt_e^T N_e[0:NL] with N of shape `from`
-      std::vector<double> M((size_t)16 * cols, 0.0);
-      for (int r = 0; r < NP; r++)
-        for (int n = 0; n < N2; n++) {
-          double acc = 0.0;
-          for (int m = 0; m < NL; m++) acc += tab->Pt[sh][e][(size_t)m * NP + r] * tab->N[from][e][(size_t)m * N2 + n];
-          M[(size_t)r * cols + scol(n)] = 0.5 * tab->sig[sh][e] * acc;
-        }
-      return M;
-    };
-    std::vector<double> out;
-    std::vector<double> base((size_t)16 * cols, 0.0);
-    const dvec& B0 = broken ? tab->B[sh] : tab->D0[sh];
-    for (int r = 0; r < NP; r++)
-      for (int n = 0; n < N2; n++) base[(size_t)r * cols + scol(n)] = B0[(size_t)r * N2 + n];
-    if (broken) { pack_tiles(out, base, 16, cols, 1, KSU); return out; }
-    const std::vector<double> E1 = E(1, sh);
-    for (size_t q = 0; q < base.size(); q++) base[q] += E1[q];
-    pack_tiles(out, base, 16, cols, 1, KSU);
-    pack_tiles(out, E(0, sh), 16, cols, 1, KSU);
-    pack_tiles(out, E(2, sh), 16, cols, 1, KSU);
-    pack_tiles(out, E(0, 1 - sh), 16, cols, 1, KSU);
-    pack_tiles(out, E(1, 1 - sh), 16, cols, 1, KSU);
-    pack_tiles(out, E(2, 1 - sh), 16, cols, 1, KSU);
-    return out;
-  }
+  // ---- matrix-core kernels (k >= 3): device copies of the tables hdg_mfma_pack.hpp packs, uploaded on first use
   const double *pgm[2] = {nullptr, nullptr}, *wdm[2] = {nullptr, nullptr}, *wdbm[2] = {nullptr, nullptr};
   // HDG_NO_MFMA_SCHUR: the per-thread kernels at every degree (A/B timing, parity of the two formulations)
   bool use_mfma_schur() const {
@@ -1200,8 +994,8 @@ struct Engine {
     for (int sh = 0; sh < 2; sh++) {
       dvec Ai, W_, Y_, SK_;
       tab->poissonBlock(sh, ps.tau, Ai, W_, Y_, SK_);
-      ps.bsm[sh] = upload(pack_backsub_mfma(Ai, W_));
-      if (sh == 0) schur_Y0 = Y_; else ps.cdm = upload(pack_condense_mfma(schur_Y0, Y_));
+      ps.bsm[sh] = upload(pack_backsub_mfma(*tab, Ai, W_));
+      if (sh == 0) schur_Y0 = Y_; else ps.cdm = upload(pack_condense_mfma(*tab, schur_Y0, Y_));
     }
   }
   dvec schur_Y0;
@@ -1214,30 +1008,39 @@ struct Engine {
     return opt.mfma_lift && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general;  // the matrix-core kernels do not wrap column indices
   }
   static constexpr int MFMA_MIN_DEGREE = 3;  // the matrix-core kernels at k = 2 were 1.8-2 x slower
+  // k >= 3: the whole operator on the matrix cores (k_adv_mfma); HDG_NO_MFMA_ADV falls back to the per-thread kernels
+  bool use_mfma_adv() const { return opt.mfma_adv && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general; }
   bool lift_pair() const { return opt.lift_pair && K <= 2 && bs() == 128 && !general; }
+  // Which form of the lift and of the advection operator runs: decided here, launched by bdm / bdm_hybrid / adv_apply and
+  // reported by hdg_get_kernel_forms.  The enumerators of LiftForm are the integers of that call.  The two-lane advection
+  // form (k_adv_apply2) has no code of its own yet and reports 0 like the per-thread form: ADVICE.md, fourth finding.
+  enum class LiftForm { per_thread = 0, pair = 1, mfma = 2, general = 3 };
+  enum class AdvForm { per_thread, two_lane, mfma, general };
+  LiftForm lift_form() const {
+    return general ? LiftForm::general : use_mfma_lift() ? LiftForm::mfma : lift_pair() ? LiftForm::pair : LiftForm::per_thread;
+  }
+  AdvForm adv_form() const {
+    if (general) return AdvForm::general;
+    if (use_mfma_adv()) return AdvForm::mfma;
+    // without the matrix-core kernel: two lanes per cell, one velocity component each, at the degrees of opt.adv_split_*
+    return (K >= opt.adv_split_lo && K <= opt.adv_split_hi) ? AdvForm::two_lane : AdvForm::per_thread;
+  }
+  static int form_code(AdvForm f) { return f == AdvForm::general ? 3 : (f == AdvForm::mfma ? 2 : 0); }
   void lift_mfma(const Geo& gx, const double* t0, const double* t1, const double* in, double* out, double* chd_ = nullptr,
                  const double* chx_ = nullptr, double c1 = 0.0, double c2 = 0.0) {
     const dim3 grid(8 * gx.rows_xcd * 2);
-    if (chd_) {  // with the fused Chebyshev step
-      switch (cfg.degree) {
-        case 3: k_edge_lift_mfma<3, true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2); break;
-        case 4: k_edge_lift_mfma<4, true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2); break;
-        default: throw std::string("MFMA lift: degree out of range");
-      }
-      return;
-    }
-    switch (cfg.degree) {
-      case 3: k_edge_lift_mfma<3><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out); break;
-      case 4: k_edge_lift_mfma<4><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out); break;
-      default: throw std::string("MFMA lift: degree out of range");
-    }
+    by_mfma_degree([&](auto k) {
+      if (chd_) k_edge_lift_mfma<k(), true><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out, chd_, chx_, c1, c2);  // with the fused Chebyshev step
+      else k_edge_lift_mfma<k()><<<grid, 64 * HDG_LIFT_MFMA_WAVES, 0, stream>>>(gx, t0, t1, in, out);
+    });
   }
   void g_lift_apply(const double* Gt, const double* x, double* out) {
     tally(LC_LIFT, 2 * bQ() + 8.0 * (double)gm->nc * 2 * NU * 3 * NE);
-    HDG_DISPATCH(k_g_lift<KK><<<(gm->nc + 63) / 64, 64, 0, stream>>>(ggeo, g_nref, Gt, x, out));
+    by_degree([&](auto k) { k_g_lift<k()><<<(gm->nc + 63) / 64, 64, 0, stream>>>(ggeo, g_nref, Gt, x, out); });
   }
   void bdm(const double* in, double* out) {
-    if (general) {
+    const LiftForm form = lift_form();
+    if (form == LiftForm::general) {
       if (g_lift) g_lift_apply(g_lift, in, out);
       else csr(gd.Pi, in, 1.0, 0.0, out);
       return;
@@ -1246,18 +1049,18 @@ struct Engine {
     const Geo gx = g_ext(ext);
     fl.set(out, ext);
     tally(LC_LIFT, 2 * bQ());
-    if (use_mfma_lift()) {
-      if (!liftm_plain[0])
-        for (int sh = 0; sh < 2; sh++) liftm_plain[sh] = upload(pack_lift_mfma(sh, tab->Lift[sh]));
-      lift_mfma(gx, liftm_plain[0], liftm_plain[1], in, out);
-      return;
+    switch (form) {
+      case LiftForm::mfma:
+        if (!liftm_plain[0])
+          for (int sh = 0; sh < 2; sh++) liftm_plain[sh] = upload(pack_lift_mfma(*tab, sh, tab->Lift[sh]));
+        lift_mfma(gx, liftm_plain[0], liftm_plain[1], in, out);
+        break;
+      case LiftForm::pair:
+        by_pair_degree([&](auto k) { k_edge_lift_pair<k(), false, 0, false><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr); });
+        break;
+      default:
+        by_degree([&](auto k) { k_edge_lift<k(), false, 0, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr); });
     }
-    if (lift_pair()) {
-      if (K == 1) k_edge_lift_pair<1, false, 0, false><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr);
-      else k_edge_lift_pair<2, false, 0, false><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr);
-      return;
-    }
-    HDG_DISPATCH(k_edge_lift<KK, false, 0, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr));
   }
   // rows a lift with the optional Chebyshev epilogue may compute (chd_ = x_{n-1} -> x_{n+1}, chx_ = x_n)
   int lift_ext(const double* in, const double* r, const double* chd_, const double* chx_, double c1) {
@@ -1277,8 +1080,9 @@ struct Engine {
     const int ext = lift_ext(in, r, chd_, chx_, c1);
     const Geo gx = g_ext(ext);
     tally(LC_LIFT, lift_bytes(true, out != nullptr, chd_ != nullptr, c1));
-    if (chd_) { HDG_DISPATCH(k_edge_lift<KK, false, 1, true><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, r, D0, D1, chd_, chx_, c1, c2, nullptr)); }
-    else { HDG_DISPATCH(k_edge_lift<KK, false, 1, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, r, D0, D1, chd_, chx_, c1, c2, nullptr)); }
+    by_degree([&](auto k) { with_bool(chd_ != nullptr, [&](auto cheb) {
+      k_edge_lift<k(), false, 1, cheb()><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, r, D0, D1, chd_, chx_, c1, c2, nullptr);
+    }); });
     fl.set(out, ext); fl.set(chd_, ext);
   }
   // hybrid two-level preconditioner in ONE kernel: out = Pi(in) + Dinv (in - Pi(in)) = in + sum_e G_e d_e(in),
@@ -1292,23 +1096,22 @@ struct Engine {
     std::vector<const double*> pw;
     if (chd_) { pw.push_back(chx_); if (c1 != 0.0) pw.push_back(chd_); }
     int ext = 0;
+    const LiftForm form = lift_form();
     stencil_launch(in, FQ, GH, false, pw, [&](const Geo& gx) {
-      if (use_mfma_lift() && !ss && (out || chd_)) {
+      if (form == LiftForm::mfma && !ss && (out || chd_)) {
         // k >= 3: matrix-core kernel with the packed G tables of this stage (GMRES path: plain; Chebyshev path: fused step)
         for (size_t q = 0; q < hybg0.size(); q++)
           if (hybg0[q] == D0) { lift_mfma(gx, liftm_hyb0[q], liftm_hyb1[q], in, out, chd_, chx_, c1, c2); return; }
       }
-      if (lift_pair()) {  // k <= 2, 128-thread workgroups: both triangles of a square in one workgroup, moments through LDS
-        auto go = [&](auto kk) {
-          constexpr int KK = decltype(kk)::value;
-          if (chd_) k_edge_lift_pair<KK, false, 2, true><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss);
-          else k_edge_lift_pair<KK, false, 2, false><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss);
-        };
-        if (K == 1) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 2>{});
+      if (form == LiftForm::pair) {  // k <= 2, 128-thread workgroups: both triangles of a square in one workgroup, moments through LDS
+        by_pair_degree([&](auto k) { with_bool(chd_ != nullptr, [&](auto cheb) {
+          k_edge_lift_pair<k(), false, 2, cheb()><<<cell_grid_of(gx), 128, 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss);
+        }); });
         return;
       }
-      if (chd_) { HDG_DISPATCH(k_edge_lift<KK, false, 2, true><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss)); }
-      else { HDG_DISPATCH(k_edge_lift<KK, false, 2, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss)); }
+      by_degree([&](auto k) { with_bool(chd_ != nullptr, [&](auto cheb) {
+        k_edge_lift<k(), false, 2, cheb()><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, D0, D1, chd_, chx_, c1, c2, ss);
+      }); });
     }, &ext);
     fl.set(out, ext); fl.set(chd_, ext);
   }
@@ -1317,55 +1120,51 @@ struct Engine {
     const int ext = stencil_in(in, FQ);
     const Geo gx = g_ext(ext);
     tally(LC_LIFT, 2 * bQ());
-    HDG_DISPATCH(k_edge_lift<KK, true, 0, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr));
+    by_degree([&](auto k) { k_edge_lift<k(), true, 0, false><<<cell_grid_of(gx), bs(), 0, stream>>>(gx, dt, in, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr); });
     fl.set(out, ext);
   }
-  // k >= 3: the whole operator on the matrix cores (k_adv_mfma); HDG_NO_MFMA_ADV falls back to the per-thread kernels
-  bool use_mfma_adv() const { return opt.mfma_adv && cfg.degree >= MFMA_MIN_DEGREE && !periodic && !general; }
   void adv_apply(const double* x, const double* qstar, double* out, double gamma, const double* bsub = nullptr) {
     KTimed kt_(*this, bsub != nullptr ? T_KADV : T_KADV_PLAIN, fl.active());
     const double up = cfg.flux_upwind ? 1.0 : 0.0;
     tally(LC_ADV, bQ() * (bsub ? 4 : 3));
-    if (general) {
-      HDG_DISPATCH(k_g_adv<KK><<<(ggeo.nc + 63) / 64, 64, 0, stream>>>(ggeo, x, qstar, out, gamma, up, bsub));
+    const AdvForm form = adv_form();
+    if (form == AdvForm::general) {
+      by_degree([&](auto k) { k_g_adv<k()><<<(ggeo.nc + 63) / 64, 64, 0, stream>>>(ggeo, x, qstar, out, gamma, up, bsub); });
       fl.set(out, 0);
       return;
     }
-    const bool mfma = use_mfma_adv();
-    if (mfma && !advm[0]) {
+    if (form == AdvForm::mfma && !advm[0]) {
       if (dt.nqc != (cfg.degree == 3 ? 36 : 64)) throw std::string("cell quadrature size does not match the matrix-core advection kernel");
       if (dt.nqe != (3 * cfg.degree + 5) / 2) throw std::string("edge quadrature size does not match the matrix-core advection kernel");
-      for (int sh = 0; sh < 2; sh++) advm[sh] = upload(pack_adv_mfma(sh));
+      for (int sh = 0; sh < 2; sh++) advm[sh] = upload(pack_adv_mfma(*tab, sh));
     }
-    // without the matrix-core kernel: two lanes per cell, one velocity component each (k_adv_apply2), at the degrees of opt.adv_split_*
-    const bool two_lane = cfg.degree >= opt.adv_split_lo && cfg.degree <= opt.adv_split_hi;
     int ext = 0;
     // the launch of one row window (the whole extended strip, or interior / boundary rows around the exchange of x)
     stencil_launch(x, FQ, GH, false, {qstar, bsub}, [&](const Geo& g) {  // shadows the member on purpose
-      if (mfma) {
-        const dim3 gridc(8 * g.rows_xcd * 2);
-        auto launch = [&](auto kk, auto res) {
-          constexpr int KK = decltype(kk)::value;
-          constexpr bool RS = decltype(res)::value;
-          k_adv_mfma<KK, RS><<<gridc, 512, 0, stream>>>(g, dt, advm[0], advm[1], x, qstar, out, gamma, up, bsub);
-        };
-        auto by_form = [&](auto kk) { if (bsub) launch(kk, std::true_type{}); else launch(kk, std::false_type{}); };
-        if (cfg.degree == 3) by_form(std::integral_constant<int, 3>{});
-        else by_form(std::integral_constant<int, 4>{});
-      } else if (two_lane) {
-        const int cpb = bs() / 2, nbx2 = (g.nx + cpb - 1) / cpb;
-        HDG_DISPATCH(k_adv_apply2<KK><<<dim3(8 * g.rows_xcd * 2 * nbx2), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub));
-      } else if (bsub) {
-        HDG_DISPATCH(k_adv_apply<KK, true><<<cell_grid_of(g), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub));
-      } else {
-        HDG_DISPATCH(k_adv_apply<KK, false><<<cell_grid_of(g), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub));
+      switch (form) {
+        case AdvForm::mfma: {
+          const dim3 gridc(8 * g.rows_xcd * 2);
+          by_mfma_degree([&](auto k) { with_bool(bsub != nullptr, [&](auto resid) {
+            k_adv_mfma<k(), resid()><<<gridc, 512, 0, stream>>>(g, dt, advm[0], advm[1], x, qstar, out, gamma, up, bsub);
+          }); });
+          break;
+        }
+        case AdvForm::two_lane: {
+          const int cpb = bs() / 2, nbx2 = (g.nx + cpb - 1) / cpb;
+          by_degree([&](auto k) { k_adv_apply2<k()><<<dim3(8 * g.rows_xcd * 2 * nbx2), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub); });
+          break;
+        }
+        default:
+          by_degree([&](auto k) { with_bool(bsub != nullptr, [&](auto resid) {
+            k_adv_apply<k(), resid()><<<cell_grid_of(g), bs(), 0, stream>>>(g, dt, x, qstar, out, gamma, up, bsub);
+          }); });
       }
     }, &ext);
     fl.set(out, ext);
   }
   void blockdiag(const double* D0, const double* D1, const double* r, const double* zin, double cz, double* out) {
     tally(LC_LIFT, bQ() * (zin ? 3 : 2));
-    HDG_DISPATCH(k_blockdiag<KK><<<cell_grid(), bs(), 0, stream>>>(g, D0, D1, r, zin, cz, out));
+    by_degree([&](auto k) { k_blockdiag<k()><<<cell_grid(), bs(), 0, stream>>>(g, D0, D1, r, zin, cz, out); });
     fl.set(out, 0);
   }
   void pgrad(const double* a, double ca, const double* b, double cb, const double* p, const double* l, double gamma,
@@ -1379,14 +1178,11 @@ struct Engine {
     halo_L(l);
     tally(LC_RHS, bQ() * (1 + (a ? 1 : 0) + (b ? 1 : 0)) + bP() + bL());
     if (use_mfma_schur()) {
-      if (!pgm[0]) for (int sh = 0; sh < 2; sh++) pgm[sh] = upload(pack_pgrad_mfma(sh));
-      switch (K) {
-        case 3: k_pgrad_mfma<3><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); break;
-        default: k_pgrad_mfma<4><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); break;
-      }
+      if (!pgm[0]) for (int sh = 0; sh < 2; sh++) pgm[sh] = upload(pack_pgrad_mfma(*tab, sh));
+      by_mfma_degree([&](auto k) { k_pgrad_mfma<k()><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, pgm[0], pgm[1], a, ca, b, cb, p, l, gamma, out); });
       return;
     }
-    HDG_DISPATCH(k_pgrad<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, a, ca, b, cb, p, l, gamma, out));
+    by_degree([&](auto k) { k_pgrad<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, a, ca, b, cb, p, l, gamma, out); });
   }
   void weak_div(const double* q, double sc, double* out, bool broken) {
     if (general) { csr(broken ? gd.Bdiv : gd.Wdiv, q, sc, 0.0, out); return; }
@@ -1394,18 +1190,13 @@ struct Engine {
     tally(LC_WDIV, bQ() + bP());
     if (use_mfma_schur()) {
       const double** tb = broken ? wdbm : wdm;
-      if (!tb[0]) for (int sh = 0; sh < 2; sh++) tb[sh] = upload(pack_weakdiv_mfma(sh, broken));
-      auto launch = [&](auto kk) {
-        constexpr int KK = decltype(kk)::value;
-        if (broken) k_weak_div_mfma<KK, true><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, tb[0], tb[1], q, sc, out);
-        else k_weak_div_mfma<KK, false><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, tb[0], tb[1], q, sc, out);
-      };
-      if (K == 3) launch(std::integral_constant<int, 3>{});
-      else launch(std::integral_constant<int, 4>{});
+      if (!tb[0]) for (int sh = 0; sh < 2; sh++) tb[sh] = upload(pack_weakdiv_mfma(*tab, sh, broken));
+      by_mfma_degree([&](auto k) { with_bool(broken, [&](auto br) {
+        k_weak_div_mfma<k(), br()><<<schur_cell_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, tb[0], tb[1], q, sc, out);
+      }); });
       return;
     }
-    if (broken) { HDG_DISPATCH(k_weak_div<KK, true><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, sc, out)); }
-    else { HDG_DISPATCH(k_weak_div<KK, false><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, sc, out)); }
+    by_degree([&](auto k) { with_bool(broken, [&](auto br) { k_weak_div<k(), br()><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, sc, out); }); });
   }
   void trace_apply(const double* lam, const double* base, double cb, double ct, double* out, int max_ext = GH) {
     if (general) {
@@ -1418,7 +1209,7 @@ struct Engine {
     if (cb != 0.0) pw.push_back(base);
     int ext = 0;
     stencil_launch(lam, FL, max_ext, true, pw, [&](const Geo& c) {
-      HDG_DISPATCH(k_trace_apply<KK><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), lam, base, cb, ct, out));
+      by_degree([&](auto k) { k_trace_apply<k()><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), lam, base, cb, ct, out); });
     }, &ext);
     fl.set(out, ext);
   }
@@ -1442,9 +1233,9 @@ struct Engine {
     const int xa = mode == 2 ? 2 : (xadd ? 1 : 0);
     // mode 2: the vertex-grid correction is valid on the strip and 3 rows around it: results on at most 2 ghost rows
     stencil_launch(v, FL, mode == 2 ? 2 : GH, true, pw, [&](const Geo& c) {
-      if (mode == 1) { HDG_DISPATCH(k_trace_smooth<KK, 1><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), v, base, cb, ct, c1, c2, r_out, d_out, x, xa, xv, aux, xin)); }
-      else if (mode == 2) { HDG_DISPATCH(k_trace_smooth<KK, 2><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), v, base, cb, ct, c1, c2, r_out, d_out, x, xa, xv, aux, xin)); }
-      else { HDG_DISPATCH(k_trace_smooth<KK, 0><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), v, base, cb, ct, c1, c2, r_out, d_out, x, xa, xv, aux, xin)); }
+      by_degree([&](auto k) { with_int<0, 1, 2>(mode, "smoother mode", [&](auto md) {
+        k_trace_smooth<k(), md()><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), v, base, cb, ct, c1, c2, r_out, d_out, x, xa, xv, aux, xin);
+      }); });
     }, &ext);
     fl.set(r_out, ext); fl.set(d_out, ext); fl.set(x, ext);
   }
@@ -1459,7 +1250,7 @@ struct Engine {
     if (x && !assign) ext = pw_in(x, ext);
     const Geo c = g_ext(ext);
     tally(LC_TRACE_SMOOTH, bL() * (2 + (c1 != 0.0 ? 1 : 0) + (x ? (assign ? 1 : 2) : 0)));
-    HDG_DISPATCH(k_trace_cheb<KK><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), r, d, x, c1, c2, assign ? 1 : 0));
+    by_degree([&](auto k) { k_trace_cheb<k()><<<corner_grid_of(c), bs(), 0, stream>>>(c, pdt(), r, d, x, c1, c2, assign ? 1 : 0); });
     fl.set(d, ext); fl.set(x, ext);
   }
   // z (+)= prolongation of the (replicated, global) vertex vector: pointwise, on every row on which z is valid
@@ -1486,22 +1277,14 @@ struct Engine {
     if (opt.mfma_condense && use_mfma_schur() && (rw || rp)) {
       PSet& ps = psets[cur_pset];
       ensure_schur_tables(ps);
-      auto launch = [&](auto kk, auto hw, auto hp) {
-        constexpr int KK = decltype(kk)::value;
-        k_condense_mfma<KK, decltype(hw)::value, decltype(hp)::value><<<schur_corner_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, ps.cdm, rw, rp, rl, out);
-      };
-      auto by_form = [&](auto kk) {
-        if (rw && !rp) launch(kk, std::true_type{}, std::false_type{});
-        else if (!rw && rp) launch(kk, std::false_type{}, std::true_type{});
-        else launch(kk, std::true_type{}, std::true_type{});
-      };
-      if (K == 3) by_form(std::integral_constant<int, 3>{});
-      else by_form(std::integral_constant<int, 4>{});
+      by_mfma_degree([&](auto k) { by_rhs(rw, rp, [&](auto f) {
+        k_condense_mfma<k(), f() != RHS_P, f() != RHS_W><<<schur_corner_grid(), 64 * HDG_SCHUR_WAVES, 0, stream>>>(g, ps.cdm, rw, rp, rl, out);
+      }); });
       return;
     }
-    if (rw && !rp) { HDG_DISPATCH(k_condense<KK, true, false><<<corner_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, rl, out)); }
-    else if (!rw && rp) { HDG_DISPATCH(k_condense<KK, false, true><<<corner_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, rl, out)); }
-    else { HDG_DISPATCH(k_condense<KK, true, true><<<corner_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, rl, out)); }
+    by_degree([&](auto k) { by_rhs(rw, rp, [&](auto f) {
+      k_condense<k(), f() != RHS_P, f() != RHS_W><<<corner_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, rl, out);
+    }); });
   }
   void backsub(const double* rw, const double* rp, const double* lam, double* u, double* phi) {
     if (general) {
@@ -1516,22 +1299,14 @@ struct Engine {
     if (use_mfma_schur() && (rw || rp)) {
       PSet& ps = psets[cur_pset];
       ensure_schur_tables(ps);
-      auto launch = [&](auto kk, auto hw, auto hp) {
-        constexpr int KK = decltype(kk)::value;
-        k_backsub_mfma<KK, decltype(hw)::value, decltype(hp)::value><<<schur_cell_grid(), 64 * HDG_BACKSUB_WAVES, 0, stream>>>(g, ps.bsm[0], ps.bsm[1], rw, rp, lam, u, phi);
-      };
-      auto by_form = [&](auto kk) {
-        if (rw && !rp) launch(kk, std::true_type{}, std::false_type{});
-        else if (!rw && rp) launch(kk, std::false_type{}, std::true_type{});
-        else launch(kk, std::true_type{}, std::true_type{});
-      };
-      if (K == 3) by_form(std::integral_constant<int, 3>{});
-      else by_form(std::integral_constant<int, 4>{});
+      by_mfma_degree([&](auto k) { by_rhs(rw, rp, [&](auto f) {
+        k_backsub_mfma<k(), f() != RHS_P, f() != RHS_W><<<schur_cell_grid(), 64 * HDG_BACKSUB_WAVES, 0, stream>>>(g, ps.bsm[0], ps.bsm[1], rw, rp, lam, u, phi);
+      }); });
       return;
     }
-    if (rw && !rp) { HDG_DISPATCH(k_backsub<KK, true, false><<<cell_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, lam, u, phi)); }
-    else if (!rw && rp) { HDG_DISPATCH(k_backsub<KK, false, true><<<cell_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, lam, u, phi)); }
-    else { HDG_DISPATCH(k_backsub<KK, true, true><<<cell_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, lam, u, phi)); }
+    by_degree([&](auto k) { by_rhs(rw, rp, [&](auto f) {
+      k_backsub<k(), f() != RHS_P, f() != RHS_W><<<cell_grid(), bs(), 0, stream>>>(g, pdt(), rw, rp, lam, u, phi);
+    }); });
   }
   void gamma_psi(const double* u, const double* phi, const double* lam, double* out) {
     if (general) {
@@ -1544,7 +1319,7 @@ struct Engine {
     }
     if (lam) halo_L(lam);
     tally(LC_OTHER, (u ? bQ() : 0.0) + (phi ? bP() : 0.0) + (lam ? bL() : 0.0) + bP());
-    HDG_DISPATCH(k_gamma_psi<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, u, phi, lam, out));
+    by_degree([&](auto k) { k_gamma_psi<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, u, phi, lam, out); });
   }
   void gamma_mu(const double* u, const double* phi, const double* lam, double* out) {
     if (general) {
@@ -1558,19 +1333,19 @@ struct Engine {
     if (u) halo_Q(u);
     if (phi) halo_P(phi);
     tally(LC_OTHER, (u ? bQ() : 0.0) + (phi ? bP() : 0.0) + bL() * (lam ? 2 : 1));
-    HDG_DISPATCH(k_gamma_mu<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, u, phi, lam, out));
+    by_degree([&](auto k) { k_gamma_mu<k()><<<corner_grid(), bs(), 0, stream>>>(g, dt, u, phi, lam, out); });
   }
   void trace_recon(const double* Q, const double* p, double* out) {
     if (general) { csr(gd.Rq, Q, 1.0, 0.0, out); csr(gd.Rp, p, 1.0, 1.0, out); return; }
     halo_Q(Q);
     halo_P(p);
     tally(LC_OTHER, bQ() + bP() + bL());
-    HDG_DISPATCH(k_trace_recon<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, Q, p, out));
+    by_degree([&](auto k) { k_trace_recon<k()><<<corner_grid(), bs(), 0, stream>>>(g, dt, Q, p, out); });
   }
   void precon_rhs(const double* Q, const double* b, double bsc, double* rp, double* rl) {
     if (general) {
       tally(LC_RHS, 2 * bQ() + bP() + bL());
-      HDG_DISPATCH(k_g_precon<KK><<<(ggeo.nc + 63) / 64, 64, 0, stream>>>(ggeo, Q, b, bsc, rp));
+      by_degree([&](auto k) { k_g_precon<k()><<<(ggeo.nc + 63) / 64, 64, 0, stream>>>(ggeo, Q, b, bsc, rp); });
       csr(gd.Rb, b, bsc, 0.0, rl);
       return;
     }
@@ -1579,18 +1354,18 @@ struct Engine {
     HIPCHECK(hipMemsetAsync(rl, 0, sizeof(double) * NLv, stream));
     tally(LC_COPY, bL());
     tally(LC_RHS, 2 * bQ() + bP() + bL());
-    HDG_DISPATCH(k_precon_rhs<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, Q, b, bsc, rp, rl));
+    by_degree([&](auto k) { k_precon_rhs<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, Q, b, bsc, rp, rl); });
   }
-  void q_to_modal(const double* nodal, double* modal) { if (general) { csr(gd.Cq, nodal, 1.0, 0.0, modal); return; } HDG_DISPATCH(k_q_nodal_to_modal<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, nodal, modal)); }
-  void q_to_nodal(const double* modal, double* nodal) { if (general) { csr(gd.Cqi, modal, 1.0, 0.0, nodal); return; } HDG_DISPATCH(k_q_modal_to_nodal<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, modal, nodal)); }
-  void p_to_modal(const double* nodal, double* modal) { if (general) { csr(gd.Cp, nodal, 1.0, 0.0, modal); return; } HDG_DISPATCH(k_p_nodal_to_modal<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, nodal, modal)); }
-  void p_to_nodal(const double* modal, double* nodal) { if (general) { csr(gd.Cpi, modal, 1.0, 0.0, nodal); return; } HDG_DISPATCH(k_p_modal_to_nodal<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, modal, nodal)); }
+  void q_to_modal(const double* nodal, double* modal) { if (general) { csr(gd.Cq, nodal, 1.0, 0.0, modal); return; } by_degree([&](auto k) { k_q_nodal_to_modal<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, nodal, modal); }); }
+  void q_to_nodal(const double* modal, double* nodal) { if (general) { csr(gd.Cqi, modal, 1.0, 0.0, nodal); return; } by_degree([&](auto k) { k_q_modal_to_nodal<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, modal, nodal); }); }
+  void p_to_modal(const double* nodal, double* modal) { if (general) { csr(gd.Cp, nodal, 1.0, 0.0, modal); return; } by_degree([&](auto k) { k_p_nodal_to_modal<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, nodal, modal); }); }
+  void p_to_nodal(const double* modal, double* nodal) { if (general) { csr(gd.Cpi, modal, 1.0, 0.0, nodal); return; } by_degree([&](auto k) { k_p_modal_to_nodal<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, modal, nodal); }); }
   void l_to_modal(double* nodal, double* modal) {
     if (general) { csr(gd.Cl, nodal, 1.0, 0.0, modal); return; }
     HIPCHECK(hipMemsetAsync(modal, 0, sizeof(double) * NLv, stream));
-    HDG_DISPATCH(k_l_convert<KK, true><<<corner_grid_all(), bs(), 0, stream>>>(g_all, dt, nodal, modal));
+    by_degree([&](auto k) { k_l_convert<k(), true><<<corner_grid_all(), bs(), 0, stream>>>(g_all, dt, nodal, modal); });
   }
-  void l_to_nodal(double* modal, double* nodal) { if (general) { csr(gd.Cli, modal, 1.0, 0.0, nodal); return; } HDG_DISPATCH(k_l_convert<KK, false><<<corner_grid_all(), bs(), 0, stream>>>(g_all, dt, nodal, modal)); }
+  void l_to_nodal(double* modal, double* nodal) { if (general) { csr(gd.Cli, modal, 1.0, 0.0, nodal); return; } by_degree([&](auto k) { k_l_convert<k(), false><<<corner_grid_all(), bs(), 0, stream>>>(g_all, dt, nodal, modal); }); }
 
   // ------------------------------------------------------------------ vector helpers
   // (whole arrays, ghost rows included: a result is valid on the ghost rows all its inputs are valid on -- fl)
@@ -1683,10 +1458,7 @@ struct Engine {
       };
       // lean instantiations by output count: <= 4 (norms, CG of round 1, early Gram-Schmidt passes), <= 6 (single-reduction
       // CG: 4 vectors + 1 cross product), <= 12 (the rest of a GMRES(8) cycle); the 32-wide one only beyond that
-      if (nout <= 4) launch(std::integral_constant<int, 4>{});
-      else if (nout <= 6) launch(std::integral_constant<int, 6>{});
-      else if (nout <= 12) launch(std::integral_constant<int, 12>{});
-      else launch(std::integral_constant<int, MAXV>{});
+      with_int<4, 6, 12, MAXV>(nout <= 4 ? 4 : (nout <= 6 ? 6 : (nout <= 12 ? 12 : MAXV)), "multidot width", launch);
       // one rank: the reduction kernel writes the pinned host copy itself (no copy kernel on the stream)
       const bool direct = res && comm->size == 1 && direct_host();
       k_reduce_parts<<<nout, 256, 0, stream>>>(nb, nout, d_part, d_res, direct ? h_res : nullptr);
@@ -1742,42 +1514,6 @@ struct Engine {
                                                     std::sqrt(dt.elen[2]), std::sqrt(dt.elen[1]));
   }
 
-  // ------------------------------------------------------------------ stage residual coefficients
-  // r_i = sum cq[j] Q_j + sum cb[j] b_j   (mass matrix = identity in the orthonormal modal basis)
-  void residual_coeffs(int i, std::vector<double>& cq, std::vector<double>& cb) const {
-    cq.assign(s, 0.0); cb.assign(s, 0.0);
-    cq[0] = 1.0;
-    for (int j = 1; j < i; j++) {  // column 0 is never read (hdg_imex.py:377)
-      double aij = cfg.a_impl[i * s + j];
-      if (aij != 0.0) {
-        double f = aij / cfg.a_impl[j * s + j];
-        std::vector<double> q2, b2;
-        residual_coeffs(j, q2, b2);
-        cq[j] += f;
-        for (int l = 0; l < s; l++) { cq[l] -= f * q2[l]; cb[l] -= f * b2[l]; }
-      }
-    }
-    for (int j = 0; j < i; j++) {
-      double ae = cfg.a_expl[i * s + j];
-      if (ae != 0.0) cb[j] += cfg.dt * ae;
-    }
-  }
-  void final_residual_coeffs(std::vector<double>& cq, std::vector<double>& cb) const {
-    cq.assign(s, 0.0); cb.assign(s, 0.0);
-    cq[0] = 1.0;
-    for (int i = 1; i < s; i++) {
-      double bi = cfg.b_impl[i];
-      if (bi != 0.0) {
-        double f = bi / cfg.a_impl[i * s + i];
-        std::vector<double> q2, b2;
-        residual_coeffs(i, q2, b2);
-        cq[i] += f;
-        for (int l = 0; l < s; l++) { cq[l] -= f * q2[l]; cb[l] -= f * b2[l]; }
-      }
-    }
-    for (int i = 0; i < s; i++)
-      if (cfg.b_expl[i] != 0.0) cb[i] += cfg.dt * cfg.b_expl[i];
-  }
   const double* bvec(int slot) const { return bsep[slot] ? profile : brhs[slot]; }
   void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
     std::vector<std::pair<const double*, double>> terms;
@@ -1820,7 +1556,7 @@ struct Engine {
       for (int sh = 0; sh < 2; sh++) {
         dvec Ge[3];
         for (int e = 0; e < 3; e++) Ge[e].assign(G[sh].begin() + (size_t)e * n2 * ne, G[sh].begin() + (size_t)(e + 1) * n2 * ne);
-        std::vector<double> pk = pack_lift_mfma(sh, Ge);
+        std::vector<double> pk = pack_lift_mfma(*tab, sh, Ge);
         double*& dstp = sh == 0 ? liftm_hyb0[idx] : liftm_hyb1[idx];
         if (!dstp) dstp = dalloc((long)pk.size());
         HIPCHECK(hipMemcpyAsync(dstp, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, stream));
@@ -2016,54 +1752,6 @@ struct Engine {
     }
   }
 
-  // eigenvalues of a small upper Hessenberg matrix: shifted QR iteration in complex arithmetic with
-  // deflation (n <= 32, used for Ritz values only)
-  static std::vector<std::complex<double>> hessenberg_eig(const std::vector<double>& Hin, int n) {
-    typedef std::complex<double> cd;
-    std::vector<cd> H((size_t)n * n);
-    for (int i = 0; i < n * n; i++) H[i] = Hin[i];
-    std::vector<cd> ev;
-    int hi = n - 1;
-    int guard = 0;
-    while (hi >= 0 && guard++ < 10000) {
-      if (hi == 0) { ev.push_back(H[0]); break; }
-      // deflate
-      double sub = std::abs(H[(size_t)hi * n + hi - 1]);
-      double diag = std::abs(H[(size_t)hi * n + hi]) + std::abs(H[(size_t)(hi - 1) * n + hi - 1]);
-      if (sub <= 1e-14 * (diag > 0 ? diag : 1.0)) { ev.push_back(H[(size_t)hi * n + hi]); hi--; continue; }
-      // Wilkinson shift from the trailing 2x2 block
-      cd a = H[(size_t)(hi - 1) * n + hi - 1], b = H[(size_t)(hi - 1) * n + hi], c = H[(size_t)hi * n + hi - 1], d = H[(size_t)hi * n + hi];
-      cd tr = a + d, det = a * d - b * c, disc = std::sqrt(tr * tr - 4.0 * det);
-      cd l1 = 0.5 * (tr + disc), l2 = 0.5 * (tr - disc);
-      cd mu = (std::abs(l1 - d) < std::abs(l2 - d)) ? l1 : l2;
-      if (guard % 11 == 10) mu += cd(0.37 * sub, 0.11 * sub);  // exceptional shift
-      // QR step on the active block 0..hi by Givens rotations
-      std::vector<cd> cs_(hi), sn_(hi);
-      for (int i = 0; i <= hi; i++) H[(size_t)i * n + i] -= mu;
-      for (int k = 0; k < hi; k++) {
-        cd x = H[(size_t)k * n + k], y = H[(size_t)(k + 1) * n + k];
-        double r = std::sqrt(std::norm(x) + std::norm(y));
-        cd cc = (r == 0) ? cd(1) : x / r, ss = (r == 0) ? cd(0) : y / r;
-        cs_[k] = cc; sn_[k] = ss;
-        for (int col = k; col <= hi; col++) {
-          cd u = H[(size_t)k * n + col], v = H[(size_t)(k + 1) * n + col];
-          H[(size_t)k * n + col] = std::conj(cc) * u + std::conj(ss) * v;
-          H[(size_t)(k + 1) * n + col] = -ss * u + cc * v;
-        }
-      }
-      for (int k = 0; k < hi; k++) {
-        int rmax = std::min(hi, k + 1);
-        for (int row = 0; row <= rmax; row++) {
-          cd u = H[(size_t)row * n + k], v = H[(size_t)row * n + k + 1];
-          H[(size_t)row * n + k] = u * cs_[k] + v * sn_[k];
-          H[(size_t)row * n + k + 1] = -u * std::conj(sn_[k]) + v * std::conj(cs_[k]);
-        }
-      }
-      for (int i = 0; i <= hi; i++) H[(size_t)i * n + i] += mu;
-    }
-    return ev;
-  }
-
   // s-step minimal-residual cycles on the left-preconditioned operator B = M (I - gamma F(Q*)) (hdg_kernels.hpp: k_gram,
   // k_sstep_update): the tail of the Chebyshev iteration (round 3: one GMRES(8) cycle, whose Gram-Schmidt passes cost more
   // than its operator applications).  Power basis K_0 = M(b - A x), K_i = B K_{i-1}, i <= s (s <= 6: 28 inner products fit one
@@ -2079,45 +1767,6 @@ struct Engine {
   long n_sstep_cycles = 0, n_sstep_fallbacks = 0;
   bool arnoldi_only = false;  // set while a fall-back of the s-step cycles runs
   double *d_gram = nullptr, *h_gram = nullptr;
-  // least-squares coefficients of min |K_0 - sum_{i=1..sl} y_i K_i| from the Gram matrix G ((sl+1) x (sl+1), row-major):
-  // scaled normal equations, Cholesky in long double truncated at the first pivot below 1e-13; returns the rank and the
-  // predicted residual norm (from the Gram matrix: reliable down to reductions of ~1e-6 of |K_0|)
-  static int sstep_ls(const std::vector<long double>& G, int nv, int sl, std::vector<long double>& y, double& rho) {
-    std::vector<long double> d(sl), L((size_t)sl * sl, 0.0L), rhs(sl);
-    y.assign(sl, 0.0L);
-    for (int i = 0; i < sl; i++) d[i] = std::sqrt(std::max(G[(size_t)(i + 1) * nv + (i + 1)], (long double)1e-300));
-    int rank = 0;
-    for (int j = 0; j < sl; j++) {
-      long double piv = 1.0L;
-      for (int q = 0; q < j; q++) piv -= L[(size_t)j * sl + q] * L[(size_t)j * sl + q];
-      if (!(piv > 1e-13L)) break;
-      L[(size_t)j * sl + j] = std::sqrt(piv);
-      for (int i = j + 1; i < sl; i++) {
-        long double v = G[(size_t)(i + 1) * nv + (j + 1)] / (d[i] * d[j]);
-        for (int q = 0; q < j; q++) v -= L[(size_t)i * sl + q] * L[(size_t)j * sl + q];
-        L[(size_t)i * sl + j] = v / L[(size_t)j * sl + j];
-      }
-      rank = j + 1;
-    }
-    for (int i = 0; i < rank; i++) {  // forward, then backward substitution on the leading rank x rank block
-      long double v = G[(size_t)(i + 1) * nv] / d[i];
-      for (int q = 0; q < i; q++) v -= L[(size_t)i * sl + q] * rhs[q];
-      rhs[i] = v / L[(size_t)i * sl + i];
-    }
-    for (int i = rank - 1; i >= 0; i--) {
-      long double v = rhs[i];
-      for (int q = i + 1; q < rank; q++) v -= L[(size_t)q * sl + i] * y[q];
-      y[i] = v / L[(size_t)i * sl + i];
-    }
-    for (int i = 0; i < rank; i++) y[i] /= d[i];
-    long double r2 = G[0];
-    for (int i = 0; i < rank; i++) {
-      r2 -= 2.0L * y[i] * G[(size_t)(i + 1) * nv];
-      for (int q = 0; q < rank; q++) r2 += y[i] * y[q] * G[(size_t)(i + 1) * nv + (q + 1)];
-    }
-    rho = std::sqrt((double)std::max(r2, 0.0L));
-    return rank;
-  }
   int sstep_mr(const double* qstar, double gamma, int didx, const double* b, double* x, double rtol, double beta0, double cur0) {
     FlowScope flow_(*this);
     flow_fixed_Q(qstar);
@@ -2167,8 +1816,7 @@ struct Engine {
           if (big(NQ)) k_gram<NV, true><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, vl, nv, d_part, mk);
           else k_gram<NV, false><<<nb, HDG_DOT_BLOCK, 0, stream>>>(NQ, vl, nv, d_part, mk);
         };
-        if (nv <= 7) gram(std::integral_constant<int, 7>{});
-        else gram(std::integral_constant<int, HDG_SSTEP_MAXV>{});
+        with_int<7, HDG_SSTEP_MAXV>(nv <= 7 ? 7 : HDG_SSTEP_MAXV, "Gram matrix width", gram);
         k_reduce_parts<<<npair, 256, 0, stream>>>(nb, npair, d_part, d_gram, direct ? h_gram : nullptr);
         comm->allreduce_sum(d_gram, npair, stream);
         n_reduce++;
@@ -2438,7 +2086,7 @@ struct Engine {
     const double gamma = cfg.a_impl[i * s + i] * cfg.dt;
     ensure_dinv(i, gamma);
     std::vector<double> cq, cb;
-    residual_coeffs(i, cq, cb);
+    residual_coeffs(cfg, i, cq, cb);
     residual_vector(cq, cb, wQ3);                          // r_i
     adv_apply(stQ[i], Qstar[i - 1], wQ4, gamma);           // (I - gamma F) Q_i
     // rhs = r_i - (I - gamma F) Q_i + gamma g(w, p_i, lambda_i)      (hdg_imex.py:239-247)
@@ -2554,13 +2202,9 @@ struct Engine {
         const SideXP sj = xp_side_slice(lev, nt, extra);
         k_p1_up<NSW><<<dim3(nt, nt + extra), HDG_P1_THREADS, 0, stream>>>(n, mg_x[lev + 1], mg_b[lev], mg_r[lev], mg_x[lev], 0, extra, xp_period(nt, extra), sj);
       };
-      if (nsw == 1) down(std::integral_constant<int, 1>{});
-      else if (nsw == 2) down(std::integral_constant<int, 2>{});
-      else down(std::integral_constant<int, 3>{});
+      with_int<1, 2, 3>(nsw, "smoothing sweeps of a fused leg", down);
       vcycle(lev + 1);
-      if (nsw == 1) up(std::integral_constant<int, 1>{});
-      else if (nsw == 2) up(std::integral_constant<int, 2>{});
-      else up(std::integral_constant<int, 3>{});
+      with_int<1, 2, 3>(nsw, "smoothing sweeps of a fused leg", up);
       return;
     }
     zero(mg_x[lev], nv);
@@ -2874,12 +2518,7 @@ struct Engine {
           *dots_out = true;
         }
       };
-      switch (K) {
-        case 1: launch(std::integral_constant<int, 1>{}); break;
-        case 2: launch(std::integral_constant<int, 2>{}); break;
-        case 3: launch(std::integral_constant<int, 3>{}); break;
-        default: launch(std::integral_constant<int, 4>{}); break;
-      }
+      by_degree(launch);
       fl.set(z, 0); fl.set(w_out, 0);
       n_tile_precond++;
       return w_out != nullptr;
@@ -3392,7 +3031,7 @@ struct Engine {
     const int ps = get_pset(cfg.tau / gamma);
     if (!fg_b.u) fg_b = alloc3();
     std::vector<double> cq, cb;
-    residual_coeffs(i, cq, cb);
+    residual_coeffs(cfg, i, cq, cb);
     residual_vector(cq, cb, fg_b.u);
     zero(fg_b.p, NPv);
     zero(fg_b.l, NLv);
@@ -3427,7 +3066,7 @@ struct Engine {
       it_sum[1] += its; it_cnt[1]++;
     } else if (key == HDG_KEY_FINAL_STAGE) {
       std::vector<double> cq, cb;
-      final_residual_coeffs(cq, cb);
+      final_residual_coeffs(cfg, cq, cb);
       residual_vector(cq, cb, wQ3);                     // r^{n+1}  (hdg_imex.py:190-192)
       condense(wQ3, nullptr, nullptr, wL1);
       if (bwd_tol > 0.0) zero(curL, NLv);
@@ -3590,11 +3229,11 @@ struct Engine {
     if (general) {
       if (!g_nref) { csr(gd.Rp, p, 1.0, 0.0, lam); return; }  // HDG_GENERAL_CSR_LIFT: the assembled form of the same map
       dg_alloc();
-      HDG_DISPATCH(k_g_dg_avg_trace<KK><<<(gm->ne + 63) / 64, 64, 0, stream>>>(ggeo, gm->ne, dg_ecl, g_nref, p, lam));
+      by_degree([&](auto k) { k_g_dg_avg_trace<k()><<<(gm->ne + 63) / 64, 64, 0, stream>>>(ggeo, gm->ne, dg_ecl, g_nref, p, lam); });
       return;
     }
     halo_P(p);
-    HDG_DISPATCH(k_dg_avg_trace<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, p, lam));
+    by_degree([&](auto k) { k_dg_avg_trace<k()><<<corner_grid(), bs(), 0, stream>>>(g, dt, p, lam); });
   }
   void dg_apply(const V2& x, const double* qstar, double dtt, V2& out) {
     adv_apply(x.u, qstar, wQ1, dtt);
@@ -3781,15 +3420,15 @@ struct Engine {
       for (int n = 0; n < NU; n++)
         for (long cc = 0; cc < g.Nc; cc++) dg[(size_t)n * g.Nc + cc] = Ml[(size_t)n * NU + n];
       HIPCHECK(hipMemcpyAsync(cg_y, dg.data(), sizeof(double) * dg.size(), hipMemcpyHostToDevice, stream));
-      HDG_DISPATCH(k_cg_gather<KK><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_dinv));
+      by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_dinv); });
       HIPCHECK(hipStreamSynchronize(stream));
     }
   }
   void cg_mass(const double* c_in, double* out) {  // out = M_CG c_in
     if (general) { csr(gcgd.M, c_in, 1.0, 0.0, out); return; }
-    HDG_DISPATCH(k_cg_cell<KK, 0><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
-                                                                     nullptr, c_in, nullptr, 0, cg_y));
-    HDG_DISPATCH(k_cg_gather<KK><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, out));
+    by_degree([&](auto k) { k_cg_cell<k(), 0><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
+                                                                     nullptr, c_in, nullptr, 0, cg_y); });
+    by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, out); });
   }
   double dot_plain(long n, const double* a, const double* b) {
     VecList<4> vl{};
@@ -3882,32 +3521,32 @@ struct Engine {
     if (!opt.cg_mass_one_by_one) {  // both components in one solve
       if (!cg_b2) for (double** v : {&cg_b2, &cg_x2, &cg_pp2, &cg_Ap3}) *v = dalloc(cgt.ncg);
       for (int d = 0; d < 2; d++) {
-        HDG_DISPATCH(k_cg_cell<KK, 1><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
-                                                                         nullptr, nullptr, const_cast<double*>(vel_in), d, cg_y));
-        HDG_DISPATCH(k_cg_gather<KK><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, d == 0 ? cg_b : cg_b2));
+        by_degree([&](auto k) { k_cg_cell<k(), 1><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
+                                                                         nullptr, nullptr, const_cast<double*>(vel_in), d, cg_y); });
+        by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, d == 0 ? cg_b : cg_b2); });
       }
       cg_solve2(cg_b, cg_b2, cg_x, cg_x2);
       for (int d = 0; d < 2; d++)
-        HDG_DISPATCH(k_cg_cell<KK, 2><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
-                                                                         nullptr, d == 0 ? cg_x : cg_x2, vel_out, d, nullptr));
+        by_degree([&](auto k) { k_cg_cell<k(), 2><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
+                                                                         nullptr, d == 0 ? cg_x : cg_x2, vel_out, d, nullptr); });
       return;
     }
     for (int d = 0; d < 2; d++) {
-      HDG_DISPATCH(k_cg_cell<KK, 1><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
-                                                                       nullptr, nullptr, const_cast<double*>(vel_in), d, cg_y));
-      HDG_DISPATCH(k_cg_gather<KK><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_b));
+      by_degree([&](auto k) { k_cg_cell<k(), 1><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
+                                                                       nullptr, nullptr, const_cast<double*>(vel_in), d, cg_y); });
+      by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_b); });
       cg_solve();
-      HDG_DISPATCH(k_cg_cell<KK, 2><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
-                                                                       nullptr, cg_x, vel_out, d, nullptr));
+      by_degree([&](auto k) { k_cg_cell<k(), 2><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, nullptr, nullptr, nullptr, nullptr,
+                                                                       nullptr, cg_x, vel_out, d, nullptr); });
     }
   }
   // vorticity of a broken velocity in CG_{k+1} (callbacks.py:43-69); result in cg_x (ncg values)
   void vorticity(const double* vel_in) {
     cg_setup();
     if (general) { csr(gcgd.Vort, vel_in, 1.0, 0.0, cg_b); cg_solve(); return; }
-    HDG_DISPATCH(k_cg_cell<KK, 3><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, cg_Wx[0], cg_Wy[0], cg_Wx[1], cg_Wy[1],
-                                                                     cg_Eb, nullptr, const_cast<double*>(vel_in), 0, cg_y));
-    HDG_DISPATCH(k_cg_gather<KK><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_b));
+    by_degree([&](auto k) { k_cg_cell<k(), 3><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, cg_Wx[0], cg_Wy[0], cg_Wx[1], cg_Wy[1],
+                                                                     cg_Eb, nullptr, const_cast<double*>(vel_in), 0, cg_y); });
+    by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_b); });
     cg_solve();
   }
   void cg_coordinates(double* xy) const {  // physical position of every continuous dof
@@ -3950,9 +3589,9 @@ struct Engine {
   }
   // out = M^-1 T(.; q, u) for a continuous velocity u given as a broken modal vector
   void tracer_adv(const double* q, const double* u, double* out) {
-    if (general) { HDG_DISPATCH(k_g_tracer<KK><<<(gm->nc + 63) / 64, 64, 0, stream>>>(ggeo, q, u, out)); return; }
+    if (general) { by_degree([&](auto k) { k_g_tracer<k()><<<(gm->nc + 63) / 64, 64, 0, stream>>>(ggeo, q, u, out); }); return; }
     halo_P(q);
-    HDG_DISPATCH(k_tracer_adv<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, u, out));
+    by_degree([&](auto k) { k_tracer_adv<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, u, out); });
   }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
@@ -4034,14 +3673,14 @@ struct Engine {
     double* epart = diag_part + (long)diag_ncb * DIAG_NPART;
     tally(LC_OTHER, bQ() + bP() * (q ? 2.0 : 1.0));
     if (general) {
-      HDG_DISPATCH(k_g_diag_cell<KK><<<diag_ncb, DIAG_BLOCK, 0, stream>>>(ggeo, diag_gVu, diag_hmin, Q, p, q, Qn, cpart));
+      by_degree([&](auto k) { k_g_diag_cell<k()><<<diag_ncb, DIAG_BLOCK, 0, stream>>>(ggeo, diag_gVu, diag_hmin, Q, p, q, Qn, cpart); });
       tally(LC_OTHER, 2.0 * bQ());
-      HDG_DISPATCH(k_g_diag_edge<KK><<<diag_neb, DIAG_BLOCK, 0, stream>>>(ggeo, gm->ne, diag_ecl, Q, epart));
+      by_degree([&](auto k) { k_g_diag_edge<k()><<<diag_neb, DIAG_BLOCK, 0, stream>>>(ggeo, gm->ne, diag_ecl, Q, epart); });
     } else {
-      HDG_DISPATCH(k_diag_cell<KK><<<cell_grid(), bs(), 0, stream>>>(g, dt, Q, p, q, Qn, cpart));
+      by_degree([&](auto k) { k_diag_cell<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, Q, p, q, Qn, cpart); });
       halo_Q(Q);  // the edges of the strip's bottom row (and the periodic wrap) read the neighbour's cells
       tally(LC_OTHER, 3.0 * bQ());
-      HDG_DISPATCH(k_diag_edge<KK><<<corner_grid(), bs(), 0, stream>>>(g, dt, Q, epart));
+      by_degree([&](auto k) { k_diag_edge<k()><<<corner_grid(), bs(), 0, stream>>>(g, dt, Q, epart); });
     }
     tally(LC_OTHER, 0.0);
     k_diag_reduce<<<1, 1024, 0, stream>>>(diag_ncb, cpart, diag_neb, epart, diag_acc);
@@ -4138,9 +3777,9 @@ struct Engine {
     const int nb = (ps.n + POINT_BLOCK - 1) / POINT_BLOCK;
     tally(LC_OTHER, 0.0);
     if (general) {
-      HDG_DISPATCH(k_g_point_eval<KK><<<nb, POINT_BLOCK, 0, stream>>>(ggeo, ps.n, ps.dev, Q, p, q, row));
+      by_degree([&](auto k) { k_g_point_eval<k()><<<nb, POINT_BLOCK, 0, stream>>>(ggeo, ps.n, ps.dev, Q, p, q, row); });
     } else {
-      HDG_DISPATCH(k_point_eval<KK><<<nb, POINT_BLOCK, 0, stream>>>(ps.n, ps.dev, g.Nc, g.h, Q, p, q, row));
+      by_degree([&](auto k) { k_point_eval<k()><<<nb, POINT_BLOCK, 0, stream>>>(ps.n, ps.dev, g.Nc, g.h, Q, p, q, row); });
     }
     if (comm->size > 1) {  // every entry has one non-zero contributor: the sum is the owner's value on every rank
       const int total = POINT_NCOL * ps.n, chunk = comm->allreduce_max();  // the shared-memory transport: 64 per call
@@ -4682,8 +4321,8 @@ int hdg_get_solver_events(hdg_handle* h, long* events, int reset) {
 int hdg_get_kernel_forms(hdg_handle* h, int* forms) {
   HDG_API_BEGIN(h)
   if (!forms) throw std::string("forms is NULL");
-  forms[0] = E.general ? 3 : (E.use_mfma_lift() ? 2 : (E.lift_pair() ? 1 : 0));
-  forms[1] = E.general ? 3 : (E.use_mfma_adv() ? 2 : 0);
+  forms[0] = (int)E.lift_form();
+  forms[1] = hdg::Engine::form_code(E.adv_form());
   forms[2] = E.general ? 3 : (E.use_trace_tile() ? (E.tile3() ? 2 : 1) : 0);
   forms[3] = E.general ? 3 : (E.use_mfma_schur() ? 2 : 0);
   HDG_API_END(h)
@@ -4798,7 +4437,7 @@ int hdg_cg_to_broken(hdg_handle* h, const double* cg_values, double* broken) {
     throw hdg::HipError{"hipMemcpyAsync failed"};
   const int K = E.K;
   if (E.general) E.csr(E.gcgd.R, E.cg_b, 1.0, 0.0, E.hQ_dev);
-  else { HDG_DISPATCH(hdg::k_cg_to_broken<KK><<<E.cell_grid(), E.bs(), 0, E.stream>>>(E.g, E.cgt, E.cg_b, E.hQ_dev)); }
+  else { E.by_degree([&](auto k) { hdg::k_cg_to_broken<k()><<<E.cell_grid(), E.bs(), 0, E.stream>>>(E.g, E.cgt, E.cg_b, E.hQ_dev); }); }
   if (hipMemcpyAsync(broken, E.hQ_dev, sizeof(double) * E.NQb / 2, hipMemcpyDeviceToHost, E.stream) != hipSuccess)
     throw hdg::HipError{"hipMemcpyAsync failed"};
   HDG_API_END(h)

@@ -487,6 +487,59 @@ def test_options_table_defaults_kinds_and_implied_switches(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
 
 
+def _host_check(tmp_path, name):
+    """compile tests/host/<name>.cpp with g++ (warnings are errors) and run it: its output"""
+    import shutil
+    import subprocess
+
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / name
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", name + ".cpp")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-o", str(exe), src], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    return r.stdout
+
+
+def test_matrix_core_tables_index_maps_tile_rule_lengths_and_backsub_product(tmp_path):
+    """csrc/hdg_mfma_pack.hpp (plain C++, compiled here with g++), k = 3 and 4: scol / srow are injective, stay inside the padded
+    columns / rows and keep the two components of a basis function 4 slots apart inside one group of 8 (the 16-byte accesses
+    of hdg_schur_mfma.hpp); pack_tiles places entry l of tile (mt, ks) at M[16 mt + l % 16][4 ks + l / 16]; every packed table
+    has the length its kernel stages; the packed back-substitution table times a vector laid out by scol equals
+    Ainv r - W lambda of Tables::poissonBlock row by row to 1e-13 sum |a_i x_i| (at most 64 products summed in two orders
+    differ by 2 * 64 * 2^-53 = 1.4e-14 of that sum: a factor 7 is left)."""
+    out = _host_check(tmp_path, "pack_check")
+    assert out.count("back-substitution rows agree") == 4, out
+
+
+def test_small_dense_host_maths_and_the_kernel_dispatcher(tmp_path):
+    """csrc/hdg_small_dense.hpp and csrc/hdg_dispatch.hpp (plain C++, compiled here with g++): hessenberg_eig on the symmetric
+    tridiagonal Toeplitz matrix (n = 8, 16, 32) returns n values within 1e-11 (|a| + 2|b|) of a + 2 b cos(j pi / (n + 1)),
+    imaginary parts below the same bound (measured: 1.3e-15 / 3e-19); sstep_ls returns the exact coefficients and residual of
+    an orthogonal set to 1e-12 and rank 2 with the rank-2 residual when the last column is the sum of the first two
+    (measured: both exact in double); with_int / with_bool call the listed instantiation and throw outside the list."""
+    out = _host_check(tmp_path, "small_dense_check")
+    assert out.count("hessenberg_eig n =") == 6 and out.count("sstep_ls") == 2, out
+
+
+def test_new_host_headers_compile_alone(tmp_path):
+    """Each host-only header of csrc/ compiles on its own with g++ -Wall -Wextra -Werror: no HIP header behind it."""
+    import shutil
+    import subprocess
+
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    csrc = os.path.join(ROOT, "incompressibleeulerhdg_amd", "csrc")
+    for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp"):
+        assert "hip" not in open(os.path.join(csrc, h)).read().split("#pragma once")[1].split("namespace hdg")[0], h
+        tu = tmp_path / (h + ".cpp")
+        tu.write_text(f'#include "{h}"\n')
+        subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", csrc, "-c", str(tu), "-o", str(tmp_path / "tu.o")], check=True)
+
+
 def test_every_switch_is_read_in_one_place_and_every_switch_a_test_sets_exists():
     """The environment is read in csrc/hdg_options.hpp only (one table, one lifetime: when an engine is built), and every
     HDG_* variable a file under tests/ or tools/ puts into an environment is a name of that table (or one the Python loader
