@@ -341,6 +341,30 @@ int hdg_evaluate_points(hdg_handle* h, const double* Q, const double* p, const d
 int hdg_set_probes(hdg_handle* h, int n, const double* xy, int capacity);
 int hdg_get_probes(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset);
 
+/* ---- Lagrangian particles (no reference counterpart).  n positions X follow dX/dt = u(X, t), u the
+ * broken velocity of the current state (columns ux, uy of hdg_evaluate_points, with its ownership rule, applied on the
+ * device at every evaluation).  Heun's method over each completed step of the flow solver (the steps where hdg_set_probes
+ * takes its rows): k1 = u^n(X^n), X* = X^n + dt k1, k2 = u^{n+1}(X*), X^{n+1} = X^n + dt/2 (k1 + k2); k1 and X* are kept per
+ * particle across the step.  One launch per step on one rank; strip partitions: positions are replicated, a rank evaluates
+ * the particles in its own cell rows, two all-reduce sums of 2 n values per step, the same update on every rank (collective).
+ * Periodic square: positions are not wrapped (location wraps).  Unit square: every coordinate is clamped to [0, L] after
+ * each of the two position updates of a step; clamped updates are counted (the corrector's, and the predictor's that a
+ * corrector used).  A position that becomes non-finite stays NaN and
+ * is counted as lost.  General meshes: HDG_ERR_UNSUPPORTED.
+ * hdg_set_particles: seeds xy[2 n]; a device buffer of `capacity` rows of 2 n values (at most HDG_MAX_PROBE_VALUES in all,
+ *   else HDG_ERR_ARG); row 0 is the seeds, then every record_every-th step (record_every >= 1) appends the positions; the
+ *   particles move every step.  A seed outside the domain (unit square: more than 1e-12 L outside; any non-finite one)
+ *   returns HDG_ERR_ARG with its index and leaves the feature off.  n = 0 or capacity = 0 switches it off and frees the
+ *   buffers.  hdg_set_state (and hdg_set_field of the current velocity) re-evaluates k1 and X* of the particles.
+ * hdg_get_particles: copies min(*n_rows, max_rows) rows (2 n doubles each: x, y per particle) to `rows`, *n_rows = rows
+ *   recorded; counts[3] (may be NULL) = clamped updates and lost particles since hdg_set_particles, rows dropped beyond the
+ *   capacity; reset != 0 empties the row buffer.  Returns HDG_ERR_ARG (outputs still filled) when rows were dropped.
+ * hdg_advance_particles: nsteps Heun steps of size dt (any sign) through the current velocity held fixed (k2 from the same
+ *   field: streamlines of a snapshot), then appends one row, the positions reached.  The flow state is not touched. */
+int hdg_set_particles(hdg_handle* h, int n, const double* xy, int capacity, int record_every);
+int hdg_get_particles(hdg_handle* h, double* rows, int max_rows, int* n_rows, long* counts, int reset);
+int hdg_advance_particles(hdg_handle* h, double dt, int nsteps);
+
 /* kernel-level access for parity tests and micro-benchmarks (nodal in / nodal out) */
 int hdg_apply_advection(hdg_handle* h, const double* Qstar, const double* x, double gamma, double* y);
 int hdg_apply_trace_operator(hdg_handle* h, const double* lam, double* out);

@@ -167,6 +167,9 @@ SIGNATURES = {
     "hdg_evaluate_points": [_h, _dp, _dp, _dp, C.c_int, _dp, _dp, _ip],
     "hdg_set_probes": [_h, C.c_int, _dp, C.c_int],
     "hdg_get_probes": [_h, _dp, C.c_int, _ip, C.c_int],
+    "hdg_set_particles": [_h, C.c_int, _dp, C.c_int, C.c_int],
+    "hdg_get_particles": [_h, _dp, C.c_int, _ip, _lp, C.c_int],
+    "hdg_advance_particles": [_h, C.c_double, C.c_int],
 }
 
 
@@ -631,6 +634,36 @@ class Engine:
         self._ck(self.lib.hdg_get_probes(self.h, _ptr(rows) if n.value and npts else None, n.value if npts else 0,
                                          C.byref(n), 1 if reset else 0))
         return rows
+
+    # --- Lagrangian particles (include/hdg_mi355x.h: hdg_set_particles / hdg_get_particles / hdg_advance_particles)
+    def set_particles(self, xy, capacity, record_every=1):
+        """Advect the particles seeded at xy (n, 2) through the velocity of every completed step on the device (Heun) and
+        record their positions every `record_every`-th step into a device buffer of `capacity` rows (row 0: the seeds);
+        capacity 0 or no particles switches the feature off.  Raises HDGError (HDG_ERR_ARG) for a seed outside the domain,
+        (HDG_ERR_UNSUPPORTED) on a general mesh."""
+        xy = self._points(xy) if xy is not None else np.zeros((0, 2))
+        self._n_particles = 0
+        self._ck(self.lib.hdg_set_particles(self.h, len(xy), _ptr(xy), int(capacity), int(record_every)))
+        self._n_particles = len(xy) if capacity > 0 else 0
+
+    def particles(self, reset=True):
+        """(rows (rows, n, 2), counts): the recorded positions and {"clamped", "lost", "dropped"}.  Raises HDGError when
+        rows were dropped beyond the capacity."""
+        npts = getattr(self, "_n_particles", 0)
+        n = C.c_int(0)
+        rc = self.lib.hdg_get_particles(self.h, None, 0, C.byref(n), None, 0)  # the row count (dropped rows: the call below)
+        if rc not in (0, -1):
+            self._ck(rc)
+        rows = np.empty((n.value, npts, 2))
+        counts = np.zeros(3, dtype=np.int64)
+        self._ck(self.lib.hdg_get_particles(self.h, _ptr(rows) if n.value and npts else None, n.value if npts else 0,
+                                            C.byref(n), counts.ctypes.data_as(_lp), 1 if reset else 0))
+        return rows, {"clamped": int(counts[0]), "lost": int(counts[1]), "dropped": int(counts[2])}
+
+    def advance_particles(self, dt, nsteps):
+        """nsteps Heun steps of size dt through the current velocity held fixed (streamlines of a snapshot); appends one row,
+        the positions reached."""
+        self._ck(self.lib.hdg_advance_particles(self.h, float(dt), int(nsteps)))
 
     def time_kernel(self, kernel, reps):
         ms = C.c_double()

@@ -44,6 +44,7 @@
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
+#include "hdg_particles.hpp"
 
 namespace hdg {
 
@@ -3830,10 +3831,135 @@ struct Engine {
       HIPCHECK(hipMemcpyAsync(rows, pt_rows, sizeof(double) * POINT_NCOL * pt_probe.n * nrows, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
   }
-  // end of a completed step: the diagnostics row and the probe row of the same state
+
+  // ------------------------------------------------------------------ Lagrangian particles (hdg_particles.hpp)
+  // Positions X, predictor X*, k1 (and, on strips, the k2 of the sum) live on the device beside the probe state; one launch
+  // per completed step at end_of_step advances them (strips: three launches around two all-reduce sums of 2 n values,
+  // every rank holding all positions and doing the same update).  Switched off (pa_n == 0) a step issues no launch more.
+  int pa_n = 0, pa_cap = 0, pa_every = 1;
+  long pa_alloc = 0, pa_rows_alloc = 0, pa_nrows = 0, pa_dropped = 0, pa_steps = 0;
+  double *pa_X = nullptr, *pa_Xs = nullptr, *pa_k1 = nullptr, *pa_k2 = nullptr, *pa_rows = nullptr, *pa_cnt = nullptr;
+  void dfree(double*& p) {
+    if (!p) return;
+    auto it = std::find(allocs.begin(), allocs.end(), (void*)p);
+    if (it != allocs.end()) allocs.erase(it);
+    HIPCHECK(hipFree(p));
+    p = nullptr;
+  }
+  ParticleGeo particle_geo() const {
+    ParticleGeo G;
+    G.nx = g.nx; G.ny = cfg.ny; G.j0 = comm->rank * g.ny; G.nyl = g.ny; G.periodic = periodic ? 1 : 0;
+    G.R = g.R; G.Nc = g.Nc; G.L = Ldom; G.h = g.h;
+    return G;
+  }
+  void particles_launch(int phase, int nsteps, double dt, double* row) {
+    const int nb = (pa_n + PARTICLE_BLOCK - 1) / PARTICLE_BLOCK;
+    const ParticleGeo G = particle_geo();
+    unsigned long long* cnt = (unsigned long long*)pa_cnt;
+    tally(LC_OTHER, 0.0);
+    by_degree([&](auto k) {
+      k_particles_step<k()><<<nb, PARTICLE_BLOCK, 0, stream>>>(G, pa_n, phase, nsteps, dt, curQ, pa_X, pa_Xs, pa_k1, pa_k2, row, cnt);
+    });
+  }
+  // every entry has one non-zero contributor: the sum is the owner's value on every rank (as points_pass)
+  void particles_reduce(double* v) {
+    const int total = 2 * pa_n, chunk = comm->allreduce_max();
+    for (int off = 0; off < total; off += chunk) {
+      comm->allreduce_sum(v + off, std::min(chunk, total - off), stream);
+      n_reduce++;
+    }
+  }
+  // k1 = u(X) of the current velocity and X* = X + dt k1
+  void particles_predict(double dt) {
+    if (pa_n == 0) return;
+    if (comm->size == 1) { particles_launch(PF_EVAL_X | PF_PREDICT, 1, dt, nullptr); return; }
+    particles_launch(PF_EVAL_X, 1, dt, nullptr);
+    particles_reduce(pa_k1);
+    particles_launch(PF_PREDICT, 1, dt, nullptr);
+  }
+  // nsteps Heun steps of size dt through the current velocity (k1 and X* of the same dt are in place); row: where the last
+  // position goes (null: nowhere).  nsteps > 1: the field is frozen, k2 of a step and k1 of the next use the same one
+  void particles_advance(double dt, int nsteps, double* row) {
+    if (pa_n == 0 || nsteps <= 0) return;
+    if (comm->size == 1) { particles_launch(PF_STEP, nsteps, dt, row); return; }
+    for (int it = 0; it < nsteps; it++) {
+      particles_launch(PF_EVAL_STAR, 1, dt, nullptr);
+      particles_reduce(pa_k2);
+      particles_launch(PF_CORRECT | PF_EVAL_X, 1, dt, it == nsteps - 1 ? row : nullptr);
+      particles_reduce(pa_k1);
+      particles_launch(PF_PREDICT, 1, dt, nullptr);
+    }
+  }
+  double* particles_next_row() {
+    if (pa_nrows >= pa_cap) { pa_dropped++; return nullptr; }
+    return pa_rows + (pa_nrows++) * 2L * pa_n;
+  }
+  // end of a completed step: X^{n+1} from k1, X* and the new velocity; then k1 and X* of the next step
+  void particles_step() {
+    if (pa_n == 0) return;
+    pa_steps++;
+    particles_advance(cfg.dt, 1, pa_steps % pa_every == 0 ? particles_next_row() : nullptr);
+  }
+  void particles_off() {
+    pa_n = 0; pa_cap = 0; pa_nrows = 0; pa_dropped = 0; pa_steps = 0; pa_every = 1;
+    dfree(pa_X); dfree(pa_Xs); dfree(pa_k1); dfree(pa_k2); dfree(pa_rows); dfree(pa_cnt);
+    pa_alloc = 0; pa_rows_alloc = 0;
+  }
+  void particles_set(int n, const double* xy, int cap, int every) {
+    if (n < 0 || cap < 0) throw std::string("particles: n and capacity must be >= 0");
+    if (every < 1) throw std::string("particles: record_every must be >= 1");
+    particles_off();
+    if (n == 0 || cap == 0) return;
+    if (2.0 * n * cap > (double)HDG_MAX_PROBE_VALUES)
+      throw std::string("particles: ") + std::to_string(n) + " particles x " + std::to_string(cap) + " rows x 2 values exceed " +
+          "the limit of " + std::to_string((long)HDG_MAX_PROBE_VALUES) + " values";
+    for (int t = 0; t < n; t++) {
+      int i, j, sh;
+      double xi, eta;
+      if (!square_locate(xy[2 * (size_t)t], xy[2 * (size_t)t + 1], g.nx, cfg.ny, Ldom, periodic, i, j, sh, xi, eta))
+        throw std::string("particles: seed ") + std::to_string(t) + " (" + std::to_string(xy[2 * (size_t)t]) + ", " +
+            std::to_string(xy[2 * (size_t)t + 1]) + ") lies outside the domain";
+    }
+    pa_X = dalloc(2L * n); pa_Xs = dalloc(2L * n); pa_k1 = dalloc(2L * n);
+    if (comm->size > 1) pa_k2 = dalloc(2L * n);
+    pa_rows = dalloc(2L * n * cap);
+    pa_cnt = dalloc(PARTICLE_NCOUNT);  // two 64-bit counters, zeroed
+    pa_alloc = n; pa_rows_alloc = 2L * n * cap;
+    pa_n = n; pa_cap = cap; pa_every = every;
+    // seeds within the location tolerance of the unit square are clamped onto it like every later position
+    std::vector<double> seeds(xy, xy + 2 * (size_t)n);
+    if (!periodic)
+      for (double& v : seeds) v = std::fmin(std::fmax(v, 0.0), Ldom);
+    HIPCHECK(hipMemcpyAsync(pa_X, seeds.data(), sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipMemcpyAsync(particles_next_row(), seeds.data(), sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));  // seeds is a host temporary
+    particles_predict(cfg.dt);
+  }
+  // the velocity changed under the particles (hdg_set_state): a stale k1 is never used
+  void particles_refresh() { particles_predict(cfg.dt); }
+  void particles_frozen(double dt, int nsteps) {
+    if (pa_n == 0) throw std::string("particles: none set (hdg_set_particles)");
+    if (!std::isfinite(dt) || nsteps < 0) throw std::string("particles: dt must be finite and nsteps >= 0");
+    if (nsteps == 0) return;
+    particles_launch(PF_PREDICT, 1, dt, nullptr);  // X* of this dt from the k1 in place
+    particles_advance(dt, nsteps, particles_next_row());
+    particles_predict(cfg.dt);  // back to the predictor of the flow's own step
+  }
+  void particles_fetch(double* rows, long nrows, long* counts) {
+    unsigned long long c[PARTICLE_NCOUNT] = {0, 0};
+    if (pa_n > 0) {
+      if (nrows > 0)
+        HIPCHECK(hipMemcpyAsync(rows, pa_rows, sizeof(double) * 2 * (size_t)pa_n * nrows, hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipMemcpyAsync(c, pa_cnt, sizeof(c), hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (counts) { counts[0] = (long)c[0]; counts[1] = (long)c[1]; counts[2] = pa_dropped; }
+  }
+  // end of a completed step: the diagnostics row and the probe row of the same state, then the particles
   void end_of_step() {
     diag_record();
     probe_record();
+    particles_step();
   }
 
   // ------------------------------------------------------------------ host <-> device fields
@@ -4138,6 +4264,7 @@ int hdg_set_state(hdg_handle* h, const double* Q, const double* p) {
   E.put_Q(Q, E.curQ);
   E.put_P(p, E.curP);
   E.shift(E.curP, nullptr);  // p_0 -= mean (hdg_imex.py:522)
+  E.particles_refresh();
   HDG_API_END(h)
 }
 int hdg_get_field(hdg_handle* h, int which, double* Q, double* p, double* lam) {
@@ -4156,6 +4283,7 @@ int hdg_set_field(hdg_handle* h, int which, const double* Q, const double* p, co
   if (Q) { if (!dQ) throw std::string("field has no velocity part"); E.put_Q(Q, dQ); }
   if (p) { if (!dP) throw std::string("field has no pressure part"); E.put_P(p, dP); }
   if (lam) { if (!dL) throw std::string("field has no trace part"); E.put_L(lam, dL); }
+  if (Q && which == HDG_STATE_CURRENT) E.particles_refresh();
   HDG_API_END(h)
 }
 int hdg_set_forcing_nodal(hdg_handle* h, int slot, const double* f) {
@@ -4549,6 +4677,34 @@ int hdg_get_probes(hdg_handle* h, double* rows, int max_rows, int* n_rows, int r
   if (dropped > 0)
     throw std::string("probes: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
         std::to_string(E.pt_cap) + " rows";
+  HDG_API_END(h)
+}
+int hdg_set_particles(hdg_handle* h, int n, const double* xy, int capacity, int record_every) {
+  if (h && h->eng && h->eng->general) {
+    h->err = "general meshes: particles are not implemented (location on the device and leaving a polygonal boundary; "
+             "structured meshes only)";
+    return HDG_ERR_UNSUPPORTED;
+  }
+  HDG_API_BEGIN(h)
+  if (n > 0 && capacity > 0 && !xy) throw std::string("null argument");
+  E.particles_set(n, xy, capacity, record_every);
+  HDG_API_END(h)
+}
+int hdg_get_particles(hdg_handle* h, double* rows, int max_rows, int* n_rows, long* counts, int reset) {
+  HDG_API_BEGIN(h)
+  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
+  const long n = E.pa_nrows, dropped = E.pa_dropped;
+  E.particles_fetch(rows, std::min<long>(n, max_rows), counts);
+  if (n_rows) *n_rows = (int)n;
+  if (reset) { E.pa_nrows = 0; E.pa_dropped = 0; }
+  if (dropped > 0)
+    throw std::string("particles: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
+        std::to_string(E.pa_cap) + " rows";
+  HDG_API_END(h)
+}
+int hdg_advance_particles(hdg_handle* h, double dt, int nsteps) {
+  HDG_API_BEGIN(h)
+  E.particles_frozen(dt, nsteps);
   HDG_API_END(h)
 }
 int hdg_time_kernel(hdg_handle* h, int kernel, int reps, double* ms_per_launch) {

@@ -7,7 +7,7 @@
 //     carried as one homogeneous polynomial Q_i(A, B) of A = a (1 - s) / 2 = 2 xi + eta - 1 and B = (1 - s) / 2 = 1 - eta
 //     through the three-term recurrence of P_i, so values and gradients are polynomials in (xi, eta) with no division:
 //     finite and exact at the vertex, and at points a rounding error outside the triangle.
-//   * square_locate: the ownership rule on the structured square meshes (closed form).
+//   * square_locate: the ownership rule on the structured square meshes (closed form), on the host and on the device.
 #pragma once
 #include <cmath>
 
@@ -87,9 +87,13 @@ __host__ __device__ inline void dubiner_at(double xi, double eta, double* val, d
 // upper triangle s = 1).  Returns false for a point outside the unit square (more than POINT_TOL * L outside [0, L]^2); on
 // the periodic square every finite point is located after wrapping into [0, L).  Reference coordinates: the lower shape maps
 // x = (x_i, y_j) + h (xi, eta), the upper one x = (x_{i+1}, y_{j+1}) - h (xi, eta) (hdg_tables.hpp).  One operation per
-// statement: no contraction into fma, so that tests/probe_reference.py reproduces every rounding.
-inline bool square_locate(double x, double y, int nx, int ny, double L, bool periodic, int& i, int& j, int& s, double& xi,
-                          double& eta) {
+// statement: no contraction into fma (the pragma holds it on the device too, where the particle kernels of hdg_particles.hpp
+// locate every step), so that tests/probe_reference.py reproduces every rounding and host and device locate alike.
+__host__ __device__ inline bool square_locate(double x, double y, int nx, int ny, double L, bool periodic, int& i, int& j,
+                                              int& s, double& xi, double& eta) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const double h = L / nx;
   const double Lx = L, Ly = ny == nx ? L : ny * h;
   if (!(std::isfinite(x) && std::isfinite(y))) return false;

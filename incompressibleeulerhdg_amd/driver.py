@@ -9,6 +9,9 @@ driver.py:203-213); the ``conforming`` discretisation raises (SURVEY.md section 
 the CG vorticity, callbacks.py:30-85) and ``--tracer_advection`` (driver.py:340-344) work on every mesh.  The final fields are written to ``solution.pvd``
 (``--output``) like the reference does (driver.py:356-385).
 
+``--particles FILE`` advects Lagrangian particles through the two structured problems on the device
+and writes their positions to ``--particle_output`` (``particles.npz``).
+
 ``--gpus N`` (N > 1) runs the two structured problems on N strips (one process per rank, include/hdg_mi355x.h:
 hdg_create_distributed): the driver starts ``python -m torch.distributed.run --nproc-per-node=N`` with the same arguments
 as a child process and returns its exit status.  Each rank chooses RCCL when every rank has a device of its own and the
@@ -83,6 +86,13 @@ def build_parser():
                              "line, '#' starts a comment) after every step on the device")
     parser.add_argument("--probe_output", metavar="CSV", type=str, default="probes.csv",
                         help="CSV the --probes time series is written to")
+    parser.add_argument("--particles", metavar="FILE", type=str, default=None,
+                        help="advect Lagrangian particles seeded at the points of FILE (the format of --probes) through the "
+                             "velocity of every step on the device")
+    parser.add_argument("--particle_output", metavar="NPZ", type=str, default="particles.npz",
+                        help="file the --particles positions are written to (t, xy (rows, n, 2), clamped, lost)")
+    parser.add_argument("--particle_every", metavar="M", type=int, default=1,
+                        help="record the particle positions every M-th step (they move every step)")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -105,6 +115,16 @@ def check_multi_gpu(args):
     for bad, what in refused:
         if bad:
             raise RuntimeError(f"--gpus {args.gpus} does not support {what}")
+
+
+def check_particles(args):
+    """Refuse --particles where the engine does not advect them, before any process is started or any engine is built."""
+    if not args.particles:
+        return
+    if args.problem == "kelvinhelmholtz":
+        raise RuntimeError("--particles does not support --problem kelvinhelmholtz (particles run on the square meshes only)")
+    if args.particle_every < 1:
+        raise RuntimeError(f"--particle_every must be at least 1 (got {args.particle_every})")
 
 
 def launch_ranks(argv, nranks):
@@ -241,12 +261,23 @@ def write_probes(path, probes):
     print()
 
 
+def write_particles(path, particles):
+    """npz with t (rows,), xy (rows, n, 2) and the numbers of clamped updates and lost particles."""
+    with open(path, "wb") as f:  # np.savez would append .npz to a name without it
+        np.savez(f, t=particles["t"], xy=particles["xy"], clamped=particles["clamped"], lost=particles["lost"])
+    rows, n = particles["xy"].shape[:2]
+    print(f"particles ({rows} rows x {n} particles, {particles['clamped']} clamped updates, {particles['lost']} lost) "
+          f"written to {path}")
+    print()
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
     if args.discretisation == "conforming":
         raise RuntimeError(f"discretisation '{args.discretisation}' is out of scope of the MI355X hot path")
     check_multi_gpu(args)
+    check_particles(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
     ranks = _Ranks(args)
@@ -353,6 +384,14 @@ def _run(args, ranks):
             bad = int(np.flatnonzero(~located)[0])
             raise RuntimeError(f"{args.probes}:{lines[bad]}: probe point ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
         kw["probes"] = xy
+    if args.particles:
+        xy, lines = read_probe_points(args.particles)
+        _, located = eng.evaluate_points(xy)  # collective on strips; stops the run before the first step
+        if not np.all(located):
+            bad = int(np.flatnonzero(~located)[0])
+            raise RuntimeError(f"{args.particles}:{lines[bad]}: particle seed ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
+        kw["particles"] = xy
+        kw["particle_every"] = args.particle_every
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
     if args.diagnostics:
         report_solver_events(eng.solver_events())
@@ -360,6 +399,8 @@ def _run(args, ranks):
             write_diagnostics(args.diagnostics, timestepper.diagnostics)
     if args.probes and ranks.rank == 0:
         write_probes(args.probe_output, timestepper.probes)
+    if args.particles and ranks.rank == 0:
+        write_particles(args.particle_output, timestepper.particles)
     log_summary()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here

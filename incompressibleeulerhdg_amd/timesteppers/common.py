@@ -32,6 +32,7 @@ class IncompressibleEuler(ABC):
         self.domain_volume = float(mesh.volume) if getattr(mesh, "general", False) else float(getattr(mesh, "L", 1.0)) ** 2
         self.diagnostics = None  # solve(..., diagnostics=True): dict of the recorded series
         self.probes = None  # solve(..., probes=xy): dict of the recorded point values
+        self.particles = None  # solve(..., particles=xy): dict of the recorded particle positions
 
     # -- engine and function spaces ------------------------------------------------------------
     def _create_engine(self, **kw):
@@ -160,6 +161,30 @@ class IncompressibleEuler(ABC):
                        "u": rows[:, :, [c["ux"], c["uy"]]].copy(), "p": rows[:, :, c["p"]].copy(),
                        "q": rows[:, :, c["q"]].copy(), "omega": rows[:, :, c["omega"]].copy()}
 
+    # -- Lagrangian particles (include/hdg_mi355x.h: hdg_set_particles) -----------------------------
+    def _start_particles(self, particles, nt, every=1):
+        """Advect the particles seeded at (n, 2) positions through every step on the device and record nt // every + 1 rows:
+        the seeds (row 0) and the positions after every `every`-th step."""
+        self.particles = None
+        self._particle_every = int(every)
+        if particles is not None:
+            if self._particle_every < 1:
+                raise ValueError(f"particle_every must be at least 1 (got {every})")
+            self._engine.set_particles(np.asarray(particles, dtype=float).reshape(-1, 2), nt // self._particle_every + 1,
+                                       self._particle_every)
+
+    def _finish_particles(self, particles):
+        """Fetch the recorded rows once (self.particles: t, xy (rows, n, 2), clamped, lost) and switch the feature off."""
+        if particles is None:
+            return
+        try:
+            rows, counts = self._engine.particles(reset=True)
+        finally:
+            self._engine.set_particles(None, 0)
+        self.particles = {"t": np.arange(rows.shape[0]) * self._particle_every * self._dt, "xy": rows,
+                          "clamped": counts["clamped"], "lost": counts["lost"]}
+
     @abstractmethod
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
+              particles=None, particle_every=1):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""

@@ -30,8 +30,10 @@ class IncompressibleEulerDGImplicit(IncompressibleEuler):
         self._create_engine(flux=flux, use_projection_method=False, n_richardson=1, tau=self.tau, alpha_penalty=self.alpha,
                             nstages=1, a_expl=[[0]], a_impl=[[1]], b_expl=[1], b_impl=[1], c_expl=[0])
 
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None):
-        """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``: see IncompressibleEulerHDGIMEX.solve."""
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
+              particles=None, particle_every=1):
+        """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``, ``particles``: see
+        IncompressibleEulerHDGIMEX.solve."""
         eng = self._engine
         tracer = self._init_tracer(q_initial)  # dg_implicit.py:103-109
         nt = self.get_timesteps(T_final, warmup)
@@ -40,6 +42,7 @@ class IncompressibleEulerDGImplicit(IncompressibleEuler):
         profile = None
         self._start_diagnostics(diagnostics, nt)
         self._start_probes(probes, nt)
+        self._start_particles(particles, nt, particle_every)
         for callback in self.callbacks:
             callback.reset()
             Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
@@ -64,6 +67,7 @@ class IncompressibleEulerDGImplicit(IncompressibleEuler):
                     callback(Function(self._V_Q, Q), Function(self._V_p, p), (k + 1) * self._dt, q_tracer=qt)
         self._finish_diagnostics(diagnostics)
         self._finish_probes(probes)
+        self._finish_particles(particles)
         Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
         if tracer:
             self._tracer_function()

@@ -122,7 +122,8 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
             self._engine.set_forcing_nodal(slot, self._as_nodal_velocity(f_rhs(t)))
 
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
-    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None):
+    def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None,
+              particles=None, particle_every=1):
         """Propagate the solution to T_final with nt timesteps; returns (Q, p).
 
         ``fused=True`` runs each step as one device-resident ``hdg_step`` call instead of the
@@ -131,6 +132,9 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         stores them as ``self.diagnostics`` (dict of arrays: ``t`` and the names of ``_lib.DIAGNOSTICS``).
         ``probes=xy`` ((n, 2) points) records the point values of the initial state and of every step on the device and
         stores them as ``self.probes`` (dict: ``t``, ``xy``, ``u`` (nt+1, n, 2), ``p``, ``q``, ``omega`` (nt+1, n)).
+        ``particles=xy`` ((n, 2) seeds) advects Lagrangian particles through the velocity of every step on the device
+        (Heun's method) and stores ``self.particles`` (dict: ``t``, ``xy`` (rows, n, 2): the seeds and the positions after
+        every ``particle_every``-th step, ``clamped``, ``lost``).
         """
         eng = self._engine
         tracer = self._init_tracer(q_initial)  # hdg_imex.py:523-529
@@ -146,6 +150,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         eng.timers(reset=True)
         self._start_diagnostics(diagnostics, nt)
         self._start_probes(probes, nt)
+        self._start_particles(particles, nt, particle_every)
         for callback in self.callbacks:
             callback.reset()
             Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
@@ -194,6 +199,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
                     callback(Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p"), tn + self._dt, q_tracer=qt)
         self._finish_diagnostics(diagnostics)
         self._finish_probes(probes)
+        self._finish_particles(particles)
         if fused:
             # per-solve breakdown of the fused steps from the engine's device-side timers (same labels as the
             # host timers of the per-solve path; "timestep" is already timed on the host)
