@@ -583,16 +583,21 @@ class Engine:
         row); 0 switches recording off."""
         self._ck(self.lib.hdg_set_diagnostics(self.h, int(capacity)))
 
-    def diagnostics(self, reset=False):
-        """The recorded rows, (n, 9) in DIAGNOSTICS order.  Raises HDGError when rows were dropped beyond the capacity."""
+    def _fetch_rows(self, fn, shape_tail, reset, *extra):
+        """The rows of a per-step output, (n, *shape_tail): `fn` is its hdg_get_* entry, `extra` the pointers that takes
+        between the row count and the reset flag.  Two calls: the row count (extras null, no reset), then the rows."""
         n = C.c_int(0)
-        rc = self.lib.hdg_get_diagnostics(self.h, None, 0, C.byref(n), 0)  # the row count (dropped rows: the call below)
+        rc = fn(self.h, None, 0, C.byref(n), *(None for _ in extra), 0)  # dropped rows (-1): raised by the call below
         if rc not in (0, -1):
             self._ck(rc)
-        rows = np.empty((n.value, len(DIAGNOSTICS)))
-        self._ck(self.lib.hdg_get_diagnostics(self.h, _ptr(rows) if n.value else None, n.value, C.byref(n),
-                                              1 if reset else 0))
+        rows = np.empty((n.value, *shape_tail))
+        self._ck(fn(self.h, _ptr(rows) if rows.size else None, n.value if rows.size else 0, C.byref(n), *extra,
+                    1 if reset else 0))
         return rows
+
+    def diagnostics(self, reset=False):
+        """The recorded rows, (n, 9) in DIAGNOSTICS order.  Raises HDGError when rows were dropped beyond the capacity."""
+        return self._fetch_rows(self.lib.hdg_get_diagnostics, (len(DIAGNOSTICS),), reset)
 
     # --- point values (include/hdg_mi355x.h: hdg_evaluate_points / hdg_set_probes / hdg_get_probes)
     @staticmethod
@@ -625,15 +630,7 @@ class Engine:
 
     def probes(self, reset=True):
         """The recorded rows, (rows, n, 5) in POINT_COLUMNS order.  Raises HDGError when rows were dropped."""
-        npts = getattr(self, "_n_probes", 0)
-        n = C.c_int(0)
-        rc = self.lib.hdg_get_probes(self.h, None, 0, C.byref(n), 0)  # the row count (dropped rows: the call below)
-        if rc not in (0, -1):
-            self._ck(rc)
-        rows = np.empty((n.value, npts, len(POINT_COLUMNS)))
-        self._ck(self.lib.hdg_get_probes(self.h, _ptr(rows) if n.value and npts else None, n.value if npts else 0,
-                                         C.byref(n), 1 if reset else 0))
-        return rows
+        return self._fetch_rows(self.lib.hdg_get_probes, (getattr(self, "_n_probes", 0), len(POINT_COLUMNS)), reset)
 
     # --- Lagrangian particles (include/hdg_mi355x.h: hdg_set_particles / hdg_get_particles / hdg_advance_particles)
     def set_particles(self, xy, capacity, record_every=1):
@@ -649,15 +646,9 @@ class Engine:
     def particles(self, reset=True):
         """(rows (rows, n, 2), counts): the recorded positions and {"clamped", "lost", "dropped"}.  Raises HDGError when
         rows were dropped beyond the capacity."""
-        npts = getattr(self, "_n_particles", 0)
-        n = C.c_int(0)
-        rc = self.lib.hdg_get_particles(self.h, None, 0, C.byref(n), None, 0)  # the row count (dropped rows: the call below)
-        if rc not in (0, -1):
-            self._ck(rc)
-        rows = np.empty((n.value, npts, 2))
         counts = np.zeros(3, dtype=np.int64)
-        self._ck(self.lib.hdg_get_particles(self.h, _ptr(rows) if n.value and npts else None, n.value if npts else 0,
-                                            C.byref(n), counts.ctypes.data_as(_lp), 1 if reset else 0))
+        rows = self._fetch_rows(self.lib.hdg_get_particles, (getattr(self, "_n_particles", 0), 2), reset,
+                                counts.ctypes.data_as(_lp))
         return rows, {"clamped": int(counts[0]), "lost": int(counts[1]), "dropped": int(counts[2])}
 
     def advance_particles(self, dt, nsteps):

@@ -45,6 +45,7 @@
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
 #include "hdg_particles.hpp"
+#include "hdg_row_log.hpp"
 
 namespace hdg {
 
@@ -223,6 +224,13 @@ struct Engine {
     HIPCHECK(hipMemsetAsync(p, 0, sizeof(double) * (size_t)std::max<long>(n, 1), stream));
     allocs.push_back(p);
     return (double*)p;
+  }
+  void dfree(double*& p) {
+    if (!p) return;
+    auto it = std::find(allocs.begin(), allocs.end(), (void*)p);
+    if (it != allocs.end()) allocs.erase(it);
+    HIPCHECK(hipFree(p));
+    p = nullptr;
   }
   const double* upload(const dvec& v) {
     double* p = dalloc((long)v.size());
@@ -3625,16 +3633,65 @@ struct Engine {
     if (tracer_on) copy(q_cur, q_fin, NPv);
   }
 
+  // ------------------------------------------------------------------ per-step outputs (hdg_row_log.hpp)
+  // The three recorders below (diagnostics, probes, particles) each append one row per completed step to a device buffer on
+  // the stream, no host synchronisation; the RowLog counts rows and drops, the buffer follows its lifetime rule.  Switched
+  // off, no step issues a single launch more.
+  void log_size(RowLog& L, double*& buf, long width, long cap) {
+    L.reset(width, cap);
+    if (width * cap > L.alloc) { dfree(buf); L.alloc = 0; buf = dalloc(width * cap); L.alloc = width * cap; }
+  }
+  double* log_next(RowLog& L, double* buf) {
+    const long off = L.next();
+    return off == RowLog::DROPPED ? nullptr : buf + off;
+  }
+  void log_fetch(const RowLog& L, const double* buf, double* rows, long nrows) {
+    if (nrows > 0) HIPCHECK(hipMemcpyAsync(rows, buf, sizeof(double) * (size_t)(L.width * nrows), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  // what hdg_get_diagnostics / hdg_get_probes / hdg_get_particles do: the row count, the first min(n, max_rows) rows, the
+  // optional reset of the counts, and the error for rows dropped since the last reset
+  void log_get(const char* label, RowLog& L, const double* buf, double* rows, int max_rows, int* n_rows, int reset,
+               long* pa_counts = nullptr) {
+    if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
+    if (pa_counts) particles_counts(pa_counts);  // hdg_get_particles: the dropped-rows error below leaves them filled
+    const long n = L.n, dropped = L.dropped;
+    log_fetch(L, buf, rows, std::min<long>(n, max_rows));
+    if (n_rows) *n_rows = (int)n;
+    if (reset) L.clear_counts();
+    if (dropped > 0)
+      throw std::string(label) + ": " + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
+          std::to_string(L.cap) + " rows";
+  }
+  // every entry has one non-zero contributor: the sum is the owner's value on every rank
+  void allreduce_chunked(double* v, int total) {
+    const int chunk = comm->allreduce_max();  // the shared-memory transport: 64 per call
+    for (int off = 0; off < total; off += chunk) {
+      comm->allreduce_sum(v + off, std::min(chunk, total - off), stream);
+      n_reduce++;
+    }
+  }
+  // modal copies of nodal host fields (hdg_compute_diagnostics, hdg_evaluate_points): one set, allocated on first use
+  double *nodal_Qw = nullptr, *nodal_pw = nullptr, *nodal_qw = nullptr;
+  const double* stage_Q(const double* host) {
+    if (!host) return nullptr;
+    if (!nodal_Qw) nodal_Qw = dalloc(NQ);
+    put_Q(host, nodal_Qw);
+    return nodal_Qw;
+  }
+  const double* stage_P(const double* host, double*& w) {
+    if (!host) return nullptr;
+    if (!w) w = dalloc(NPv);
+    put_P(host, w);
+    return w;
+  }
+
   // ------------------------------------------------------------------ flow diagnostics (hdg_diagnostics.hpp)
-  // Recording (diag_cap > 0): every completed step appends one row to diag_rows on the stream, no host synchronisation;
-  // rows beyond the capacity are counted (diag_dropped) and reported when the rows are fetched.  Switched off, no step
-  // issues a single launch more.
+  RowLog diag_log;
   double *diag_part = nullptr, *diag_acc = nullptr, *diag_gat = nullptr, *diag_out = nullptr, *diag_rows = nullptr;
-  double *diag_Qw = nullptr, *diag_pw = nullptr, *diag_qw = nullptr;  // hdg_compute_diagnostics: modal copies of the inputs
   const double *diag_hmin = nullptr, *diag_gVu = nullptr;  // general meshes: shortest edge per cell, unscaled modal -> nodal
   const int* diag_ecl = nullptr;                            // general meshes: (3 c + l) of the cells of every edge
-  int diag_ncb = 0, diag_neb = 0, diag_cap = 0, diag_alloc_rows = 0;
-  long diag_n = 0, diag_dropped = 0;
+  int diag_ncb = 0, diag_neb = 0;
   void diag_alloc() {
     if (diag_part) return;
     if (general) {
@@ -3697,49 +3754,36 @@ struct Engine {
   }
   // end of a completed step: one row of the current state
   void diag_record() {
-    if (diag_cap <= 0) return;
-    if (diag_n >= diag_cap) { diag_dropped++; return; }
-    diag_pass(curQ, curP, tracer_on ? q_cur : nullptr, diag_rows + diag_n * DIAG_NCOL);
-    diag_n++;
+    if (double* row = log_next(diag_log, diag_rows)) diag_pass(curQ, curP, tracer_on ? q_cur : nullptr, row);
   }
   void diag_set(int cap) {
     if (cap < 0) throw std::string("diagnostics capacity must be >= 0");
-    diag_n = 0; diag_dropped = 0; diag_cap = cap;
-    if (cap == 0) return;
-    if (cap > diag_alloc_rows) { diag_rows = dalloc((long)cap * DIAG_NCOL); diag_alloc_rows = cap; }
+    log_size(diag_log, diag_rows, DIAG_NCOL, cap);
     diag_record();  // row 0: the state as it is now
-  }
-  void diag_fetch(double* rows, long nrows) {
-    if (nrows > 0) HIPCHECK(hipMemcpyAsync(rows, diag_rows, sizeof(double) * DIAG_NCOL * nrows, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
   }
   void diag_compute(const double* Q, const double* p, const double* q, double* out) {
     diag_alloc();  // before diag_out is read below
-    if (!diag_Qw) { diag_Qw = dalloc(NQ); diag_pw = dalloc(NPv); }
-    if (q) {
-      if (!diag_qw) diag_qw = dalloc(NPv);
-      put_P(q, diag_qw);
-    }
-    put_P(p, diag_pw);
-    put_Q(Q, diag_Qw);  // last: the staging buffer hQ_dev keeps the nodal velocity for the maxima
-    diag_pass(diag_Qw, diag_pw, q ? diag_qw : nullptr, diag_out, hQ_dev);
+    const double* qw = stage_P(q, nodal_qw);
+    const double* pw = stage_P(p, nodal_pw);
+    const double* Qw = stage_Q(Q);  // last: the staging buffer hQ_dev keeps the nodal velocity for the maxima
+    diag_pass(Qw, pw, qw, diag_out, hQ_dev);
     HIPCHECK(hipMemcpyAsync(out, diag_out, sizeof(double) * DIAG_NCOL, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
   }
 
   // ------------------------------------------------------------------ point values (hdg_points.hpp, hdg_probes.hpp)
   // A point set is located on the host once (every rank locates every point, the same way) into a device table; one launch
-  // per row evaluates it (strip partitions: one all-reduce sum of the row).  Probe recording (pt_cap > 0) appends one row per
-  // completed step at end_of_step, next to the diagnostics row; switched off, a step issues no launch more.
+  // per row evaluates it (strip partitions: one all-reduce sum of the row).  Probe recording appends one row per completed
+  // step at end_of_step, next to the diagnostics row.
   struct PointSet {
     int n = 0, alloc = 0;
     PointLoc* dev = nullptr;
   };
   PointSet pt_eval, pt_probe;
   GLocator* glocator = nullptr;
-  double *pt_out = nullptr, *pt_rows = nullptr, *pt_Qw = nullptr, *pt_pw = nullptr, *pt_qw = nullptr;
-  long pt_out_alloc = 0, pt_rows_alloc = 0, pt_n = 0, pt_dropped = 0;
-  int pt_cap = 0;
+  RowLog probe_log;
+  double *pt_out = nullptr, *pt_rows = nullptr;
+  long pt_out_alloc = 0;
   // located[i] = 1 / 0; throws nothing for an outside point (PT_OUTSIDE)
   void points_locate(int n, const double* xy, PointSet& ps, int* located) {
     if (n < 0 || (n > 0 && !xy)) throw std::string("points: bad arguments");
@@ -3782,33 +3826,24 @@ struct Engine {
     } else {
       by_degree([&](auto k) { k_point_eval<k()><<<nb, POINT_BLOCK, 0, stream>>>(ps.n, ps.dev, g.Nc, g.h, Q, p, q, row); });
     }
-    if (comm->size > 1) {  // every entry has one non-zero contributor: the sum is the owner's value on every rank
-      const int total = POINT_NCOL * ps.n, chunk = comm->allreduce_max();  // the shared-memory transport: 64 per call
-      for (int off = 0; off < total; off += chunk) {
-        comm->allreduce_sum(row + off, std::min(chunk, total - off), stream);
-        n_reduce++;
-      }
-    }
+    if (comm->size > 1) allreduce_chunked(row, POINT_NCOL * ps.n);
   }
   void points_evaluate(const double* Q, const double* p, const double* q, int n, const double* xy, double* out, int* located) {
     points_locate(n, xy, pt_eval, located);
     if ((long)n * POINT_NCOL > pt_out_alloc) { pt_out = dalloc((long)n * POINT_NCOL); pt_out_alloc = (long)n * POINT_NCOL; }
-    if (Q) { if (!pt_Qw) pt_Qw = dalloc(NQ); put_Q(Q, pt_Qw); }
-    if (p) { if (!pt_pw) pt_pw = dalloc(NPv); put_P(p, pt_pw); }
-    if (q) { if (!pt_qw) pt_qw = dalloc(NPv); put_P(q, pt_qw); }
-    points_pass(pt_eval, Q ? pt_Qw : nullptr, p ? pt_pw : nullptr, q ? pt_qw : nullptr, pt_out);
+    const double* Qw = stage_Q(Q);
+    const double* pw = stage_P(p, nodal_pw);
+    const double* qw = stage_P(q, nodal_qw);
+    points_pass(pt_eval, Qw, pw, qw, pt_out);
     if (n > 0) HIPCHECK(hipMemcpyAsync(out, pt_out, sizeof(double) * POINT_NCOL * (size_t)n, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
   }
   void probe_record() {
-    if (pt_cap <= 0) return;
-    if (pt_n >= pt_cap) { pt_dropped++; return; }
-    points_pass(pt_probe, curQ, curP, tracer_on ? q_cur : nullptr, pt_rows + pt_n * POINT_NCOL * pt_probe.n);
-    pt_n++;
+    if (double* row = log_next(probe_log, pt_rows)) points_pass(pt_probe, curQ, curP, tracer_on ? q_cur : nullptr, row);
   }
   void probe_set(int n, const double* xy, int cap) {
     if (n < 0 || cap < 0) throw std::string("probes: n and capacity must be >= 0");
-    pt_cap = 0; pt_n = 0; pt_dropped = 0;
+    probe_log.reset(0, 0);
     if (n == 0 || cap == 0) { pt_probe.n = 0; return; }
     if ((double)n * cap * POINT_NCOL > (double)HDG_MAX_PROBE_VALUES)
       throw std::string("probes: ") + std::to_string(n) + " points x " + std::to_string(cap) + " rows x " +
@@ -3821,31 +3856,19 @@ struct Engine {
         throw std::string("probes: point ") + std::to_string(t) + " (" + std::to_string(xy[2 * (size_t)t]) + ", " +
             std::to_string(xy[2 * (size_t)t + 1]) + ") lies outside the domain";
       }
-    const long need = (long)n * cap * POINT_NCOL;
-    if (need > pt_rows_alloc) { pt_rows = dalloc(need); pt_rows_alloc = need; }
-    pt_cap = cap;
+    log_size(probe_log, pt_rows, (long)POINT_NCOL * n, cap);
     probe_record();  // row 0: the state as it is now
-  }
-  void probe_fetch(double* rows, long nrows) {
-    if (nrows > 0)
-      HIPCHECK(hipMemcpyAsync(rows, pt_rows, sizeof(double) * POINT_NCOL * pt_probe.n * nrows, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
   }
 
   // ------------------------------------------------------------------ Lagrangian particles (hdg_particles.hpp)
   // Positions X, predictor X*, k1 (and, on strips, the k2 of the sum) live on the device beside the probe state; one launch
   // per completed step at end_of_step advances them (strips: three launches around two all-reduce sums of 2 n values,
-  // every rank holding all positions and doing the same update).  Switched off (pa_n == 0) a step issues no launch more.
-  int pa_n = 0, pa_cap = 0, pa_every = 1;
-  long pa_alloc = 0, pa_rows_alloc = 0, pa_nrows = 0, pa_dropped = 0, pa_steps = 0;
+  // every rank holding all positions and doing the same update).  Switched off: pa_n == 0, and the work vectors X, X*,
+  // k1, k2 and the counters are freed (the row buffer follows the rule of hdg_row_log.hpp).
+  RowLog pa_log;
+  int pa_n = 0, pa_every = 1;
+  long pa_steps = 0;
   double *pa_X = nullptr, *pa_Xs = nullptr, *pa_k1 = nullptr, *pa_k2 = nullptr, *pa_rows = nullptr, *pa_cnt = nullptr;
-  void dfree(double*& p) {
-    if (!p) return;
-    auto it = std::find(allocs.begin(), allocs.end(), (void*)p);
-    if (it != allocs.end()) allocs.erase(it);
-    HIPCHECK(hipFree(p));
-    p = nullptr;
-  }
   ParticleGeo particle_geo() const {
     ParticleGeo G;
     G.nx = g.nx; G.ny = cfg.ny; G.j0 = comm->rank * g.ny; G.nyl = g.ny; G.periodic = periodic ? 1 : 0;
@@ -3861,20 +3884,12 @@ struct Engine {
       k_particles_step<k()><<<nb, PARTICLE_BLOCK, 0, stream>>>(G, pa_n, phase, nsteps, dt, curQ, pa_X, pa_Xs, pa_k1, pa_k2, row, cnt);
     });
   }
-  // every entry has one non-zero contributor: the sum is the owner's value on every rank (as points_pass)
-  void particles_reduce(double* v) {
-    const int total = 2 * pa_n, chunk = comm->allreduce_max();
-    for (int off = 0; off < total; off += chunk) {
-      comm->allreduce_sum(v + off, std::min(chunk, total - off), stream);
-      n_reduce++;
-    }
-  }
   // k1 = u(X) of the current velocity and X* = X + dt k1
   void particles_predict(double dt) {
     if (pa_n == 0) return;
     if (comm->size == 1) { particles_launch(PF_EVAL_X | PF_PREDICT, 1, dt, nullptr); return; }
     particles_launch(PF_EVAL_X, 1, dt, nullptr);
-    particles_reduce(pa_k1);
+    allreduce_chunked(pa_k1, 2 * pa_n);
     particles_launch(PF_PREDICT, 1, dt, nullptr);
   }
   // nsteps Heun steps of size dt through the current velocity (k1 and X* of the same dt are in place); row: where the last
@@ -3884,16 +3899,13 @@ struct Engine {
     if (comm->size == 1) { particles_launch(PF_STEP, nsteps, dt, row); return; }
     for (int it = 0; it < nsteps; it++) {
       particles_launch(PF_EVAL_STAR, 1, dt, nullptr);
-      particles_reduce(pa_k2);
+      allreduce_chunked(pa_k2, 2 * pa_n);
       particles_launch(PF_CORRECT | PF_EVAL_X, 1, dt, it == nsteps - 1 ? row : nullptr);
-      particles_reduce(pa_k1);
+      allreduce_chunked(pa_k1, 2 * pa_n);
       particles_launch(PF_PREDICT, 1, dt, nullptr);
     }
   }
-  double* particles_next_row() {
-    if (pa_nrows >= pa_cap) { pa_dropped++; return nullptr; }
-    return pa_rows + (pa_nrows++) * 2L * pa_n;
-  }
+  double* particles_next_row() { return log_next(pa_log, pa_rows); }
   // end of a completed step: X^{n+1} from k1, X* and the new velocity; then k1 and X* of the next step
   void particles_step() {
     if (pa_n == 0) return;
@@ -3901,9 +3913,9 @@ struct Engine {
     particles_advance(cfg.dt, 1, pa_steps % pa_every == 0 ? particles_next_row() : nullptr);
   }
   void particles_off() {
-    pa_n = 0; pa_cap = 0; pa_nrows = 0; pa_dropped = 0; pa_steps = 0; pa_every = 1;
-    dfree(pa_X); dfree(pa_Xs); dfree(pa_k1); dfree(pa_k2); dfree(pa_rows); dfree(pa_cnt);
-    pa_alloc = 0; pa_rows_alloc = 0;
+    pa_n = 0; pa_steps = 0; pa_every = 1;
+    pa_log.reset(0, 0);
+    dfree(pa_X); dfree(pa_Xs); dfree(pa_k1); dfree(pa_k2); dfree(pa_cnt);
   }
   void particles_set(int n, const double* xy, int cap, int every) {
     if (n < 0 || cap < 0) throw std::string("particles: n and capacity must be >= 0");
@@ -3922,10 +3934,9 @@ struct Engine {
     }
     pa_X = dalloc(2L * n); pa_Xs = dalloc(2L * n); pa_k1 = dalloc(2L * n);
     if (comm->size > 1) pa_k2 = dalloc(2L * n);
-    pa_rows = dalloc(2L * n * cap);
+    log_size(pa_log, pa_rows, 2L * n, cap);
     pa_cnt = dalloc(PARTICLE_NCOUNT);  // two 64-bit counters, zeroed
-    pa_alloc = n; pa_rows_alloc = 2L * n * cap;
-    pa_n = n; pa_cap = cap; pa_every = every;
+    pa_n = n; pa_every = every;
     // seeds within the location tolerance of the unit square are clamped onto it like every later position
     std::vector<double> seeds(xy, xy + 2 * (size_t)n);
     if (!periodic)
@@ -3945,15 +3956,12 @@ struct Engine {
     particles_advance(dt, nsteps, particles_next_row());
     particles_predict(cfg.dt);  // back to the predictor of the flow's own step
   }
-  void particles_fetch(double* rows, long nrows, long* counts) {
+  // clamped updates, lost particles, dropped rows
+  void particles_counts(long* counts) {
     unsigned long long c[PARTICLE_NCOUNT] = {0, 0};
-    if (pa_n > 0) {
-      if (nrows > 0)
-        HIPCHECK(hipMemcpyAsync(rows, pa_rows, sizeof(double) * 2 * (size_t)pa_n * nrows, hipMemcpyDeviceToHost, stream));
-      HIPCHECK(hipMemcpyAsync(c, pa_cnt, sizeof(c), hipMemcpyDeviceToHost, stream));
-    }
+    if (pa_n > 0) HIPCHECK(hipMemcpyAsync(c, pa_cnt, sizeof(c), hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
-    if (counts) { counts[0] = (long)c[0]; counts[1] = (long)c[1]; counts[2] = pa_dropped; }
+    counts[0] = (long)c[0]; counts[1] = (long)c[1]; counts[2] = pa_log.dropped;
   }
   // end of a completed step: the diagnostics row and the probe row of the same state, then the particles
   void end_of_step() {
@@ -4642,15 +4650,7 @@ int hdg_set_diagnostics(hdg_handle* h, int capacity) {
 }
 int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset) {
   HDG_API_BEGIN(h)
-  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
-  const long n = E.diag_n, dropped = E.diag_dropped;
-  const long ncopy = std::min<long>(n, max_rows);
-  E.diag_fetch(rows, ncopy);
-  if (n_rows) *n_rows = (int)n;
-  if (reset) { E.diag_n = 0; E.diag_dropped = 0; }
-  if (dropped > 0)
-    throw std::string("diagnostics: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
-        std::to_string(E.diag_cap) + " rows";
+  E.log_get("diagnostics", E.diag_log, E.diag_rows, rows, max_rows, n_rows, reset);
   HDG_API_END(h)
 }
 int hdg_evaluate_points(hdg_handle* h, const double* Q, const double* p, const double* q, int n, const double* xy, double* out,
@@ -4668,15 +4668,7 @@ int hdg_set_probes(hdg_handle* h, int n, const double* xy, int capacity) {
 }
 int hdg_get_probes(hdg_handle* h, double* rows, int max_rows, int* n_rows, int reset) {
   HDG_API_BEGIN(h)
-  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
-  const long n = E.pt_n, dropped = E.pt_dropped;
-  const long ncopy = std::min<long>(n, max_rows);
-  E.probe_fetch(rows, ncopy);
-  if (n_rows) *n_rows = (int)n;
-  if (reset) { E.pt_n = 0; E.pt_dropped = 0; }
-  if (dropped > 0)
-    throw std::string("probes: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
-        std::to_string(E.pt_cap) + " rows";
+  E.log_get("probes", E.probe_log, E.pt_rows, rows, max_rows, n_rows, reset);
   HDG_API_END(h)
 }
 int hdg_set_particles(hdg_handle* h, int n, const double* xy, int capacity, int record_every) {
@@ -4692,14 +4684,7 @@ int hdg_set_particles(hdg_handle* h, int n, const double* xy, int capacity, int 
 }
 int hdg_get_particles(hdg_handle* h, double* rows, int max_rows, int* n_rows, long* counts, int reset) {
   HDG_API_BEGIN(h)
-  if (max_rows < 0 || (max_rows > 0 && !rows)) throw std::string("bad arguments");
-  const long n = E.pa_nrows, dropped = E.pa_dropped;
-  E.particles_fetch(rows, std::min<long>(n, max_rows), counts);
-  if (n_rows) *n_rows = (int)n;
-  if (reset) { E.pa_nrows = 0; E.pa_dropped = 0; }
-  if (dropped > 0)
-    throw std::string("particles: ") + std::to_string(dropped) + " row(s) dropped beyond the capacity of " +
-        std::to_string(E.pa_cap) + " rows";
+  E.log_get("particles", E.pa_log, E.pa_rows, rows, max_rows, n_rows, reset, counts);
   HDG_API_END(h)
 }
 int hdg_advance_particles(hdg_handle* h, double dt, int nsteps) {

@@ -247,6 +247,17 @@ def read_probe_points(path):
     return np.array(pts, dtype=float), lines
 
 
+def read_points_inside(path, eng, noun):
+    """The points of a --probes / --particles file, every one inside the mesh: the first that is not stops the run, before
+    its first step, with file:line and what the point is (`noun`)."""
+    xy, lines = read_probe_points(path)
+    _, located = eng.evaluate_points(xy)  # collective on strips
+    if not np.all(located):
+        bad = int(np.flatnonzero(~located)[0])
+        raise RuntimeError(f"{path}:{lines[bad]}: {noun} ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
+    return xy
+
+
 def write_probes(path, probes):
     """CSV with one row per recorded state and point: step, t, point, x, y and the five point values."""
     t, xy = probes["t"], probes["xy"]
@@ -378,19 +389,9 @@ def _run(args, ranks):
     if args.diagnostics:
         kw["diagnostics"] = True
     if args.probes:
-        xy, lines = read_probe_points(args.probes)
-        _, located = eng.evaluate_points(xy)  # collective on strips; stops the run before the first step
-        if not np.all(located):
-            bad = int(np.flatnonzero(~located)[0])
-            raise RuntimeError(f"{args.probes}:{lines[bad]}: probe point ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
-        kw["probes"] = xy
+        kw["probes"] = read_points_inside(args.probes, eng, "probe point")
     if args.particles:
-        xy, lines = read_probe_points(args.particles)
-        _, located = eng.evaluate_points(xy)  # collective on strips; stops the run before the first step
-        if not np.all(located):
-            bad = int(np.flatnonzero(~located)[0])
-            raise RuntimeError(f"{args.particles}:{lines[bad]}: particle seed ({xy[bad, 0]}, {xy[bad, 1]}) lies outside the mesh")
-        kw["particles"] = xy
+        kw["particles"] = read_points_inside(args.particles, eng, "particle seed")
         kw["particle_every"] = args.particle_every
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
     if args.diagnostics:

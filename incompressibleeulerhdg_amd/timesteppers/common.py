@@ -7,7 +7,8 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from .._lib import DIAGNOSTICS, POINT_COLUMNS, Engine
+from .._lib import DIAGNOSTICS, HDG_STATE_CURRENT, POINT_COLUMNS, Engine
+from ..auxilliary.logging import PerformanceLog
 from ..mesh import Function, FunctionSpace
 
 __all__ = ["IncompressibleEuler"]
@@ -115,24 +116,6 @@ class IncompressibleEuler(ABC):
         vals = self._engine.compute_diagnostics(self._as_nodal_velocity(Q), self._as_nodal_pressure(p), qn)
         return {name: float(v) for name, v in zip(DIAGNOSTICS, vals)}
 
-    def _start_diagnostics(self, on, nt):
-        """Record nt + 1 rows on the device: the current state (row 0) and the state after every step."""
-        self.diagnostics = None
-        if on:
-            self._engine.set_diagnostics(nt + 1)
-
-    def _finish_diagnostics(self, on):
-        """Fetch the recorded rows once (self.diagnostics: t and the nine series) and switch recording off."""
-        if not on:
-            return
-        try:
-            rows = self._engine.diagnostics(reset=True)
-        finally:
-            self._engine.set_diagnostics(0)
-        self.diagnostics = {"t": np.arange(rows.shape[0]) * self._dt}
-        for i, name in enumerate(DIAGNOSTICS):
-            self.diagnostics[name] = rows[:, i].copy()
-
     # -- point values (include/hdg_mi355x.h: hdg_evaluate_points / hdg_set_probes; DESIGN.md section 13) ------------------
     def evaluate_points(self, xy, Q=None, p=None, q=None):
         """Values of the given fields (what _as_nodal_* accepts, None: NaN) at the points xy (n, 2), computed on the device:
@@ -141,50 +124,145 @@ class IncompressibleEuler(ABC):
                                             None if p is None else self._as_nodal_pressure(p),
                                             None if q is None else self._as_nodal_pressure(q))
 
-    def _start_probes(self, probes, nt):
-        """Record nt + 1 rows of point values on the device: the current state (row 0) and the state after every step."""
-        self.probes = None
-        if probes is not None:
-            self._engine.set_probes(np.asarray(probes, dtype=float).reshape(-1, 2), nt + 1)
+    # -- forcing -------------------------------------------------------------------------------
+    def _set_forcing(self, slot, f_rhs, t):
+        if f_rhs is None or (isinstance(f_rhs, (int, float)) and f_rhs == 0):
+            self._engine.set_forcing_scale(slot, 0.0)
+        elif hasattr(f_rhs, "profile") and hasattr(f_rhs, "scale"):
+            if self._forcing_profile is not f_rhs.profile:
+                self._engine.set_forcing_profile(f_rhs.profile)
+                self._forcing_profile = f_rhs.profile
+            self._engine.set_forcing_scale(slot, f_rhs.scale(t))
+        else:
+            self._engine.set_forcing_nodal(slot, self._as_nodal_velocity(f_rhs(t)))
 
-    def _finish_probes(self, probes):
-        """Fetch the recorded rows once (self.probes: t, xy, u (nt+1, n, 2), p, q, omega (nt+1, n)) and switch recording
-        off."""
-        if probes is None:
-            return
-        try:
-            rows = self._engine.probes(reset=True)
-        finally:
-            self._engine.set_probes(None, 0)
-        c = {name: i for i, name in enumerate(POINT_COLUMNS)}
-        self.probes = {"t": np.arange(rows.shape[0]) * self._dt, "xy": np.asarray(probes, dtype=float).reshape(-1, 2).copy(),
-                       "u": rows[:, :, [c["ux"], c["uy"]]].copy(), "p": rows[:, :, c["p"]].copy(),
-                       "q": rows[:, :, c["q"]].copy(), "omega": rows[:, :, c["omega"]].copy()}
+    # -- time loop (hdg_imex.py:505-660, hdg_implicit.py:52-197, dg_implicit.py:84-136) -------------------------------
+    _callback_names = (None, None)  # names of the velocity and pressure Functions handed to callbacks
+    _result_names = ("velocity", "pressure")  # ... and of those solve() returns
 
-    # -- Lagrangian particles (include/hdg_mi355x.h: hdg_set_particles; DESIGN.md section 15) -----------------------------
-    def _start_particles(self, particles, nt, every=1):
-        """Advect the particles seeded at (n, 2) positions through every step on the device and record nt // every + 1 rows:
-        the seeds (row 0) and the positions after every `every`-th step."""
-        self.particles = None
-        self._particle_every = int(every)
-        if particles is not None:
-            if self._particle_every < 1:
-                raise ValueError(f"particle_every must be at least 1 (got {every})")
-            self._engine.set_particles(np.asarray(particles, dtype=float).reshape(-1, 2), nt // self._particle_every + 1,
-                                       self._particle_every)
+    def _begin_solve(self):
+        """After the state is set, before the recorders start."""
 
-    def _finish_particles(self, particles):
-        """Fetch the recorded rows once (self.particles: t, xy (rows, n, 2), clamped, lost) and switch the feature off."""
-        if particles is None:
-            return
-        try:
-            rows, counts = self._engine.particles(reset=True)
-        finally:
-            self._engine.set_particles(None, 0)
-        self.particles = {"t": np.arange(rows.shape[0]) * self._particle_every * self._dt, "xy": rows,
-                          "clamped": counts["clamped"], "lost": counts["lost"]}
+    def _advance(self, k, f_rhs, tracer):
+        """Step k (forcing included); returns the time reached, which the callbacks are given."""
+        raise NotImplementedError
+
+    def _end_solve(self):
+        """After the recorders have finished, before the final fields are fetched."""
+
+    def _current(self):
+        """The current nodal velocity and pressure"""
+        return self._engine.get_field(HDG_STATE_CURRENT, lam=False)[:2]
+
+    def _functions(self, Q, p, names):
+        return Function(self._V_Q, Q, names[0]), Function(self._V_p, p, names[1])
+
+    def _solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, **requests):
+        """The time loop of every stepper; ``requests``: the per-step outputs asked for, by the names of RECORDERS (each
+        class there says what counts as asked for) and ``particle_every``.  Each one asked for leaves its dict in the attribute of its name."""
+        eng = self._engine
+        tracer = self._init_tracer(q_initial)
+        nt = self.get_timesteps(T_final, warmup)
+        self._forcing_profile = None
+        eng.set_state(self._as_nodal_velocity(Q_initial), self._as_nodal_pressure(p_initial))
+        self._begin_solve()
+        recorders = []
+        for name, make in RECORDERS:
+            setattr(self, name, None)
+            if make.requested(requests[name]):
+                recorders.append((name, make(requests[name], self._dt, requests["particle_every"])))
+                recorders[-1][1].start(eng, nt)
+        for callback in self.callbacks:
+            callback.reset()
+            callback(*self._functions(*self._current(), self._callback_names), 0, q_tracer=self.q_tracer)
+        for k in range(nt):
+            with PerformanceLog("timestep"):
+                t = self._advance(k, f_rhs, tracer)
+            if self.callbacks:
+                Q, p = self._current()
+                qt = self._tracer_function() if tracer else None
+                for callback in self.callbacks:
+                    callback(*self._functions(Q, p, self._callback_names), t, q_tracer=qt)
+        for name, rec in recorders:
+            setattr(self, name, rec.finish(eng))
+        self._end_solve()
+        Q, p = self._current()
+        if tracer:
+            self._tracer_function()  # the final tracer field: self.q_tracer (the reference returns (Q, p) only)
+        return self._functions(Q, p, self._result_names)
 
     @abstractmethod
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
               particles=None, particle_every=1):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""
+
+
+# -- per-step outputs: each is switched on for a run of nt steps (row 0: the state as it is, then one row per step) and, when
+# the run is over, fetched once into a dict and switched off.  The rows live in the engine's row logs (DESIGN.md section 12).
+class _Diagnostics:
+    requested = staticmethod(bool)  # solve(..., diagnostics=True)
+
+    def __init__(self, on, dt, every):
+        self.dt = dt
+
+    def start(self, eng, nt):
+        eng.set_diagnostics(nt + 1)
+
+    def finish(self, eng):
+        """t and the nine series"""
+        try:
+            rows = eng.diagnostics(reset=True)
+        finally:
+            eng.set_diagnostics(0)
+        out = {"t": np.arange(rows.shape[0]) * self.dt}
+        out.update((name, rows[:, i].copy()) for i, name in enumerate(DIAGNOSTICS))
+        return out
+
+
+class _Probes:
+    @staticmethod
+    def requested(xy):  # solve(..., probes=xy): an empty point set is one too
+        return xy is not None
+
+    def __init__(self, xy, dt, every):
+        self.xy, self.dt = np.asarray(xy, dtype=float).reshape(-1, 2), dt
+
+    def start(self, eng, nt):
+        eng.set_probes(self.xy, nt + 1)
+
+    def finish(self, eng):
+        """t, xy, u (nt+1, n, 2), p, q, omega (nt+1, n)"""
+        try:
+            rows = eng.probes(reset=True)
+        finally:
+            eng.set_probes(None, 0)
+        c = {name: i for i, name in enumerate(POINT_COLUMNS)}
+        return {"t": np.arange(rows.shape[0]) * self.dt, "xy": self.xy.copy(),
+                "u": rows[:, :, [c["ux"], c["uy"]]].copy(), "p": rows[:, :, c["p"]].copy(),
+                "q": rows[:, :, c["q"]].copy(), "omega": rows[:, :, c["omega"]].copy()}
+
+
+class _Particles:
+    """Seeds (n, 2) advected through every step on the device; nt // every + 1 rows: the seeds and the positions after every
+    `every`-th step."""
+    requested = staticmethod(_Probes.requested)
+
+    def __init__(self, xy, dt, every):
+        self.xy, self.dt, self.every = np.asarray(xy, dtype=float).reshape(-1, 2), dt, int(every)
+        if self.every < 1:
+            raise ValueError(f"particle_every must be at least 1 (got {every})")
+
+    def start(self, eng, nt):
+        eng.set_particles(self.xy, nt // self.every + 1, self.every)
+
+    def finish(self, eng):
+        """t, xy (rows, n, 2), clamped, lost"""
+        try:
+            rows, counts = eng.particles(reset=True)
+        finally:
+            eng.set_particles(None, 0)
+        return {"t": np.arange(rows.shape[0]) * self.every * self.dt, "xy": rows,
+                "clamped": counts["clamped"], "lost": counts["lost"]}
+
+
+RECORDERS = (("diagnostics", _Diagnostics), ("probes", _Probes), ("particles", _Particles))

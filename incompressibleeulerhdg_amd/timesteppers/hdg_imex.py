@@ -11,7 +11,6 @@ import numpy as np
 from .. import _lib
 from ..auxilliary.logging import PerformanceLog
 from ..auxilliary.utils import Averager
-from ..mesh import Function
 from .common import IncompressibleEuler
 
 __all__ = [
@@ -109,18 +108,6 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         """hdg_imex.py:471-478; `which` selects _update / _stage_state[i] / _current_state."""
         self._engine.shift_pressure(which)
 
-    # -- forcing -------------------------------------------------------------------------------
-    def _set_forcing(self, slot, f_rhs, t):
-        if f_rhs is None or (isinstance(f_rhs, (int, float)) and f_rhs == 0):  # SURVEY.md C-6
-            self._engine.set_forcing_scale(slot, 0.0)
-        elif hasattr(f_rhs, "profile") and hasattr(f_rhs, "scale"):
-            if self._forcing_profile is not f_rhs.profile:
-                self._engine.set_forcing_profile(f_rhs.profile)
-                self._forcing_profile = f_rhs.profile
-            self._engine.set_forcing_scale(slot, f_rhs.scale(t))
-        else:
-            self._engine.set_forcing_nodal(slot, self._as_nodal_velocity(f_rhs(t)))
-
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None,
               particles=None, particle_every=1):
@@ -136,79 +123,70 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         (Heun's method) and stores ``self.particles`` (dict: ``t``, ``xy`` (rows, n, 2): the seeds and the positions after
         every ``particle_every``-th step, ``clamped``, ``lost``).
         """
-        eng = self._engine
-        tracer = self._init_tracer(q_initial)  # hdg_imex.py:523-529
-        s = self.nstages
-        nt = self.get_timesteps(T_final, warmup)
-        self._forcing_profile = None
-        eng.set_state(self._as_nodal_velocity(Q_initial), self._as_nodal_pressure(p_initial))
+        self._fused = fused
+        return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
+                           particles=particles, particle_every=particle_every)
+
+    _callback_names = _result_names = ("Q", "p")
+
+    def _averagers(self):
+        return self.niter_tentative, self.niter_pressure, self.niter_final_pressure, self.niter_pressure_reconstruction
+
+    def _begin_solve(self):
         self._reconstruct_trace()
-        for a in (self.niter_tentative, self.niter_pressure, self.niter_final_pressure,
-                  self.niter_pressure_reconstruction):
+        for a in self._averagers():
             a.reset()
-        eng.iteration_stats(reset=True)
-        eng.timers(reset=True)
-        self._start_diagnostics(diagnostics, nt)
-        self._start_probes(probes, nt)
-        self._start_particles(particles, nt, particle_every)
-        for callback in self.callbacks:
-            callback.reset()
-            Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
-            callback(Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p"), 0, q_tracer=self.q_tracer)
-        for k in range(nt):
-            with PerformanceLog("timestep"):
-                tn = k * self._dt
-                for i in range(s):
-                    self._set_forcing(i, f_rhs, tn + self._c_expl[i] * self._dt)
-                self._set_forcing(s, f_rhs, tn + self._dt)  # _b_new (hdg_imex.py:629)
-                if fused:
-                    eng.step()
-                else:
-                    eng.begin_step()
-                    if tracer:
-                        eng.tracer_begin_step()  # self._q[0].assign(q_tracer), hdg_imex.py:560
-                    for i in range(1, s):
-                        with PerformanceLog("bdm_projection"):
-                            eng.project_bdm(i - 1, i - 1)
-                        if self.use_projection_method:
-                            for _ in range(self.n_richardson):
-                                its = self.tentative_velocity_solve(f"stage_{i:d}")
-                                self.niter_tentative.update(its)
-                                its = self.pressure_solve(f"stage_{i:d}")
-                                self.niter_pressure.update(its)
-                                self._shift_pressure(_lib.HDG_STATE_UPDATE)
-                                eng.stage_update(i)
-                        else:
-                            with PerformanceLog("unsplit_solve"):
-                                its = eng.unsplit_solve(i)  # hdg_imex.py:600-620
-                            self.niter_tentative.update(its)
-                        self._shift_pressure(i)
-                        if tracer:
-                            eng.tracer_stage(i)  # hdg_imex.py:622-623
-                    its = self.pressure_solve("final_stage")
-                    self.niter_final_pressure.update(its)
-                    its = self.pressure_solve("pressure_reconstruction")
-                    self.niter_pressure_reconstruction.update(its)
-                    eng.finish_step()
-                    if tracer:
-                        eng.tracer_finish_step()  # hdg_imex.py:638-639
-            if self.callbacks:
-                Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
-                qt = self._tracer_function() if tracer else None
-                for callback in self.callbacks:
-                    callback(Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p"), tn + self._dt, q_tracer=qt)
-        self._finish_diagnostics(diagnostics)
-        self._finish_probes(probes)
-        self._finish_particles(particles)
-        if fused:
+        self._engine.iteration_stats(reset=True)
+        self._engine.timers(reset=True)
+
+    def _advance(self, k, f_rhs, tracer):
+        eng, s = self._engine, self.nstages
+        tn = k * self._dt
+        for i in range(s):
+            self._set_forcing(i, f_rhs, tn + self._c_expl[i] * self._dt)
+        self._set_forcing(s, f_rhs, tn + self._dt)  # _b_new (hdg_imex.py:629)
+        if self._fused:
+            eng.step()
+            return tn + self._dt
+        eng.begin_step()
+        if tracer:
+            eng.tracer_begin_step()  # self._q[0].assign(q_tracer), hdg_imex.py:560
+        for i in range(1, s):
+            with PerformanceLog("bdm_projection"):
+                eng.project_bdm(i - 1, i - 1)
+            if self.use_projection_method:
+                for _ in range(self.n_richardson):
+                    its = self.tentative_velocity_solve(f"stage_{i:d}")
+                    self.niter_tentative.update(its)
+                    its = self.pressure_solve(f"stage_{i:d}")
+                    self.niter_pressure.update(its)
+                    self._shift_pressure(_lib.HDG_STATE_UPDATE)
+                    eng.stage_update(i)
+            else:
+                with PerformanceLog("unsplit_solve"):
+                    its = eng.unsplit_solve(i)  # hdg_imex.py:600-620
+                self.niter_tentative.update(its)
+            self._shift_pressure(i)
+            if tracer:
+                eng.tracer_stage(i)  # hdg_imex.py:622-623
+        its = self.pressure_solve("final_stage")
+        self.niter_final_pressure.update(its)
+        its = self.pressure_solve("pressure_reconstruction")
+        self.niter_pressure_reconstruction.update(its)
+        eng.finish_step()
+        if tracer:
+            eng.tracer_finish_step()  # hdg_imex.py:638-639
+        return tn + self._dt
+
+    def _end_solve(self):
+        if self._fused:
             # per-solve breakdown of the fused steps from the engine's device-side timers (same labels as the
             # host timers of the per-solve path; "timestep" is already timed on the host)
-            for label, (n, tot, sq) in eng.timers(reset=True).items():
+            for label, (n, tot, sq) in self._engine.timers(reset=True).items():
                 if label != "timestep" and n:
                     PerformanceLog.add_aggregate(label, n, tot, sq)
-            sums, cnt = eng.iteration_stats()
-            for a, sm, c in zip((self.niter_tentative, self.niter_pressure, self.niter_final_pressure,
-                                 self.niter_pressure_reconstruction), sums, cnt):
+            sums, cnt = self._engine.iteration_stats()
+            for a, sm, c in zip(self._averagers(), sums, cnt):
                 a._n_samples, a._average = int(c), (sm / c if c else 0)
         print("average number of solver iterations")
         print(40 * "-")
@@ -218,10 +196,6 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
             print(f"  final pressure its          : {self.niter_final_pressure.value:8.2f}")
         print(f"  pressure reconstruction its : {self.niter_pressure_reconstruction.value:8.2f}")
         print()
-        Q, p, _ = eng.get_field(_lib.HDG_STATE_CURRENT, lam=False)
-        if tracer:
-            self._tracer_function()  # the final tracer field: self.q_tracer (the reference returns (Q, p) only)
-        return Function(self._V_Q, Q, "Q"), Function(self._V_p, p, "p")
 
 
 #######################################################################################

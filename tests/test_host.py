@@ -524,6 +524,13 @@ def test_small_dense_host_maths_and_the_kernel_dispatcher(tmp_path):
     assert out.count("hessenberg_eig n =") == 6 and out.count("sstep_ls") == 2, out
 
 
+def test_row_log_counts_rows_and_drops(tmp_path):
+    """csrc/hdg_row_log.hpp (plain C++, compiled here with g++), the bookkeeping of every per-step output: width 3 and capacity 2
+    give the offsets 0 and 3, then "dropped" with one drop counted; clear_counts keeps width, capacity and allocation; with
+    capacity 0 (and before the first reset) next() is a no-op that counts nothing."""
+    _host_check(tmp_path, "row_log_check")
+
+
 def test_new_host_headers_compile_alone(tmp_path):
     """Each host-only header of csrc/ compiles on its own with g++ -Wall -Wextra -Werror: no HIP header behind it."""
     import shutil
@@ -533,7 +540,7 @@ def test_new_host_headers_compile_alone(tmp_path):
     if gxx is None:
         pytest.skip("no g++")
     csrc = os.path.join(ROOT, "incompressibleeulerhdg_amd", "csrc")
-    for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp"):
+    for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_row_log.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp"):
         assert "hip" not in open(os.path.join(csrc, h)).read().split("#pragma once")[1].split("namespace hdg")[0], h
         tu = tmp_path / (h + ".cpp")
         tu.write_text(f'#include "{h}"\n')
