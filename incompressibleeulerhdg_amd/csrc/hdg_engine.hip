@@ -69,6 +69,7 @@ struct NotConverged {
 static constexpr int MAXV = 32;  // vectors per multi-dot launch
 
 struct Engine {
+  typedef std::vector<std::pair<const double*, double>> Terms;  // a linear combination of vectors: (vector, coefficient)
   const Options opt = options_from_env();  // every HDG_* switch, read when the engine is built (hdg_options.hpp)
   hdg_config cfg;
   Geo g;
@@ -1193,6 +1194,21 @@ struct Engine {
     }
     by_degree([&](auto k) { k_pgrad<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, a, ca, b, cb, p, l, gamma, out); });
   }
+  // the pressure gradient that takes the neighbouring linear combination into its own launch exists in the per-thread form at
+  // k <= 2 only (k_pgrad_terms)
+  bool glue_kernels() const { return opt.glue_fusion && !general && K <= 2 && !use_mfma_schur(); }
+  // out = (sum of terms) - b + gamma g(p, l) in one launch: the sum is formed in registers with the chain of k_lincomb, the
+  // rest is pgrad(sum, 1, b, -1, ...).  False: not this form (glue_kernels(); empty or chunked list) -- nothing launched.
+  bool pgrad_terms(const Terms& terms, const double* b, const double* p, const double* l, double gamma, double* out) {
+    LinComb lc;
+    if (!glue_kernels() || !b || !single_chain(lincomb_terms(terms), lc)) return false;
+    halo_L(l);
+    tally(LC_RHS, bQ() * (2 + lc.n) + bP() + bL());
+    by_degree([&](auto k) {
+      if constexpr (k() <= 2) k_pgrad_terms<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, lc, b, p, l, gamma, out);
+    });
+    return true;
+  }
   void weak_div(const double* q, double sc, double* out, bool broken) {
     if (general) { csr(broken ? gd.Bdiv : gd.Wdiv, q, sc, 0.0, out); return; }
     if (!broken) halo_Q(q);
@@ -1404,9 +1420,9 @@ struct Engine {
     for (int l = 0; l < nv; l++) d = std::min(d, fl.get(gm_V[l]));
     fl.set(out, d);
   }
-  void lincomb(long n, const std::vector<std::pair<const double*, double>>& terms, double* out) {
-    // merge duplicate pointers, drop zeros, chunks of 8
-    std::vector<std::pair<const double*, double>> t;
+  // the list a linear combination runs over: duplicate pointers merged, zeros dropped, order of first appearance
+  static Terms lincomb_terms(const Terms& terms) {
+    Terms t;
     for (auto& pr : terms) {
       if (pr.second == 0.0) continue;
       bool found = false;
@@ -1414,6 +1430,19 @@ struct Engine {
         if (q.first == pr.first) { q.second += pr.second; found = true; }
       if (!found) t.push_back(pr);
     }
+    return t;
+  }
+  // a merged list of 1 .. 8 terms as the kernel argument of a single k_lincomb-style chain
+  static bool single_chain(const Terms& t, LinComb& lc) {
+    if (t.empty() || t.size() > 8) return false;
+    lc.n = 0;
+    for (auto& q : t) { lc.v[lc.n] = q.first; lc.c[lc.n] = q.second; lc.n++; }
+    for (int k = lc.n; k < 8; k++) { lc.v[k] = nullptr; lc.c[k] = 0.0; }
+    return true;
+  }
+  void lincomb(long n, const Terms& terms, double* out) {
+    // merged terms in chunks of 8
+    const Terms t = lincomb_terms(terms);
     if (t.empty()) { zero(out, n); return; }
     bool first = true;
     for (size_t off = 0; off < t.size();) {
@@ -1524,11 +1553,14 @@ struct Engine {
   }
 
   const double* bvec(int slot) const { return bsep[slot] ? profile : brhs[slot]; }
-  void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
-    std::vector<std::pair<const double*, double>> terms;
+  Terms residual_terms(const std::vector<double>& cq, const std::vector<double>& cb) const {
+    Terms terms;
     for (int j = 0; j < s; j++) terms.push_back({stQ[j], cq[j]});
     for (int j = 0; j < s; j++) terms.push_back({bvec(j), cb[j] * bscale[j]});
-    lincomb(NQ, terms, out);
+    return terms;
+  }
+  void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
+    lincomb(NQ, residual_terms(cq, cb), out);
   }
 
   // ------------------------------------------------------------------ tentative velocity solve
@@ -1904,7 +1936,9 @@ struct Engine {
   std::vector<char> ch_slow;  // the last Chebyshev solve of the stage was slow: GMRES until the next re-estimate
   std::vector<int> ch_hand;   // learnt hand-over point of the stage: the check after which the Chebyshev rate last turned slow
   double* chd = nullptr;
-  int cheb_gmres(const double* qstar, double gamma, int didx, const double* b, double* x) {
+  // x: the engine's pointer to the iterate (Qtent[.]).  The solve may end with the iterate in the second buffer; the two
+  // pointers are then exchanged instead of the vector copied, so x is a reference and every reader goes through the member.
+  int cheb_gmres(const double* qstar, double gamma, int didx, const double* b, double*& x) {
     FlowScope flow_(*this);
     flow_fixed_Q(qstar);
     flow_fixed_Q(b);
@@ -1987,7 +2021,11 @@ struct Engine {
     // k_cheb_update), then the roles swap.  `cur` holds the newest iterate; x receives it when the solve ends.
     double* cur = x;
     double* oth = chd;
-    auto finish_in_x = [&]() { if (cur != x) copy(x, cur, NQ); };
+    auto finish_in_x = [&]() {
+      if (cur == x) return;
+      if (opt.glue_fusion) std::swap(x, chd);  // the bookkeeping (fl) goes by address and follows
+      else copy(x, cur, NQ);
+    };
     if (estimate) {
       adv_apply(cur, qstar, t, gamma, b);
       tent_precond_cheb(didx, t, nullptr, oth, cur, 0.0, 1.0 / theta);
@@ -2096,11 +2134,16 @@ struct Engine {
     ensure_dinv(i, gamma);
     std::vector<double> cq, cb;
     residual_coeffs(cfg, i, cq, cb);
-    residual_vector(cq, cb, wQ3);                          // r_i
-    adv_apply(stQ[i], Qstar[i - 1], wQ4, gamma);           // (I - gamma F) Q_i
     // rhs = r_i - (I - gamma F) Q_i + gamma g(w, p_i, lambda_i)      (hdg_imex.py:239-247)
     double* rhs = updU;  // _update.u is overwritten by the following pressure solve anyway
-    pgrad(wQ3, 1.0, wQ4, -1.0, stP[i], stL[i], gamma, rhs);
+    const Terms ri = residual_terms(cq, cb);               // r_i
+    adv_apply(stQ[i], Qstar[i - 1], wQ4, gamma);           // (I - gamma F) Q_i
+    // r_i is formed inside the pressure-gradient kernel where that has a form for it; otherwise as a vector of its own (the
+    // two launches commute: they write wQ3 and wQ4)
+    if (!pgrad_terms(ri, wQ4, stP[i], stL[i], gamma, rhs)) {
+      lincomb(NQ, ri, wQ3);
+      pgrad(wQ3, 1.0, wQ4, -1.0, stP[i], stL[i], gamma, rhs);
+    }
     int its = cfg.tent_solver == 0 ? gmres(Qstar[i - 1], gamma, i, rhs, Qtent[i])
                                    : cheb_gmres(Qstar[i - 1], gamma, i, rhs, Qtent[i]);
     it_sum[0] += its; it_cnt[0]++;
@@ -3105,7 +3148,19 @@ struct Engine {
     else throw std::string("unknown state selector");
   }
 
-  void begin_step() { copy(stQ[0], curQ, NQ); copy(stP[0], curP, NPv); copy(stL[0], curL, NLv); }
+  // Stage slot 0 is the state at the start of the step.  Nothing reads its pressure or trace (state_ptrs does not even expose
+  // slot 0), and the velocity of the current state is read by nothing between here and the final-stage back-substitution,
+  // which writes all of it after the last reader of slot 0 (the final residual) has run: the recorders (end_of_step), the
+  // tracer (stQ[0]) and hdg_get_field all come after that or go through the members.  So a whole step (whole_step: step(),
+  // which reaches that back-substitution or fails and undoes the exchange) exchanges the velocity pointers and drops the
+  // other two copies.
+  // hdg_begin_step keeps the copies: its caller may read the current state, or begin again, before the step is complete.
+  // curL and recL keep their copies too (finish_step): the final-stage and reconstruction solves warm-start from the values
+  // at those addresses, and HDG_STATE_RECON is readable.
+  void begin_step(bool whole_step = false) {
+    if (whole_step && opt.glue_fusion) { std::swap(stQ[0], curQ); return; }
+    copy(stQ[0], curQ, NQ); copy(stP[0], curP, NPv); copy(stL[0], curL, NLv);
+  }
   void stage_update(int i) {
     const double gamma = cfg.a_impl[i * s + i] * cfg.dt;
     lincomb(NQ, {{stQ[i], 1.0}, {Qtent[i], 1.0}, {updU, gamma}}, stQ[i]);
@@ -3119,7 +3174,14 @@ struct Engine {
   }
   void step() {
     Timed tm_(*this, T_STEP);
-    begin_step();
+    begin_step(true);
+    // a step that fails (a Krylov solve that does not converge) before the final-stage back-substitution has written the new
+    // velocity leaves the current state where it was, as the copy did: the exchange is undone
+    struct Undo {
+      Engine& e;
+      bool armed;
+      ~Undo() { if (armed) std::swap(e.stQ[0], e.curQ); }
+    } undo{*this, opt.glue_fusion};
     tracer_begin_step();
     for (int i = 1; i < s; i++) {
       { Timed tb_(*this, T_BDM); bdm(stQ[i - 1], Qstar[i - 1]); }
@@ -3137,6 +3199,7 @@ struct Engine {
       tracer_stage(i);
     }
     pressure_solve(HDG_KEY_FINAL_STAGE);
+    undo.armed = false;
     pressure_solve(HDG_KEY_PRESSURE_RECONSTRUCTION);
     finish_step();
     tracer_finish_step();

@@ -1230,23 +1230,13 @@ __global__ __launch_bounds__(128) void k_blockdiag(Geo g, const double* __restri
 // pressure gradient:  out = ca*a + cb*b + gamma * ( B^T p - sum_e C_e^T lambda_e )
 //   g(w,p,lambda) = (p, div w)_K - <lambda, w.n_K>_{dK}   (hdg_imex.py:333-340)
 // ------------------------------------------------------------------------------------------
+// gamma * ( B^T p - sum_e C_e^T lambda_e ) added to y, result stored: the part of k_pgrad after its vector operands
 template <int K>
-__global__ __launch_bounds__(128) void k_pgrad(Geo g, DevTables T, const double* __restrict__ a, double ca,
-                                                const double* __restrict__ b, double cb, const double* __restrict__ p,
-                                                const double* __restrict__ lam, double gamma, double* __restrict__ out) {
+__device__ __forceinline__ void pgrad_finish(const Geo& g, const DevTables& T, int s, int i, int j, long c,
+                                             const double* __restrict__ p, const double* __restrict__ lam, double gamma,
+                                             double (&y)[2 * Dim<K>::NU], double* __restrict__ out) {
   constexpr int NU = Dim<K>::NU, NP = Dim<K>::NP, NL = Dim<K>::NL, N2 = 2 * NU;
-  HDG_CELL_PROLOGUE
-  double y[N2], pp[NP], acc[N2];
-  {
-    double ta[N2], tb[N2];
-    if (a) load_vel<NU>(a, g.Nc, c, ta);
-    if (b) load_vel<NU>(b, g.Nc, c, tb);
-#pragma unroll
-    for (int n = 0; n < N2; n++) {
-      y[n] = (a ? ca * ta[n] : 0.0) + (b ? cb * tb[n] : 0.0);
-      acc[n] = 0.0;
-    }
-  }
+  double pp[NP], acc[N2];
   load_cell<NP>(p, g.Nc, c, pp);
   const double* __restrict__ Bm = T.B[s];
 #pragma unroll
@@ -1276,6 +1266,56 @@ __global__ __launch_bounds__(128) void k_pgrad(Geo g, DevTables T, const double*
 #pragma unroll
   for (int n = 0; n < N2; n++) y[n] = fma(gamma, acc[n], y[n]);
   store_vel<NU>(out, g.Nc, c, y);
+}
+template <int K>
+__global__ __launch_bounds__(128) void k_pgrad(Geo g, DevTables T, const double* __restrict__ a, double ca,
+                                                const double* __restrict__ b, double cb, const double* __restrict__ p,
+                                                const double* __restrict__ lam, double gamma, double* __restrict__ out) {
+  constexpr int NU = Dim<K>::NU, N2 = 2 * NU;
+  HDG_CELL_PROLOGUE
+  double y[N2];
+  {
+    double ta[N2], tb[N2];
+    if (a) load_vel<NU>(a, g.Nc, c, ta);
+    if (b) load_vel<NU>(b, g.Nc, c, tb);
+#pragma unroll
+    for (int n = 0; n < N2; n++) y[n] = (a ? ca * ta[n] : 0.0) + (b ? cb * tb[n] : 0.0);
+  }
+  pgrad_finish<K>(g, T, s, i, j, c, p, lam, gamma, y, out);
+}
+// out = a - b + gamma * ( ... ) with a given as a term list (at most 8 terms, merged by Engine::lincomb_terms): a = sum_k c_k v_k
+// is formed per cell in registers by the chain of k_lincomb -- accumulator from 0, fma(c_k, v_k, acc) in list order -- so the
+// result has the bits of k_lincomb followed by k_pgrad(a, 1, b, -1), without the vector a going through memory.  Only these
+// coefficients: 1 * a + (-1) * b is the same number whether or not the compiler contracts a product into the sum, which
+// general ca, cb would not promise of two differently written kernels.
+struct LinComb {
+  const double* v[8];
+  double c[8];
+  int n;
+};
+template <int K>
+__global__ __launch_bounds__(128) void k_pgrad_terms(Geo g, DevTables T, LinComb lc, const double* __restrict__ b,
+                                                      const double* __restrict__ p, const double* __restrict__ lam,
+                                                      double gamma, double* __restrict__ out) {
+  constexpr int NU = Dim<K>::NU, N2 = 2 * NU;
+  HDG_CELL_PROLOGUE
+  double y[N2];
+  {
+    double ta[N2], tb[N2];
+#pragma unroll
+    for (int n = 0; n < N2; n++) ta[n] = 0.0;
+    for (int k = 0; k < lc.n; k++) {
+      double tv[N2];
+      load_vel<NU>(lc.v[k], g.Nc, c, tv);
+      const double ck = lc.c[k];
+#pragma unroll
+      for (int n = 0; n < N2; n++) ta[n] = fma(ck, tv[n], ta[n]);
+    }
+    load_vel<NU>(b, g.Nc, c, tb);
+#pragma unroll
+    for (int n = 0; n < N2; n++) y[n] = ta[n] - tb[n];
+  }
+  pgrad_finish<K>(g, T, s, i, j, c, p, lam, gamma, y, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2065,11 +2105,6 @@ __device__ __forceinline__ hdg_d2 ldv(const float* p, long i) {
   return hdg_d2{(double)v.x, (double)v.y};
 }
 
-struct LinComb {
-  const double* v[8];
-  double c[8];
-  int n;
-};
 template <bool NT>
 __global__ void k_lincomb(long N, LinComb lc, double* __restrict__ out) {
   HDG_VEC_PROLOGUE
