@@ -26,6 +26,7 @@ extern "C" {
 #endif
 
 #define HDG_MAX_STAGES 5
+#define HDG_MAX_TRACERS 16
 
 enum {
   HDG_OK = 0,
@@ -89,6 +90,9 @@ typedef struct hdg_config {
   double dg_rtol;
   int dg_restart;
   int dg_maxit;
+  /* number of passive tracers one engine carries (hdg_set_tracer): 0 means 1, at most HDG_MAX_TRACERS; anything else is
+   * HDG_ERR_ARG from the three constructors.  Always the LAST field: callers that zero the struct keep one tracer. */
+  int n_tracers;
 } hdg_config;
 
 typedef struct hdg_handle hdg_handle;
@@ -264,7 +268,14 @@ int hdg_get_kernel_forms(hdg_handle* h, int* forms);
  * after every stage (hdg_imex.py:415-431,622-623), q^{n+1} = q_0 + dt sum_i b_expl[i] M^-1 T(q_i, P(Q_i)) at the end of
  * the step (:433-448,638-639); hdg_implicit.py:93-96,192-193: q^{n+1} = q^n + dt M^-1 T(q^n, P(Q^n)).
  * hdg_set_tracer(h, q) switches the tracer on (q: nodal DG_k values, pressure layout; NULL switches it off); hdg_step /
- * hdg_run_separable / hdg_implicit_step then carry it along; the three step-level calls serve the per-solve loop. */
+ * hdg_run_separable / hdg_implicit_step / hdg_dg_implicit_step then carry it along; the three step-level calls serve the
+ * per-solve loop.
+ * Several tracers: an engine created with cfg.n_tracers = n > 1 carries n tracers through the one
+ * flow.  q of hdg_set_tracer / hdg_get_tracer is then n consecutive nodal DG_k fields, tracer-major, each in the pressure
+ * layout (n * N_c * n_p values; NULL switches all of them off), and every call above advances all of them: the velocity
+ * is projected once per stage and one launch of the transport kernel covers every tracer.  Each tracer evolves exactly as it
+ * would alone.  hdg_apply_tracer_advection stays a single-field hook.  The tracer columns of the per-step outputs (columns 5
+ * and 6 of the diagnostics, column q of the point values) refer to tracer 0.  Strip partitions: no tracer, as before. */
 int hdg_set_tracer(hdg_handle* h, const double* q);
 int hdg_get_tracer(hdg_handle* h, double* q);
 int hdg_tracer_begin_step(hdg_handle* h);        /* self._q[0].assign(q_tracer), hdg_imex.py:560 */
@@ -297,7 +308,7 @@ int hdg_integrate_pressure(hdg_handle* h, const double* p, double* integral);
  * pressure p and tracer q:
  *   0 energy 1/2 int |u|^2;  1 enstrophy 1/2 sum_K int_K (d_x u_y - d_y u_x)^2 (broken curl);  2 div_l2 (sum_K int_K (div u)^2)^1/2;
  *   3 jump_l2 (sum_F int_F [u.n]^2)^1/2 over every edge once, boundary edges (u.n) included on non-periodic meshes;
- *   4 int p;  5 int q;  6 1/2 int q^2 (5, 6: NaN without a tracer);  7 max |u| over the nodes of hdg_node_coordinates;
+ *   4 int p;  5 int q;  6 1/2 int q^2 (5, 6: NaN without a tracer; recorded rows: tracer 0 of several);  7 max |u| over the nodes of hdg_node_coordinates;
  *   8 dt max_K (max nodal |u| in K) / h_K, h_K the shortest edge of K.
  * Strip partitions: every rank passes its own strip and receives the global values (collective).
  * hdg_compute_diagnostics: the nine values of nodal fields (layouts of hdg_set_state; q NULL: no tracer) into out[9].
@@ -314,7 +325,8 @@ int hdg_get_diagnostics(hdg_handle* h, double* rows, int max_rows, int* n_rows, 
 
 /* ---- point values.  Five columns per point (x, y):
  *   0 ux  1 uy  2 p  3 q  4 omega = d_x uy - d_y ux, the curl of the broken velocity inside the cell that owns the point
- *   (not the continuous vorticity of the animation callback).  A column whose field is not given is NaN (q without a tracer).
+ *   (not the continuous vorticity of the animation callback).  A column whose field is not given is NaN (q without a tracer;
+ *   recorded rows take q from tracer 0 of several).
  * Ownership (the fields are discontinuous across cell boundaries):
  *   square meshes: i = min(floor(x / h), nx - 1), j = min(floor(y / h), ny - 1), fx = x / h - i, fy = y / h - j; the lower
  *     triangle when fx + fy <= 1, the upper one otherwise.  Periodic square: x, y first wrapped into [0, L) (a value that

@@ -17,6 +17,7 @@ SRC = os.path.join(_HERE, "csrc", "hdg_engine.hip")
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_mi355x.h"))
 
 HDG_MAX_STAGES = 5
+HDG_MAX_TRACERS = 16
 HDG_KEY_FINAL_STAGE = 0
 HDG_KEY_PRESSURE_RECONSTRUCTION = -1
 HDG_STATE_CURRENT = 0
@@ -79,6 +80,7 @@ class hdg_config(C.Structure):
         ("dg_rtol", C.c_double),
         ("dg_restart", C.c_int),
         ("dg_maxit", C.c_int),
+        ("n_tracers", C.c_int),  # always the last field (include/hdg_mi355x.h)
     ]
 
 
@@ -260,6 +262,8 @@ class Engine:
         cfg.dg_rtol = float(kw.get("dg_rtol", 1e-10))
         cfg.dg_restart = int(kw.get("dg_restart", 100))
         cfg.dg_maxit = int(kw.get("dg_maxit", 3000))
+        # passive tracers carried through the one flow (0 means 1; the library refuses anything outside 0 .. HDG_MAX_TRACERS)
+        cfg.n_tracers = int(kw.get("n_tracers", 0))
         self.cfg = cfg
         self.h = _h()
         self.rank, self.nranks = int(kw.get("rank", 0)), int(kw.get("nranks", 1))
@@ -290,6 +294,9 @@ class Engine:
         self.shape_Q = (self.n_cells * self.n_u, 2)
         self.shape_p = (self.n_cells * self.n_p,)
         self.shape_l = (self.n_edges * self.n_l,)
+        # the tracer block of set_tracer / get_tracer: one field, or (n_tracers, N_p) tracer-major
+        self.n_tracers = max(1, cfg.n_tracers)
+        self.shape_q = self.shape_p if self.n_tracers == 1 else (self.n_tracers,) + self.shape_p
         # dimension of the GLOBAL mixed state (Q, p, lambda) advanced per step
         nxg, nyg = cfg.nx, cfg.ny
         self.n_total = 2 * nxg * nyg * (2 * self.n_u + self.n_p) + (3 * nxg * nyg + (0 if cfg.periodic else nxg + nyg)) * self.n_l
@@ -434,11 +441,12 @@ class Engine:
 
     # --- passive tracer, continuous-space diagnostics
     def set_tracer(self, q):
-        q = None if q is None else _arr(q, self.shape_p)
+        """q: (N_p,) with one tracer, (n_tracers, N_p) with several (Engine(n_tracers=...)); None switches all of them off."""
+        q = None if q is None else _arr(q, self.shape_q)
         self._ck(self.lib.hdg_set_tracer(self.h, _ptr(q)))
 
     def get_tracer(self):
-        q = np.empty(self.shape_p)
+        q = np.empty(self.shape_q)
         self._ck(self.lib.hdg_get_tracer(self.h, _ptr(q)))
         return q
 

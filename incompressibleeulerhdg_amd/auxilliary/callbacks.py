@@ -17,7 +17,8 @@ class Callback(ABC):
 
     @abstractmethod
     def __call__(self, Q, p, t, q_tracer=None):
-        """Invoke the callback for velocity / pressure (and tracer) fields at time t."""
+        """Invoke the callback for velocity / pressure (and tracer) fields at time t; q_tracer: the Function of one tracer,
+        the list of Functions of several (steppers built with n_tracers > 1)."""
 
     @abstractmethod
     def reset(self):
@@ -48,6 +49,8 @@ class AnimationCallback(Callback):
 
     def __call__(self, Q, p, t, q_tracer=None):
         fields = [Q, p, self.vorticity(Q)]
-        if q_tracer is not None:
+        if isinstance(q_tracer, (list, tuple)):  # several tracers (n_tracers > 1): every member, by its own name
+            fields.extend(q_tracer)
+        elif q_tracer is not None:
             fields.append(q_tracer)
         self.outfile.write(*fields, time=t)

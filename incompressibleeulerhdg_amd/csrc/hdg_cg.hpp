@@ -173,61 +173,106 @@ __global__ __launch_bounds__(128) void k_cg_gather(Geo g, CgTabs C, const double
 //   un_K = (u.n_K + |u.n_K|)/2 (outflow), un_K' = (|u.n_K| - u.n_K)/2 (inflow); u continuous, so taken from this cell.
 // The pressure / tracer modes are the first NP velocity modes (hierarchical Dubiner basis, same scaling), so the
 // tabulations of the advection operator serve both.  Cell rule exact to 3k+2, edge rule ceil((3k+4)/2) Gauss points.
+//
+// Batched over nt tracers stored tracer-major (tracer t of q / out starts at t * tstride): a thread
+// owns one cell and the TB tracers blockIdx.y * TB ... of it.  The velocity coefficients are loaded once; at every
+// quadrature point the quantities that depend on the velocity alone -- the cell rule's G_r = grad chi_r . u + chi_r div u,
+// the edge rule's outflow / inflow speeds -- are formed once and applied to each tracer, which keeps its own qc, qn and F.
+// Per tracer the floating-point operations and their order are those of one tracer alone, whatever TB.  The last block of
+// tracers may be short (nb < TB, uniform over the block): its spare slots hold zeros, and only their loads and stores are
+// skipped.  The host picks TB <= nt (Engine::tracer_adv), so a short block occurs only behind a full one.
 template <int K>
-__global__ __launch_bounds__(128) void k_tracer_adv(Geo g, DevTables T, const double* __restrict__ q, const double* __restrict__ u,
-                                                     double* __restrict__ out) {
+struct TracerBlock { static constexpr int TB = K == 1 ? 4 : K == 2 ? 4 : K == 3 ? 2 : 1; };  // register budget: DESIGN.md section 16
+template <int K, int TB>
+__global__ __launch_bounds__(128) void k_tracer_adv(Geo g, DevTables T, int nt, long tstride, const double* __restrict__ q,
+                                                     const double* __restrict__ u, double* __restrict__ out) {
   constexpr int NU = Dim<K>::NU, NP = Dim<K>::NP;
   HDG_CELL_PROLOGUE
-  double qc[NP], uc[2 * NU], F[NP];
-  load_cell<NP>(q, g.Nc, c, qc);
-  load_vel<NU>(u, g.Nc, c, uc);
+  const int t0 = blockIdx.y * TB;
+  const int nb = nt - t0 < TB ? nt - t0 : TB;
+  double qc[TB][NP], uc[2 * NU], F[TB][NP];
 #pragma unroll
-  for (int r = 0; r < NP; r++) F[r] = 0.0;
+  for (int b = 0; b < TB; b++) {
+    if (b < nb) load_cell<NP>(q + (t0 + b) * tstride, g.Nc, c, qc[b]);
+#pragma unroll
+    for (int r = 0; r < NP; r++) { F[b][r] = 0.0; if (b >= nb) qc[b][r] = 0.0; }
+  }
+  load_vel<NU>(u, g.Nc, c, uc);
   {
     const double* __restrict__ Phi = T.cPhi[s];
     const double* __restrict__ Gx = T.cGx[s];
     const double* __restrict__ Gy = T.cGy[s];
 #pragma unroll 1
     for (int p = 0; p < T.nqc; p++) {
-      double qq = 0, ux = 0, uy = 0, dv = 0;
+      double ux = 0, uy = 0, dv = 0, qq[TB];
+#pragma unroll
+      for (int b = 0; b < TB; b++) qq[b] = 0;
 #pragma unroll
       for (int m = 0; m < NU; m++) {
         const double ph = Phi[p * NU + m];
         ux = fma(ph, uc[m], ux);
         uy = fma(ph, uc[NU + m], uy);
         dv = fma(Gx[p * NU + m], uc[m], fma(Gy[p * NU + m], uc[NU + m], dv));
-        if (m < NP) qq = fma(ph, qc[m], qq);
-      }
-      const double w = T.cw[p] * qq;
+        if (m < NP) {
 #pragma unroll
-      for (int r = 0; r < NP; r++) F[r] = fma(w, fma(Gx[p * NU + r], ux, fma(Gy[p * NU + r], uy, Phi[p * NU + r] * dv)), F[r]);
+          for (int b = 0; b < TB; b++) qq[b] = fma(ph, qc[b][m], qq[b]);
+        }
+      }
+      double G[NP];
+#pragma unroll
+      for (int r = 0; r < NP; r++) G[r] = fma(Gx[p * NU + r], ux, fma(Gy[p * NU + r], uy, Phi[p * NU + r] * dv));
+      const double cw = T.cw[p];
+#pragma unroll
+      for (int b = 0; b < TB; b++) {
+        const double w = cw * qq[b];
+#pragma unroll
+        for (int r = 0; r < NP; r++) F[b][r] = fma(w, G[r], F[b][r]);
+      }
     }
   }
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     long cn;
     if (!nbr(s, e, i, j, g, cn)) continue;
-    double qn[NP];
-    load_cell<NP>(q, g.Nc, cn, qn);
+    double qn[TB][NP];
+#pragma unroll
+    for (int b = 0; b < TB; b++) {
+      if (b < nb) load_cell<NP>(q + (t0 + b) * tstride, g.Nc, cn, qn[b]);
+      else {
+#pragma unroll
+        for (int r = 0; r < NP; r++) qn[b][r] = 0.0;
+      }
+    }
     const double* __restrict__ Po = T.ePhi[s][e];
     const double* __restrict__ Pn = T.ePhi[1 - s][e];
     const double nxo = T.sig[s][e] * T.enx[e], nyo = T.sig[s][e] * T.eny[e];
 #pragma unroll 1
     for (int p = 0; p < T.nqe; p++) {
-      double un = 0, qk = 0, qm = 0;
+      double un = 0, qk[TB], qm[TB];
+#pragma unroll
+      for (int b = 0; b < TB; b++) qk[b] = qm[b] = 0;
 #pragma unroll
       for (int m = 0; m < NU; m++) {
         const double po = Po[p * NU + m];
         un = fma(po, fma(nxo, uc[m], nyo * uc[NU + m]), un);
-        if (m < NP) { qk = fma(po, qc[m], qk); qm = fma(Pn[p * NU + m], qn[m], qm); }
-      }
-      const double a = fabs(un);
-      const double flux = T.ew[e][p] * (0.5 * (un + a) * qk - 0.5 * (a - un) * qm);
+        if (m < NP) {
+          const double pn = Pn[p * NU + m];
 #pragma unroll
-      for (int r = 0; r < NP; r++) F[r] = fma(-Po[p * NU + r], flux, F[r]);
+          for (int b = 0; b < TB; b++) { qk[b] = fma(po, qc[b][m], qk[b]); qm[b] = fma(pn, qn[b][m], qm[b]); }
+        }
+      }
+      const double a = fabs(un), ew = T.ew[e][p];
+#pragma unroll
+      for (int b = 0; b < TB; b++) {
+        const double flux = ew * (0.5 * (un + a) * qk[b] - 0.5 * (a - un) * qm[b]);
+#pragma unroll
+        for (int r = 0; r < NP; r++) F[b][r] = fma(-Po[p * NU + r], flux, F[b][r]);
+      }
     }
   }
-  store_cell<NP>(out, g.Nc, c, F);
+#pragma unroll
+  for (int b = 0; b < TB; b++)
+    if (b < nb) store_cell<NP>(out + (t0 + b) * tstride, g.Nc, c, F[b]);
 }
 
 

@@ -418,6 +418,7 @@ struct Engine {
   }
   Engine(const hdg_config& c, Comm* comm_, int nv, const double* coords, int nc, const int* cells) : cfg(c), comm(comm_) {
     if (c.degree < 1 || c.degree > 4) throw std::string("degree must be in 1..4");
+    n_tr = checked_n_tracers(c);
     if (c.nstages < 1 || c.nstages > HDG_MAX_STAGES) throw std::string("nstages out of range");
     if (!(c.dt > 0)) throw std::string("dt must be positive");
     if (comm->size != 1) throw std::string("general meshes are implemented for a single rank");
@@ -516,6 +517,7 @@ struct Engine {
   // ------------------------------------------------------------------ construction
   Engine(const hdg_config& c, Comm* comm_) : cfg(c), comm(comm_) {
     if (c.degree < 1 || c.degree > 4) throw std::string("degree must be in 1..4");
+    n_tr = checked_n_tracers(c);
     if (c.nx < 1 || c.ny < 1) throw std::string("nx, ny must be positive");
     if (c.nx != c.ny) throw std::string("only square meshes nx == ny (UnitSquareMesh(nx, nx), driver.py:181)");
     if (c.nstages < 1 || c.nstages > HDG_MAX_STAGES) throw std::string("nstages out of range");
@@ -3210,11 +3212,11 @@ struct Engine {
     const double dtt = cfg.dt;
     if (tracer_on) {  // hdg_implicit.py:93-96: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
-      tracer_adv(q_cur, uproj, q_t);
+      tracer_adv(q_cur, uproj, q_t, n_tr);
     }
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
-    auto tracer_end = [&]() { if (tracer_on) axpby(NPv, dtt, q_t, 1.0, q_cur); };
+    auto tracer_end = [&]() { if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur); };
     ensure_dinv(0, dtt);
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }             // hdg_implicit.py:98
     if (!cfg.use_projection) {
@@ -3344,7 +3346,7 @@ struct Engine {
     const double dtt = cfg.dt;
     if (tracer_on) {  // dg_implicit.py:117-120: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
-      tracer_adv(q_cur, uproj, q_t);
+      tracer_adv(q_cur, uproj, q_t, n_tr);
     }
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
     lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
@@ -3357,7 +3359,7 @@ struct Engine {
     shift(curP, nullptr);
     it_sum[0] += it; it_cnt[0]++;
     if (its) *its = it;
-    if (tracer_on) axpby(NPv, dtt, q_t, 1.0, q_cur);  // dg_implicit.py:131-132, after a successful solve only
+    if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur);  // dg_implicit.py:131-132, after a successful solve only
   }
   // operator-level access (hdg_apply_dg_operator): out = K x of dg_implicit.py:48-71 (unscaled rows, phi not y)
   void dg_operator(const double* qstar, const double* u, const double* p, double dtt, double* out_u, double* out_p) {
@@ -3650,30 +3652,60 @@ struct Engine {
       }
   }
 
-  // ------------------------------------------------------------------ passive tracer (explicit DG transport)
+  // ------------------------------------------------------------------ passive tracers (explicit DG transport)
+  // n_tr tracers (hdg_config::n_tracers, 0 means 1) ride one flow: every tracer vector holds them tracer-major and contiguous,
+  // [t][NPv], so the copies and updates below are the single-tracer calls over n_tr * NPv entries, the projection of the
+  // stage velocity runs once per stage and one launch of the transport kernel covers all tracers.
   bool tracer_on = false;
+  int n_tr = 1;
+  // hdg_config::n_tracers: 0 means 1; anything outside 0 .. HDG_MAX_TRACERS is refused (the three constructors call this
+  // before they touch the device or the transport)
+  static int checked_n_tracers(const hdg_config& c) {
+    if (c.n_tracers < 0 || c.n_tracers > HDG_MAX_TRACERS)
+      throw std::string("n_tracers must be in 0 .. " + std::to_string(HDG_MAX_TRACERS) + " (got " + std::to_string(c.n_tracers) + ")");
+    return c.n_tracers == 0 ? 1 : c.n_tracers;
+  }
+  long NTv() const { return (long)n_tr * NPv; }
   double *q_cur = nullptr, *q_fin = nullptr, *q_t = nullptr;
   std::vector<double*> q_st;
   void tracer_alloc() {
     if (q_cur) return;
-    q_cur = dalloc(NPv); q_fin = dalloc(NPv); q_t = dalloc(NPv);
-    for (int i = 0; i < s; i++) q_st.push_back(dalloc(NPv));
+    q_cur = dalloc(NTv()); q_fin = dalloc(NTv()); q_t = dalloc(NTv());
+    for (int i = 0; i < s; i++) q_st.push_back(dalloc(NTv()));
   }
-  // out = M^-1 T(.; q, u) for a continuous velocity u given as a broken modal vector
-  void tracer_adv(const double* q, const double* u, double* out) {
-    if (general) { by_degree([&](auto k) { k_g_tracer<k()><<<(gm->nc + 63) / 64, 64, 0, stream>>>(ggeo, q, u, out); }); return; }
-    halo_P(q);
-    by_degree([&](auto k) { k_tracer_adv<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt, q, u, out); });
+  // tracers per thread of the transport kernels: the largest power of two within the degree's register budget
+  // (TracerBlock<K>) and within n, so one tracer runs the TB = 1 instantiation and a short block only follows a full one
+  template <int TBMAX, class F> static void by_tracer_block(int n, F&& f) {
+    const int tb = std::min(TBMAX, n >= 4 ? 4 : (n >= 2 ? 2 : 1));
+    if constexpr (TBMAX >= 4) { if (tb == 4) { f(std::integral_constant<int, 4>()); return; } }
+    if constexpr (TBMAX >= 2) { if (tb == 2) { f(std::integral_constant<int, 2>()); return; } }
+    f(std::integral_constant<int, 1>());
+  }
+  // out = M^-1 T(.; q, u) for a continuous velocity u given as a broken modal vector; q, out: n tracers, tracer-major
+  void tracer_adv(const double* q, const double* u, double* out, int n) {
+    if (n < 1 || n > HDG_MAX_TRACERS) throw std::string("tracer count out of range");
+    if (!general) halo_rows(const_cast<double*>(q), (long)g.R * g.nx, g.nx, NP * 2 * n, 1);  // halo_P of every tracer: contiguous planes
+    by_degree([&](auto k) {
+      constexpr int KK = decltype(k)::value;
+      by_tracer_block<TracerBlock<KK>::TB>(n, [&](auto tb) {
+        constexpr int TB = decltype(tb)::value;
+        const unsigned nblk = (unsigned)((n + TB - 1) / TB);
+        if (general) { k_g_tracer<KK, TB><<<dim3((gm->nc + 63) / 64, nblk), 64, 0, stream>>>(ggeo, n, NPv, q, u, out); return; }
+        dim3 grid = cell_grid();
+        grid.y = nblk;
+        k_tracer_adv<KK, TB><<<grid, bs(), 0, stream>>>(g, dt, n, NPv, q, u, out);
+      });
+    });
   }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
     if (!tracer_on) return;
-    copy(q_st[0], q_cur, NPv);
-    copy(q_fin, q_cur, NPv);
+    copy(q_st[0], q_cur, NTv());
+    copy(q_fin, q_cur, NTv());
     if (cfg.b_expl[0] != 0.0) {
       cg_project(stQ[0], uproj);
-      tracer_adv(q_st[0], uproj, q_t);
-      axpby(NPv, cfg.dt * cfg.b_expl[0], q_t, 1.0, q_fin);
+      tracer_adv(q_st[0], uproj, q_t, n_tr);
+      axpby(NTv(), cfg.dt * cfg.b_expl[0], q_t, 1.0, q_fin);
     }
   }
   // hdg_imex.py:622-623: q_i = q_0 + dt sum_{j<i} a_expl[i,j] T(q_j, P(Q_i)); plus the i-th term of the final residual
@@ -3681,19 +3713,19 @@ struct Engine {
     if (!tracer_on) return;
     if (i < 1 || i >= s) throw std::string("stage out of range");
     cg_project(stQ[i], uproj);
-    copy(q_st[i], q_st[0], NPv);
+    copy(q_st[i], q_st[0], NTv());
     for (int j = 0; j < i; j++)
       if (cfg.a_expl[i * s + j] != 0.0) {
-        tracer_adv(q_st[j], uproj, q_t);
-        axpby(NPv, cfg.dt * cfg.a_expl[i * s + j], q_t, 1.0, q_st[i]);
+        tracer_adv(q_st[j], uproj, q_t, n_tr);
+        axpby(NTv(), cfg.dt * cfg.a_expl[i * s + j], q_t, 1.0, q_st[i]);
       }
     if (cfg.b_expl[i] != 0.0) {
-      tracer_adv(q_st[i], uproj, q_t);
-      axpby(NPv, cfg.dt * cfg.b_expl[i], q_t, 1.0, q_fin);
+      tracer_adv(q_st[i], uproj, q_t, n_tr);
+      axpby(NTv(), cfg.dt * cfg.b_expl[i], q_t, 1.0, q_fin);
     }
   }
   void tracer_finish_step() {  // hdg_imex.py:638-639
-    if (tracer_on) copy(q_cur, q_fin, NPv);
+    if (tracer_on) copy(q_cur, q_fin, NTv());
   }
 
   // ------------------------------------------------------------------ per-step outputs (hdg_row_log.hpp)
@@ -4257,6 +4289,7 @@ static int create_impl(const hdg_config* cfg, int rank, int nranks, int backend,
   if (!cfg || !out || nranks < 1 || rank < 0 || rank >= nranks) return HDG_ERR_ARG;
   *out = nullptr;
   try {
+    hdg::Engine::checked_n_tracers(*cfg);
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed (no GPU?)"; return HDG_ERR_HIP; }
     std::unique_ptr<hdg::Comm> comm;  // owned here until the engine has been built
     if (nranks == 1 && hdg::options_from_env().force_rccl) {
@@ -4290,6 +4323,7 @@ int hdg_create_general(const hdg_config* cfg, int n_vertices, const double* coor
   if (!cfg || !out || !coords || !cells) return HDG_ERR_ARG;
   *out = nullptr;
   try {
+    hdg::Engine::checked_n_tracers(*cfg);
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed (no GPU?)"; return HDG_ERR_HIP; }
     std::unique_ptr<hdg::Comm> comm(new hdg::Comm());
     hdg::Engine* e = new hdg::Engine(*cfg, comm.get(), n_vertices, coords, n_cells, cells);
@@ -4569,7 +4603,7 @@ int hdg_set_tracer(hdg_handle* h, const double* q) {
   else {
     E.cg_setup();
     E.tracer_alloc();
-    E.put_P(q, E.q_cur);
+    for (int t = 0; t < E.n_tr; t++) E.put_P(q + t * E.NPb, E.q_cur + t * E.NPv);
     E.tracer_on = true;
   }
   HDG_API_END(h)
@@ -4577,7 +4611,7 @@ int hdg_set_tracer(hdg_handle* h, const double* q) {
 int hdg_get_tracer(hdg_handle* h, double* q) {
   HDG_API_BEGIN(h)
   if (!E.tracer_on || !q) throw std::string("no tracer field");
-  E.get_P(E.q_cur, q);
+  for (int t = 0; t < E.n_tr; t++) E.get_P(E.q_cur + t * E.NPv, q + t * E.NPb);
   HDG_API_END(h)
 }
 int hdg_tracer_begin_step(hdg_handle* h) {
@@ -4650,7 +4684,7 @@ int hdg_apply_tracer_advection(hdg_handle* h, const double* q, const double* u, 
   const double* vel = E.wQ1;
   if (project) { E.cg_project(E.wQ1, E.uproj); vel = E.uproj; }
   E.put_P(q, E.wP1);
-  E.tracer_adv(E.wP1, vel, E.q_t);
+  E.tracer_adv(E.wP1, vel, E.q_t, 1);
   E.get_P(E.q_t, out);
   HDG_API_END(h)
 }

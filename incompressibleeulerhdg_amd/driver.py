@@ -27,7 +27,7 @@ import time
 
 import numpy as np
 
-from ._lib import DIAGNOSTICS, POINT_COLUMNS
+from ._lib import DIAGNOSTICS, HDG_MAX_TRACERS, POINT_COLUMNS
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
@@ -73,6 +73,9 @@ def build_parser():
     parser.add_argument("--animation", action="store_true", default=False,
                         help="save velocity and pressure fields at the end of each timestep as an animation")
     parser.add_argument("--tracer_advection", action="store_true", default=False, help="advect tracer field")
+    parser.add_argument("--tracers", metavar="N", type=int, default=1,
+                        help="number of passive tracers advected through the one flow (with --tracer_advection); tracer m "
+                             "starts from sin(2 pi (m+1) x) sin(2 pi (m+1) y)")
     # additions of the build
     parser.add_argument("--fused", action="store_true", default=False, help="run each timestep as one device-resident call")
     parser.add_argument("--output", type=str, default="solution.pvd",
@@ -125,6 +128,19 @@ def check_particles(args):
         raise RuntimeError("--particles does not support --problem kelvinhelmholtz (particles run on the square meshes only)")
     if args.particle_every < 1:
         raise RuntimeError(f"--particle_every must be at least 1 (got {args.particle_every})")
+
+
+def check_tracers(args):
+    """Refuse a tracer count the engine does not carry, before any process is started or any engine is built."""
+    if not 1 <= args.tracers <= HDG_MAX_TRACERS:
+        raise RuntimeError(f"--tracers must be in 1 .. {HDG_MAX_TRACERS} (got {args.tracers})")
+    if args.tracers > 1 and not args.tracer_advection:
+        raise RuntimeError(f"--tracers {args.tracers} needs --tracer_advection")
+
+
+def tracer_initial(m):
+    """Initial field of tracer m: sin(2 pi (m+1) x) sin(2 pi (m+1) y); m = 0 is driver.py:342."""
+    return lambda x, y: np.sin(2 * (m + 1) * np.pi * x) * np.sin(2 * (m + 1) * np.pi * y)
 
 
 def launch_ranks(argv, nranks):
@@ -289,6 +305,7 @@ def main(argv=None):
         raise RuntimeError(f"discretisation '{args.discretisation}' is out of scope of the MI355X hot path")
     check_multi_gpu(args)
     check_particles(args)
+    check_tracers(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
     ranks = _Ranks(args)
@@ -308,21 +325,22 @@ def _run(args, ranks):
         mesh = UnitDiskMesh(refinement_level=args.refinement)  # driver.py:184-185
     else:
         mesh = UnitSquareMesh(args.nx, args.nx, quadrilateral=False)  # driver.py:181
+    several = {"n_tracers": args.tracers} if args.tracers > 1 else {}
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
         if args.timestepper != "implicit":
             raise RuntimeError(f"Invalid timestepping method for DG discretisation: '{args.timestepper}'")
         timestepper = IncompressibleEulerDGImplicit(mesh, args.degree, args.dt, flux=args.flux, callbacks=callbacks,
-                                                    device=args.device)
+                                                    device=args.device, **several)
     elif args.timestepper == "implicit":
         timestepper = IncompressibleEulerHDGImplicit(  # driver.py:220-228 (passes n_richardson: SURVEY C-1)
             mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs)
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
     elif args.timestepper in TIMESTEPPERS:
         timestepper = TIMESTEPPERS[args.timestepper](
             mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs)
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
     else:
         raise RuntimeError(f"Invalid timestepping method for HDG discretisation: '{args.timestepper}'")
 
@@ -345,6 +363,8 @@ def _run(args, ranks):
     print(f"number of Richardson iterations = {args.richardson}")
     print(f"use projection method = {args.use_projection_method}")
     print(f"advect tracer = {args.tracer_advection}")
+    if args.tracers > 1:
+        print(f"number of tracers = {args.tracers}")
     print(f"timestepping method = {timestepper.label}")
     print()
 
@@ -385,6 +405,8 @@ def _run(args, ranks):
     Q_0, p_0 = model_problem.initial_condition()
     # driver.py:340-344
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None
+    if args.tracers > 1:
+        q_0 = [tracer_initial(m) for m in range(args.tracers)]
     kw = {"fused": True} if (args.fused and args.timestepper != "implicit") else {}
     if args.diagnostics:
         kw["diagnostics"] = True
@@ -402,6 +424,12 @@ def _run(args, ranks):
         write_probes(args.probe_output, timestepper.probes)
     if args.particles and ranks.rank == 0:
         write_particles(args.particle_output, timestepper.particles)
+    if args.tracers > 1:
+        for q in timestepper.q_tracers:
+            integral = eng.integrate_pressure(q.dat.data)
+            half_sq = timestepper.compute_diagnostics(Q, p, q)["tracer_half_sq"]
+            print(f"{q.name()}: integral = {integral!r}, half square integral = {half_sq!r}")
+        print()
     log_summary()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here

@@ -92,20 +92,39 @@ class IncompressibleEuler(ABC):
         out = self._engine.project_bdm_nodal(self._as_nodal_velocity(Q))
         return Function(self._V_Q, out, "Q_star")
 
+    def _stack_tracers(self, q_initial, n_tracers):
+        """The nodal tracer block of Engine.set_tracer: one field of what _as_nodal_pressure accepts, or -- for an engine
+        with n_tracers > 1 -- a list / tuple of exactly n_tracers of them, stacked tracer-major."""
+        if n_tracers <= 1:
+            return self._as_nodal_pressure(q_initial)
+        if not isinstance(q_initial, (list, tuple)) or len(q_initial) != n_tracers:
+            got = f"{len(q_initial)} items" if isinstance(q_initial, (list, tuple)) else type(q_initial).__name__
+            raise ValueError(f"q_initial must be a list or tuple of {n_tracers} tracer fields (n_tracers = {n_tracers}), got {got}")
+        return np.stack([self._as_nodal_pressure(q) for q in q_initial])
+
+    @staticmethod
+    def _tracer_names(n_tracers):
+        return ["tracer"] if n_tracers <= 1 else [f"tracer_{m}" for m in range(n_tracers)]
+
     def _init_tracer(self, q_initial):
-        """q_initial (expression / array / None, driver.py:340-344) -> the engine's tracer state; returns whether a
-        tracer is advected."""
+        """q_initial (expression / array / None, driver.py:340-344; a list of them for several tracers) -> the engine's
+        tracer state; returns whether a tracer is advected."""
         if q_initial is None or q_initial is False:
             self._engine.set_tracer(None)
-            self.q_tracer = None
+            self.q_tracer, self.q_tracers = None, []
             return False
-        self._engine.set_tracer(self._as_nodal_pressure(q_initial))
-        self.q_tracer = Function(self._V_q, self._engine.get_tracer(), "tracer")
+        self._engine.set_tracer(self._stack_tracers(q_initial, self._engine.n_tracers))
+        self._tracer_function()
         return True
 
     def _tracer_function(self):
-        self.q_tracer = Function(self._V_q, self._engine.get_tracer(), "tracer")
-        return self.q_tracer
+        """Fetches the tracers: self.q_tracers (all of them), self.q_tracer (tracer 0); returns what the callbacks are
+        given as q_tracer=: the Function of one tracer, the list of several."""
+        n = self._engine.n_tracers
+        block = self._engine.get_tracer().reshape(n, -1)
+        self.q_tracers = [Function(self._V_q, block[m].copy(), name) for m, name in enumerate(self._tracer_names(n))]
+        self.q_tracer = self.q_tracers[0]
+        return self.q_tracer if n == 1 else self.q_tracers
 
     # -- flow diagnostics (include/hdg_mi355x.h: hdg_compute_diagnostics; DESIGN.md section 12) ----------------------
     def compute_diagnostics(self, Q, p, q=None):
@@ -174,7 +193,8 @@ class IncompressibleEuler(ABC):
                 recorders[-1][1].start(eng, nt)
         for callback in self.callbacks:
             callback.reset()
-            callback(*self._functions(*self._current(), self._callback_names), 0, q_tracer=self.q_tracer)
+            callback(*self._functions(*self._current(), self._callback_names), 0,
+                     q_tracer=self.q_tracers if len(self.q_tracers) > 1 else self.q_tracer)
         for k in range(nt):
             with PerformanceLog("timestep"):
                 t = self._advance(k, f_rhs, tracer)
@@ -188,7 +208,7 @@ class IncompressibleEuler(ABC):
         self._end_solve()
         Q, p = self._current()
         if tracer:
-            self._tracer_function()  # the final tracer field: self.q_tracer (the reference returns (Q, p) only)
+            self._tracer_function()  # the final tracer fields: self.q_tracer(s) (the reference returns (Q, p) only)
         return self._functions(Q, p, self._result_names)
 
     @abstractmethod
