@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HDG_LIB_PATH") or os.path.join(_HERE, "libhdg_mi355x.so")
 SRC = os.path.join(_HERE, "csrc", "hdg_engine.hip")
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_mi355x.h"))
+CHECKPOINT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_checkpoint.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -87,7 +88,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -174,6 +175,17 @@ SIGNATURES = {
     "hdg_advance_particles": [_h, C.c_double, C.c_int],
 }
 
+_ullp = C.POINTER(C.c_ulonglong)
+# checkpoint and restart: the symbols include/hdg_checkpoint.h declares, in a table of their own (the table above is exactly
+# include/hdg_mi355x.h); load_library walks both
+CHECKPOINT_SIGNATURES = {
+    "hdg_checkpoint_size": [_h, _lp],
+    "hdg_checkpoint_save": [_h, C.c_long, C.c_double, C.c_void_p, C.c_long],
+    "hdg_checkpoint_load": [_h, C.c_void_p, C.c_long, _lp, _dp],
+    "hdg_state_digest": [_h, _ullp],
+    "hdg_digest_vector": [_h, _dp, C.c_long, _ullp],
+}
+
 
 def load_library():
     """Load libhdg_mi355x.so; raise loudly when it has not been built."""
@@ -186,7 +198,7 @@ def load_library():
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -663,6 +675,55 @@ class Engine:
         """nsteps Heun steps of size dt through the current velocity held fixed (streamlines of a snapshot); appends one row,
         the positions reached."""
         self._ck(self.lib.hdg_advance_particles(self.h, float(dt), int(nsteps)))
+
+    # --- checkpoint and restart (include/hdg_checkpoint.h)
+    # byte offsets of the two counts in the blob header a binding needs to shape recorder rows (csrc/hdg_checkpoint.hpp: Header)
+    _CK_HEADER = "<8sIIqdQQiiQ"
+    _CK_FLAGS = (("tracer", 1), ("diagnostics", 2), ("probes", 4), ("particles", 8))
+
+    def save_checkpoint(self, step, t):
+        """The engine's whole state as bytes (between steps only); `step` and `t` come back from load_checkpoint."""
+        n = C.c_long()
+        self._ck(self.lib.hdg_checkpoint_size(self.h, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        self._ck(self.lib.hdg_checkpoint_save(self.h, int(step), float(t), buf.ctypes.data_as(C.c_void_p), n.value))
+        return buf.tobytes()
+
+    @classmethod
+    def checkpoint_info(cls, blob):
+        """What the header of a checkpoint says, without an engine: step, t, whether a tracer, diagnostics, probes and
+        particles were switched on, and the numbers of probe points and particles.  The engine validates the blob when it
+        loads it; this only reads the header (ValueError when there is none)."""
+        import struct
+        if len(blob) < struct.calcsize(cls._CK_HEADER) or bytes(blob[:8]) != b"HDGCKPT\0":
+            raise ValueError("not a checkpoint of this engine (bad magic or shorter than a header)")
+        hdr = struct.unpack_from(cls._CK_HEADER, blob, 0)
+        info = {name: bool(hdr[9] & bit) for name, bit in cls._CK_FLAGS}
+        info.update(step=int(hdr[3]), t=float(hdr[4]), n_probes=int(hdr[7]), n_particles=int(hdr[8]))
+        return info
+
+    def load_checkpoint(self, blob):
+        """Make this engine the one that wrote `blob`; returns (step, t).  Raises HDGError (HDG_ERR_ARG) naming the cause for a
+        blob of another engine or a damaged one, and then leaves the engine as it was."""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        step, t = C.c_long(), C.c_double()
+        self._ck(self.lib.hdg_checkpoint_load(self.h, buf.ctypes.data_as(C.c_void_p), len(buf), C.byref(step), C.byref(t)))
+        info = self.checkpoint_info(blob)
+        self._n_probes, self._n_particles = info["n_probes"], info["n_particles"]  # the shapes of probes() / particles()
+        return step.value, t.value
+
+    def state_digest(self):
+        """(d0, d1): 16 bytes that say whether two engines are in the same state (hdg_state_digest)."""
+        out = (C.c_ulonglong * 2)()
+        self._ck(self.lib.hdg_state_digest(self.h, out))
+        return int(out[0]), int(out[1])
+
+    def digest_vector(self, v):
+        """(d0, d1) of the 64-bit patterns of v, computed by the device kernel (hdg_digest_vector)."""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        out = (C.c_ulonglong * 2)()
+        self._ck(self.lib.hdg_digest_vector(self.h, _ptr(v) if v.size else None, v.size, out))
+        return int(out[0]), int(out[1])
 
     def time_kernel(self, kernel, reps):
         ms = C.c_double()

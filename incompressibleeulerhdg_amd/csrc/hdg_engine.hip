@@ -22,11 +22,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/hdg_mi355x.h"
+#include "../../include/hdg_checkpoint.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -46,6 +48,8 @@
 #include "hdg_probes.hpp"
 #include "hdg_particles.hpp"
 #include "hdg_row_log.hpp"
+#include "hdg_checkpoint.hpp"
+#include "hdg_digest.hpp"
 
 namespace hdg {
 
@@ -433,6 +437,9 @@ struct Engine {
   }
   void construct_general(const hdg_config& c, int nv, const double* coords, int nc, const int* cells) {
     general = true;
+    ck_mesh_nv = nv; ck_mesh_nc = nc;
+    ck_mesh_coords = ckpt::digest_bytes(coords, sizeof(double) * 2 * (size_t)nv);
+    ck_mesh_cells = ckpt::digest_bytes(cells, sizeof(int) * 3 * (size_t)nc);
     K = c.degree; s = c.nstages;
     NU = n_scalar(K + 1); NP = n_scalar(K); NL = K + 1; NE = K + 2; NX = 2 * NU + NP;
     // solvers of this path: GMRES(m) with the element block-Jacobi, CG with the edge block-Jacobi (the two-level
@@ -3877,6 +3884,7 @@ struct Engine {
   PointSet pt_eval, pt_probe;
   GLocator* glocator = nullptr;
   RowLog probe_log;
+  std::vector<double> pt_probe_xy;
   double *pt_out = nullptr, *pt_rows = nullptr;
   long pt_out_alloc = 0;
   // located[i] = 1 / 0; throws nothing for an outside point (PT_OUTSIDE)
@@ -3939,6 +3947,7 @@ struct Engine {
   void probe_set(int n, const double* xy, int cap) {
     if (n < 0 || cap < 0) throw std::string("probes: n and capacity must be >= 0");
     probe_log.reset(0, 0);
+    pt_probe_xy.clear();
     if (n == 0 || cap == 0) { pt_probe.n = 0; return; }
     if ((double)n * cap * POINT_NCOL > (double)HDG_MAX_PROBE_VALUES)
       throw std::string("probes: ") + std::to_string(n) + " points x " + std::to_string(cap) + " rows x " +
@@ -3952,6 +3961,7 @@ struct Engine {
             std::to_string(xy[2 * (size_t)t + 1]) + ") lies outside the domain";
       }
     log_size(probe_log, pt_rows, (long)POINT_NCOL * n, cap);
+    pt_probe_xy.assign(xy, xy + 2 * (size_t)n);  // a checkpoint stores the points; a load locates them again
     probe_record();  // row 0: the state as it is now
   }
 
@@ -4063,6 +4073,346 @@ struct Engine {
     diag_record();
     probe_record();
     particles_step();
+  }
+
+  // ------------------------------------------------------------------ checkpoint and restart (hdg_checkpoint.hpp)
+  // After checkpoint_load the engine is the engine that was saved: every vector a later step or getter reads before it is
+  // written, stored raw (ghost and padding rows included) BY ROLE -- begin_step exchanges stQ[0] and curQ, the Chebyshev
+  // iteration Qtent[i] and chd -- plus the host history of the solvers and the three row logs.  Timers and the launch census are
+  // not state: they start at zero.  Tables built from the configuration alone (ensure_dinv, get_pset, the dense V-cycle tails,
+  // the matrix-core packs, estimate_cheb with its fixed seed) are set-up: a restored engine builds them again on first use.
+  bool step_open = false;  // between hdg_begin_step and the end of the step: no save
+  int ck_mesh_nv = 0, ck_mesh_nc = 0;
+  ckpt::Digest ck_mesh_coords, ck_mesh_cells;
+  unsigned long long *dig_part = nullptr, *dig_out = nullptr;
+  static constexpr int DIG_SLOTS = 256;  // results of one batch of digests (one per section)
+  // digest of the n doubles at v (device) into result slot `slot`: two launches on the stream, no synchronisation
+  void digest_launch(const double* v, long n, int slot) {
+    if (n < 0 || slot < 0 || slot >= DIG_SLOTS) throw std::string("digest: bad arguments");
+    if (n > 0 && (!v || (reinterpret_cast<uintptr_t>(v) & 15))) throw std::string("digest: the vector must be 16-byte aligned");
+    if (!dig_part) {
+      dig_part = reinterpret_cast<unsigned long long*>(dalloc(2L * HDG_DIGEST_MAX_BLOCKS));
+      dig_out = reinterpret_cast<unsigned long long*>(dalloc(2L * DIG_SLOTS));
+    }
+    const int nb = (int)std::min<long>(vec_blocks(n), HDG_DIGEST_MAX_BLOCKS);
+    tally(LC_OTHER, 8.0 * (double)n);
+    k_digest<<<nb, HDG_DIGEST_BLOCK, 0, stream>>>(n, reinterpret_cast<const unsigned long long*>(v), dig_part);
+    tally(LC_OTHER, 0.0);
+    k_digest_final<<<1, HDG_DIGEST_BLOCK, 0, stream>>>(nb, dig_part, dig_out + 2 * slot);
+  }
+  void digest_fetch(int nslots, std::vector<ckpt::Digest>& out) {
+    std::vector<unsigned long long> h(2 * (size_t)std::max(nslots, 1), 0ULL);
+    if (nslots > 0) HIPCHECK(hipMemcpyAsync(h.data(), dig_out, sizeof(unsigned long long) * 2 * (size_t)nslots, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    out.resize((size_t)nslots);
+    for (int q = 0; q < nslots; q++) { out[(size_t)q].d0 = h[2 * (size_t)q]; out[(size_t)q].d1 = h[2 * (size_t)q + 1]; }
+  }
+  // hdg_digest_vector: a host vector through the device kernel (operator hook)
+  void digest_host_vector(const double* v, long n, unsigned long long* out) {
+    if (n < 0 || (n > 0 && !v) || !out) throw std::string("digest: bad arguments");
+    double* d = dalloc(n);
+    if (n > 0) HIPCHECK(hipMemcpyAsync(d, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
+    digest_launch(d, n, 0);
+    std::vector<ckpt::Digest> r;
+    digest_fetch(1, r);
+    dfree(d);
+    out[0] = r[0].d0; out[1] = r[0].d1;
+  }
+
+  // the host part of the state
+  struct CkHost {
+    std::vector<double> ch_lmin, ch_lmax, ch_widen, bscale;
+    std::vector<long> ch_count;
+    std::vector<int> ch_last, ch_hand, bsep;
+    std::vector<char> ch_slow;
+    double it_sum[4] = {0, 0, 0, 0};
+    long it_cnt[4] = {0, 0, 0, 0}, ev[4] = {0, 0, 0, 0};
+    double trace_scale = 0.0;
+    int tracer_on = 0, tracer_vecs = 0, has_chd = 0;
+    long log[3][4] = {{0}};  // width, cap, n, dropped of the diagnostics, probe and particle logs
+    std::vector<double> probe_xy;
+    int pa_n = 0, pa_every = 1;
+    long pa_steps = 0;
+  };
+  CkHost ck_capture() const {
+    CkHost h;
+    h.ch_lmin = ch_lmin; h.ch_lmax = ch_lmax; h.ch_widen = ch_widen; h.ch_count = ch_count; h.ch_last = ch_last;
+    h.ch_hand = ch_hand; h.ch_slow = ch_slow; h.bscale = bscale; h.bsep = bsep;
+    for (int q = 0; q < 4; q++) { h.it_sum[q] = it_sum[q]; h.it_cnt[q] = it_cnt[q]; }
+    h.ev[0] = ev_cg_replacements; h.ev[1] = ev_cg_floor_exits; h.ev[2] = n_sstep_cycles; h.ev[3] = n_sstep_fallbacks;
+    h.trace_scale = trace_scale;
+    // Only what can be observed is state: the tracer vectors while a tracer is on (switched off, nothing reads them before
+    // hdg_set_tracer has written them again), a row log while it records (switched off, its width is what the last user left).
+    // So a run that recorded diagnostics and a run that did not end in the same state, with the same digest.
+    h.tracer_on = tracer_on ? 1 : 0; h.tracer_vecs = tracer_on ? 1 : 0; h.has_chd = chd ? 1 : 0;
+    const RowLog* L[3] = {&diag_log, &probe_log, &pa_log};
+    for (int q = 0; q < 3; q++)
+      if (L[q]->cap > 0) { h.log[q][0] = L[q]->width; h.log[q][1] = L[q]->cap; h.log[q][2] = L[q]->n; h.log[q][3] = L[q]->dropped; }
+    if (pt_probe.n > 0) h.probe_xy = pt_probe_xy;
+    h.pa_n = pa_n; h.pa_every = pa_every; h.pa_steps = pa_steps;
+    return h;
+  }
+  static void ck_write_host(const CkHost& h, ckpt::ByteWriter& solver, ckpt::ByteWriter& outputs) {
+    solver.vec(h.ch_lmin); solver.vec(h.ch_lmax); solver.vec(h.ch_widen); solver.vec(h.ch_count); solver.vec(h.ch_last);
+    solver.vec(h.ch_hand); solver.vec(h.ch_slow); solver.vec(h.bscale); solver.vec(h.bsep);
+    solver.raw(h.it_sum, sizeof(h.it_sum)); solver.raw(h.it_cnt, sizeof(h.it_cnt)); solver.raw(h.ev, sizeof(h.ev));
+    solver.put(h.trace_scale); solver.put(h.tracer_on); solver.put(h.tracer_vecs); solver.put(h.has_chd);
+    outputs.raw(h.log, sizeof(h.log)); outputs.vec(h.probe_xy); outputs.put(h.pa_n); outputs.put(h.pa_every); outputs.put(h.pa_steps);
+  }
+  // empty return: read; otherwise what is wrong with the record
+  std::string ck_read_host(CkHost& h, const void* solver, size_t ns, const void* outputs, size_t no) const {
+    ckpt::ByteReader a(solver, ns), b(outputs, no);
+    a.vec(h.ch_lmin); a.vec(h.ch_lmax); a.vec(h.ch_widen); a.vec(h.ch_count); a.vec(h.ch_last);
+    a.vec(h.ch_hand); a.vec(h.ch_slow); a.vec(h.bscale); a.vec(h.bsep);
+    a.raw(h.it_sum, sizeof(h.it_sum)); a.raw(h.it_cnt, sizeof(h.it_cnt)); a.raw(h.ev, sizeof(h.ev));
+    h.trace_scale = a.get<double>(); h.tracer_on = a.get<int>(); h.tracer_vecs = a.get<int>(); h.has_chd = a.get<int>();
+    if (!a.done()) return "section 'solver': the record does not have the length its fields need";
+    b.raw(h.log, sizeof(h.log)); b.vec(h.probe_xy); h.pa_n = b.get<int>(); h.pa_every = b.get<int>(); h.pa_steps = b.get<long>();
+    if (!b.done()) return "section 'outputs': the record does not have the length its fields need";
+    const size_t nh = h.ch_lmin.size();
+    if ((nh != 0 && nh != (size_t)s + 1) || h.ch_lmax.size() != nh) return "section 'solver': Chebyshev bounds of another stage count";
+    for (size_t n : {h.ch_widen.size(), h.ch_count.size(), h.ch_last.size(), h.ch_hand.size(), h.ch_slow.size()})
+      if (n != 0 && n != (size_t)s + 1) return "section 'solver': Chebyshev history of another stage count";
+    if (h.bscale.size() != (size_t)s + 1 || h.bsep.size() != (size_t)s + 1) return "section 'solver': forcing scales of another stage count";
+    for (int q = 0; q < 3; q++)
+      if (h.log[q][0] < 0 || h.log[q][1] < 0 || h.log[q][2] < 0 || h.log[q][2] > h.log[q][1] || h.log[q][3] < 0 ||
+          (double)h.log[q][0] * (double)h.log[q][1] > 4.0 * (double)HDG_MAX_PROBE_VALUES)
+        return "section 'outputs': row log " + std::to_string(q) + " has impossible counts";
+    if (h.pa_n < 0 || h.pa_every < 1 || h.pa_steps < 0 || (h.pa_n > 0 && h.log[2][0] != 2L * h.pa_n)) return "section 'outputs': particle counts";
+    if (h.pa_n > 0 && general) return "section 'outputs': particles on a general mesh";
+    if (h.probe_xy.size() % 2 != 0 || (!h.probe_xy.empty() && h.log[1][0] != (long)POINT_NCOL * (long)(h.probe_xy.size() / 2)))
+      return "section 'outputs': probe points do not match the width of the probe log";
+    if (h.tracer_vecs && comm->size > 1) return "section 'solver': a tracer on a strip partition";
+    return "";
+  }
+  // the device sections of a state whose host part is hs, in blob order; ptr() is called once the vectors exist
+  struct CkDev { std::string id; long n; std::function<double*()> ptr; };
+  std::vector<CkDev> ck_device_sections(const CkHost& hs) {
+    std::vector<CkDev> v;
+    auto add = [&](const std::string& id, long n, std::function<double*()> f) { v.push_back(CkDev{id, n, std::move(f)}); };
+    auto idx = [](const char* base, int i) { return std::string(base) + std::to_string(i); };
+    add("curQ", NQ, [this] { return curQ; }); add("curP", NPv, [this] { return curP; }); add("curL", NLv, [this] { return curL; });
+    for (int i = 0; i < s; i++) {
+      add(idx("stQ", i), NQ, [this, i] { return stQ[(size_t)i]; });
+      add(idx("stP", i), NPv, [this, i] { return stP[(size_t)i]; });
+      add(idx("stL", i), NLv, [this, i] { return stL[(size_t)i]; });
+      add(idx("Qtent", i), NQ, [this, i] { return Qtent[(size_t)i]; });
+    }
+    for (int i = 0; i < (int)Qstar.size(); i++) add(idx("Qstar", i), NQ, [this, i] { return Qstar[(size_t)i]; });
+    for (int i = 0; i <= s; i++) add(idx("brhs", i), NQ, [this, i] { return brhs[(size_t)i]; });
+    add("profile", NQ, [this] { return profile; });
+    add("updU", NQ, [this] { return updU; }); add("updP", NPv, [this] { return updP; }); add("updL", NLv, [this] { return updL; });
+    add("recP", NPv, [this] { return recP; }); add("recL", NLv, [this] { return recL; });
+    if (hs.has_chd) add("chd", NQ, [this] { return chd; });
+    if (comm->size > 1) {
+      // Strips: the work vectors of the solvers are state as well.  A stencil writes as many ghost rows as its inputs allow and
+      // leaves the rest of a work vector as earlier solves left it; the whole-array updates (x += V y, the s-step update)
+      // carry those stale rows into the ghost rows of Qtent[i] and from there into stQ[i].  No owned value ever depends on
+      // them (the bookkeeping exchanges before a stencil reads), but the raw vectors, and with them the state digest, do.
+      // On one rank there is nothing to carry: ghost rows are never written (unit square) or rewritten by the wrap before
+      // every use (periodic square).
+      add("wQ1", NQ, [this] { return wQ1; }); add("wQ2", NQ, [this] { return wQ2; });
+      add("wQ3", NQ, [this] { return wQ3; }); add("wQ4", NQ, [this] { return wQ4; });
+      for (int i = 0; i < (int)gm_V.size(); i++) add(idx("gm_V", i), NQ, [this, i] { return gm_V[(size_t)i]; });
+      add("wP1", NPv, [this] { return wP1; }); add("wL1", NLv, [this] { return wL1; }); add("wL2", NLv, [this] { return wL2; });
+      add("cg_r", NLv, [this] { return cg_r; }); add("cg_z", NLv, [this] { return cg_z; }); add("cg_p", NLv, [this] { return cg_p; });
+      add("cg_Ap", NLv, [this] { return cg_Ap; }); add("ch_d", NLv, [this] { return ch_d; }); add("ch_r", NLv, [this] { return ch_r; });
+    }
+    if (hs.tracer_vecs) {
+      add("q_cur", NTv(), [this] { return q_cur; }); add("q_fin", NTv(), [this] { return q_fin; });
+      for (int i = 0; i < s; i++) add(idx("q_st", i), NTv(), [this, i] { return q_st[(size_t)i]; });
+    }
+    if (hs.pa_n > 0) {
+      add("pa_X", 2L * hs.pa_n, [this] { return pa_X; }); add("pa_Xs", 2L * hs.pa_n, [this] { return pa_Xs; });
+      add("pa_k1", 2L * hs.pa_n, [this] { return pa_k1; });
+      if (comm->size > 1) add("pa_k2", 2L * hs.pa_n, [this] { return pa_k2; });
+      add("pa_cnt", PARTICLE_NCOUNT, [this] { return pa_cnt; });
+    }
+    // the rows written so far
+    if (hs.log[0][2] > 0) add("diag_rows", hs.log[0][0] * hs.log[0][2], [this] { return diag_rows; });
+    if (hs.log[1][2] > 0) add("probe_rows", hs.log[1][0] * hs.log[1][2], [this] { return pt_rows; });
+    if (hs.log[2][2] > 0) add("particle_rows", hs.log[2][0] * hs.log[2][2], [this] { return pa_rows; });
+    if ((int)v.size() > DIG_SLOTS) throw std::string("checkpoint: too many sections");
+    return v;
+  }
+  // what a checkpoint is bound to.  hdg_config::device is left out: where a run is computed is not part of what it computes
+  ckpt::Fingerprint ck_fingerprint() const {
+    ckpt::Fingerprint f;
+    f.add("engine_kind", (long)(general ? 2 : (comm->size > 1 ? 1 : 0)));  // hdg_create / hdg_create_distributed / hdg_create_general
+    f.add("mesh_kind", (long)(general ? 2 : (periodic ? 1 : 0)));
+    f.add("nx", (long)cfg.nx); f.add("ny", (long)cfg.ny); f.add("degree", (long)cfg.degree); f.add("dt", cfg.dt);
+    f.add("flux_upwind", (long)cfg.flux_upwind); f.add("use_projection", (long)cfg.use_projection);
+    f.add("n_richardson", (long)cfg.n_richardson); f.add("tau", cfg.tau); f.add("alpha_penalty", cfg.alpha_penalty);
+    f.add("nstages", (long)cfg.nstages);
+    auto arr = [&](const char* name, const double* a, int n) { for (int q = 0; q < n; q++) f.add(std::string(name) + "[" + std::to_string(q) + "]", a[q]); };
+    arr("a_expl", cfg.a_expl, HDG_MAX_STAGES * HDG_MAX_STAGES); arr("a_impl", cfg.a_impl, HDG_MAX_STAGES * HDG_MAX_STAGES);
+    arr("b_expl", cfg.b_expl, HDG_MAX_STAGES); arr("b_impl", cfg.b_impl, HDG_MAX_STAGES + 1); arr("c_expl", cfg.c_expl, HDG_MAX_STAGES);
+    f.add("equispaced_nodes", (long)cfg.equispaced_nodes); f.add("tent_rtol", cfg.tent_rtol); f.add("tent_maxit", (long)cfg.tent_maxit);
+    f.add("gmres_restart", (long)cfg.gmres_restart); f.add("tent_precond", (long)cfg.tent_precond); f.add("tent_solver", (long)cfg.tent_solver);
+    f.add("trace_rtol", cfg.trace_rtol); f.add("trace_maxit", (long)cfg.trace_maxit); f.add("trace_precond", (long)cfg.trace_precond);
+    f.add("unsplit_rtol", cfg.unsplit_rtol); f.add("unsplit_inner_rtol", cfg.unsplit_inner_rtol);
+    f.add("unsplit_restart", (long)cfg.unsplit_restart); f.add("unsplit_maxit", (long)cfg.unsplit_maxit);
+    f.add("periodic", (long)cfg.periodic); f.add("length", cfg.length);
+    f.add("dg_rtol", cfg.dg_rtol); f.add("dg_restart", (long)cfg.dg_restart); f.add("dg_maxit", (long)cfg.dg_maxit);
+    f.add("n_tracers", (long)cfg.n_tracers);
+    if (general) {
+      f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
+      f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
+      f.add_u64("cells_d0", ck_mesh_cells.d0); f.add_u64("cells_d1", ck_mesh_cells.d1);
+    }
+    f.add("rank", (long)comm->rank); f.add("nranks", (long)comm->size);
+    f.add("NQ", NQ); f.add("NPv", NPv); f.add("NLv", NLv);
+    f.add("rows", (long)g.R); f.add("row_pitch", (long)g.P);  // the row padding (HDG_ROW_PAD or the channel rule)
+    return f;
+  }
+  struct CkPlan {
+    CkHost hs;
+    std::vector<CkDev> dev;
+    ckpt::ByteWriter hb[2];
+    std::vector<ckpt::Section> secs;  // device sections, then 'solver' and 'outputs'
+    std::string fp;
+    uint64_t total = 0;
+  };
+  CkPlan ck_plan() {
+    CkPlan P;
+    P.hs = ck_capture();
+    P.dev = ck_device_sections(P.hs);
+    ck_write_host(P.hs, P.hb[0], P.hb[1]);
+    for (const CkDev& d : P.dev) {
+      ckpt::Section sc;
+      sc.id = d.id; sc.kind = ckpt::DEVICE_DOUBLES; sc.length = (uint64_t)d.n;
+      P.secs.push_back(sc);
+    }
+    const char* names[2] = {"solver", "outputs"};
+    for (int q = 0; q < 2; q++) {
+      ckpt::Section sc;
+      sc.id = names[q]; sc.kind = ckpt::HOST_BYTES; sc.length = P.hb[q].b.size();
+      sc.digest = ckpt::digest_bytes(P.hb[q].b.data(), P.hb[q].b.size());
+      P.secs.push_back(sc);
+    }
+    P.fp = ck_fingerprint().text();
+    P.total = ckpt::layout(P.fp, P.secs);
+    return P;
+  }
+  void ck_refuse_open_step() const {
+    if (step_open)
+      throw std::string("checkpoint: a step is open (between hdg_begin_step and the end of the step); a save is valid between steps only");
+  }
+  long checkpoint_size() {
+    ck_refuse_open_step();
+    return (long)ck_plan().total;
+  }
+  void checkpoint_save(long step, double t, void* buf, long nbytes) {
+    ck_refuse_open_step();
+    if (!buf) throw std::string("checkpoint: no buffer");
+    CkPlan P = ck_plan();
+    if ((uint64_t)nbytes != P.total)
+      throw std::string("checkpoint: byte count: the buffer has ") + std::to_string(nbytes) + " bytes, the state needs " +
+          std::to_string(P.total) + " (hdg_checkpoint_size)";
+    unsigned char* c = static_cast<unsigned char*>(buf);
+    // every device section: digest on the device, download, check the downloaded bytes against that digest
+    for (size_t q = 0; q < P.dev.size(); q++) {
+      const double* p = P.dev[q].ptr();
+      digest_launch(p, P.dev[q].n, (int)q);
+      if (P.dev[q].n > 0) HIPCHECK(hipMemcpyAsync(c + P.secs[q].offset, p, sizeof(double) * (size_t)P.dev[q].n, hipMemcpyDeviceToHost, stream));
+    }
+    std::vector<ckpt::Digest> dd;
+    digest_fetch((int)P.dev.size(), dd);
+    for (size_t q = 0; q < P.dev.size(); q++) {
+      if (ckpt::digest_words(c + P.secs[q].offset, (uint64_t)P.dev[q].n) != dd[q])
+        throw std::string("checkpoint: section '") + P.dev[q].id + "': the downloaded bytes do not match the digest taken on the device";
+      P.secs[q].digest = dd[q];
+    }
+    for (int q = 0; q < 2; q++)
+      if (!P.hb[q].b.empty()) std::memcpy(c + P.secs[P.dev.size() + (size_t)q].offset, P.hb[q].b.data(), P.hb[q].b.size());
+    const uint64_t flags = (P.hs.tracer_on ? ckpt::FLAG_TRACER : 0) | (P.hs.log[0][1] > 0 ? ckpt::FLAG_DIAGNOSTICS : 0) |
+                           (P.hs.log[1][1] > 0 ? ckpt::FLAG_PROBES : 0) | (P.hs.pa_n > 0 ? ckpt::FLAG_PARTICLES : 0);
+    ckpt::write_front(buf, P.total, step, t, (int)(P.hs.probe_xy.size() / 2), P.hs.pa_n, flags, P.fp, P.secs);
+  }
+  void state_digest(unsigned long long* out) {
+    if (!out) throw std::string("null argument");
+    ck_refuse_open_step();
+    CkPlan P = ck_plan();
+    for (size_t q = 0; q < P.dev.size(); q++) digest_launch(P.dev[q].ptr(), P.dev[q].n, (int)q);
+    std::vector<ckpt::Digest> dd;
+    digest_fetch((int)P.dev.size(), dd);
+    for (int q = 0; q < 2; q++) dd.push_back(P.secs[P.dev.size() + (size_t)q].digest);
+    const ckpt::Digest d = ckpt::digest_of_digests(dd);
+    out[0] = d.d0; out[1] = d.d1;
+  }
+  void ck_restore_log(RowLog& L, double*& rows, const long* rec) {
+    log_size(L, rows, rec[0], rec[1]);
+    L.n = rec[2]; L.dropped = rec[3];
+  }
+  void checkpoint_load(const void* buf, long nbytes, long* step, double* t) {
+    // ---- everything is validated before the engine is touched
+    if (nbytes < 0) throw std::string("checkpoint: negative byte count");
+    ckpt::Parsed B;
+    const std::string perr = ckpt::parse(buf, (uint64_t)nbytes, B);
+    if (!perr.empty()) throw "checkpoint: " + perr;
+    const std::string fdiff = ck_fingerprint().difference(ckpt::Fingerprint::parse(B.fingerprint));
+    if (!fdiff.empty()) throw "checkpoint: " + fdiff;
+    const unsigned char* c = static_cast<const unsigned char*>(buf);
+    const ckpt::Section *hsolver = nullptr, *houtputs = nullptr;
+    for (const ckpt::Section& sc : B.sections) {
+      if (sc.kind == ckpt::HOST_BYTES && sc.id == "solver") hsolver = &sc;
+      if (sc.kind == ckpt::HOST_BYTES && sc.id == "outputs") houtputs = &sc;
+    }
+    if (!hsolver) throw std::string("checkpoint: section 'solver' is missing");
+    if (!houtputs) throw std::string("checkpoint: section 'outputs' is missing");
+    CkHost hs;
+    const std::string herr = ck_read_host(hs, c + hsolver->offset, (size_t)hsolver->length, c + houtputs->offset, (size_t)houtputs->length);
+    if (!herr.empty()) throw "checkpoint: " + herr;
+    std::vector<CkDev> dev = ck_device_sections(hs);
+    if (B.sections.size() != dev.size() + 2)
+      throw std::string("checkpoint: ") + std::to_string(B.sections.size()) + " sections in the table, this state has " + std::to_string(dev.size() + 2);
+    for (size_t q = 0; q < dev.size(); q++) {
+      const ckpt::Section& sc = B.sections[q];
+      if (sc.id != dev[q].id || sc.kind != ckpt::DEVICE_DOUBLES)
+        throw std::string("checkpoint: section ") + std::to_string(q) + " is '" + sc.id + "' where this engine expects '" + dev[q].id + "'";
+      if (sc.length != (uint64_t)dev[q].n)
+        throw std::string("checkpoint: section '") + sc.id + "' holds " + std::to_string(sc.length) + " values, this engine's has " + std::to_string(dev[q].n);
+    }
+    // ---- the engine becomes the saved one
+    if (hs.tracer_vecs) { cg_setup(); tracer_alloc(); }
+    if (hs.has_chd && !chd) chd = dalloc(NQ);
+    ch_lmin = hs.ch_lmin; ch_lmax = hs.ch_lmax; ch_widen = hs.ch_widen; ch_count = hs.ch_count; ch_last = hs.ch_last;
+    ch_hand = hs.ch_hand; ch_slow = hs.ch_slow; bscale = hs.bscale; bsep = hs.bsep;
+    for (int q = 0; q < 4; q++) { it_sum[q] = hs.it_sum[q]; it_cnt[q] = hs.it_cnt[q]; }
+    ev_cg_replacements = hs.ev[0]; ev_cg_floor_exits = hs.ev[1]; n_sstep_cycles = hs.ev[2]; n_sstep_fallbacks = hs.ev[3];
+    trace_scale = hs.trace_scale;
+    tracer_on = hs.tracer_on != 0;
+    ck_restore_log(diag_log, diag_rows, hs.log[0]);
+    if (!hs.probe_xy.empty()) {  // located again, by the code hdg_set_probes uses
+      points_locate((int)(hs.probe_xy.size() / 2), hs.probe_xy.data(), pt_probe, nullptr);
+      pt_probe_xy = hs.probe_xy;
+    } else { pt_probe.n = 0; pt_probe_xy.clear(); }
+    ck_restore_log(probe_log, pt_rows, hs.log[1]);
+    particles_off();
+    if (hs.pa_n > 0) {
+      pa_X = dalloc(2L * hs.pa_n); pa_Xs = dalloc(2L * hs.pa_n); pa_k1 = dalloc(2L * hs.pa_n);
+      if (comm->size > 1) pa_k2 = dalloc(2L * hs.pa_n);
+      pa_cnt = dalloc(PARTICLE_NCOUNT);
+      pa_n = hs.pa_n; pa_every = hs.pa_every; pa_steps = hs.pa_steps;
+    }
+    ck_restore_log(pa_log, pa_rows, hs.log[2]);
+    // upload, digest again on the device, compare with the table
+    for (size_t q = 0; q < dev.size(); q++) {
+      double* p = dev[q].ptr();
+      if (dev[q].n > 0) HIPCHECK(hipMemcpyAsync(p, c + B.sections[q].offset, sizeof(double) * (size_t)dev[q].n, hipMemcpyHostToDevice, stream));
+      digest_launch(p, dev[q].n, (int)q);
+    }
+    std::vector<ckpt::Digest> dd;
+    digest_fetch((int)dev.size(), dd);
+    for (size_t q = 0; q < dev.size(); q++)
+      if (dd[q] != B.sections[q].digest)
+        throw std::string("checkpoint: section '") + dev[q].id + "': the uploaded vector does not match the digest in the table";
+    step_open = false;
+    // timers and the launch census are not state
+    for (int q = 0; q < HDG_N_TIMERS; q++) { tm_total[q] = 0; tm_sumsq[q] = 0; tm_calls[q] = 0; }
+    for (int q = 0; q < HDG_N_LAUNCH_CLASSES; q++) { lc_calls[q] = 0; lc_bytes[q] = 0.0; }
+    if (step) *step = (long)B.header.step;
+    if (t) *t = B.header.t;
   }
 
   // ------------------------------------------------------------------ host <-> device fields
@@ -4433,6 +4783,7 @@ int hdg_project_bdm_nodal(hdg_handle* h, const double* Qin, double* Qout) {
 }
 int hdg_begin_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
+  E.step_open = true;  // no checkpoint until the step is complete
   E.begin_step();
   HDG_API_END(h)
 }
@@ -4471,13 +4822,14 @@ int hdg_stage_update(hdg_handle* h, int stage) {
 int hdg_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.finish_step();
-  if (!E.tracer_on) E.end_of_step();  // with a tracer the rows are taken after hdg_tracer_finish_step
+  if (!E.tracer_on) { E.end_of_step(); E.step_open = false; }  // with a tracer the rows are taken after hdg_tracer_finish_step
   HDG_API_END(h)
 }
 int hdg_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.step();
   E.end_of_step();
+  E.step_open = false;  // a whole step: complete
   HDG_API_END(h)
 }
 int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
@@ -4487,6 +4839,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
     for (int sl = 0; sl <= E.s; sl++) { E.bscale[sl] = scales[(long)n * (E.s + 1) + sl]; E.bsep[sl] = 1; }
     E.step();
     E.end_of_step();
+    E.step_open = false;
     E.harvest_completed();  // keeps the number of live timer events bounded over a long run
   }
   HDG_API_END(h)
@@ -4495,6 +4848,7 @@ int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure) {
   HDG_API_BEGIN(h)
   E.implicit_step(its_tentative, its_pressure);
   E.end_of_step();
+  E.step_open = false;  // a whole step: complete
   HDG_API_END(h)
 }
 // ---- implicit DG discretisation (dg_implicit.py:10-136), single rank
@@ -4510,6 +4864,7 @@ int hdg_dg_implicit_step(hdg_handle* h, int* its) {
   HDG_API_BEGIN(h)
   E.dg_implicit_step(its);
   E.end_of_step();
+  E.step_open = false;  // a whole step: complete
   HDG_API_END(h)
 }
 int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
@@ -4616,6 +4971,7 @@ int hdg_get_tracer(hdg_handle* h, double* q) {
 }
 int hdg_tracer_begin_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
+  E.step_open = true;
   E.tracer_begin_step();
   HDG_API_END(h)
 }
@@ -4627,7 +4983,7 @@ int hdg_tracer_stage(hdg_handle* h, int stage) {
 int hdg_tracer_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.tracer_finish_step();
-  if (E.tracer_on) E.end_of_step();
+  if (E.tracer_on) { E.end_of_step(); E.step_open = false; }
   HDG_API_END(h)
 }
 int hdg_cg_size(hdg_handle* h, long* n_cg) {
@@ -4793,6 +5149,34 @@ int hdg_time_kernel(hdg_handle* h, int kernel, int reps, double* ms_per_launch) 
   HDG_API_BEGIN(h)
   if (reps < 1 || !ms_per_launch) throw std::string("bad arguments");
   *ms_per_launch = E.time_kernel(kernel, reps);
+  HDG_API_END(h)
+}
+
+// ---- checkpoint and restart (include/hdg_checkpoint.h)
+int hdg_checkpoint_size(hdg_handle* h, long* nbytes) {
+  HDG_API_BEGIN(h)
+  if (!nbytes) throw std::string("null argument");
+  *nbytes = E.checkpoint_size();
+  HDG_API_END(h)
+}
+int hdg_checkpoint_save(hdg_handle* h, long step, double t, void* buf, long nbytes) {
+  HDG_API_BEGIN(h)
+  E.checkpoint_save(step, t, buf, nbytes);
+  HDG_API_END(h)
+}
+int hdg_checkpoint_load(hdg_handle* h, const void* buf, long nbytes, long* step, double* t) {
+  HDG_API_BEGIN(h)
+  E.checkpoint_load(buf, nbytes, step, t);
+  HDG_API_END(h)
+}
+int hdg_state_digest(hdg_handle* h, unsigned long long out[2]) {
+  HDG_API_BEGIN(h)
+  E.state_digest(out);
+  HDG_API_END(h)
+}
+int hdg_digest_vector(hdg_handle* h, const double* v, long n, unsigned long long out[2]) {
+  HDG_API_BEGIN(h)
+  E.digest_host_vector(v, n, out);
   HDG_API_END(h)
 }
 

@@ -12,6 +12,11 @@ the CG vorticity, callbacks.py:30-85) and ``--tracer_advection`` (driver.py:340-
 ``--particles FILE`` advects Lagrangian particles through the two structured problems on the device
 and writes their positions to ``--particle_output`` (``particles.npz``).
 
+``--checkpoint FILE`` writes the engine's whole state after every ``--checkpoint_every``-th step and after the last one;
+``--restart FILE`` continues such a file to ``--tfinal``: the same run, bit for bit.  With ``--gpus N``
+each rank writes and reads ``FILE.<rank>``.  The final printout carries ``state digest``, 16 bytes that are equal exactly when
+two runs ended in the same engine state.
+
 ``--gpus N`` (N > 1) runs the two structured problems on N strips (one process per rank, include/hdg_mi355x.h:
 hdg_create_distributed): the driver starts ``python -m torch.distributed.run --nproc-per-node=N`` with the same arguments
 as a child process and returns its exit status.  Each rank chooses RCCL when every rank has a device of its own and the
@@ -96,6 +101,13 @@ def build_parser():
                         help="file the --particles positions are written to (t, xy (rows, n, 2), clamped, lost)")
     parser.add_argument("--particle_every", metavar="M", type=int, default=1,
                         help="record the particle positions every M-th step (they move every step)")
+    parser.add_argument("--checkpoint", metavar="FILE", type=str, default=None,
+                        help="write the engine's whole state to FILE after every --checkpoint_every-th step and after the last "
+                             "one (--gpus N: FILE.<rank>)")
+    parser.add_argument("--checkpoint_every", metavar="M", type=int, default=None,
+                        help="with --checkpoint: write after every M-th step (default: after the last step only)")
+    parser.add_argument("--restart", metavar="FILE", type=str, default=None,
+                        help="continue the run whose --checkpoint FILE this is, to --tfinal")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -136,6 +148,25 @@ def check_tracers(args):
         raise RuntimeError(f"--tracers must be in 1 .. {HDG_MAX_TRACERS} (got {args.tracers})")
     if args.tracers > 1 and not args.tracer_advection:
         raise RuntimeError(f"--tracers {args.tracers} needs --tracer_advection")
+
+
+def check_checkpoint(args):
+    """Refuse a checkpoint request that cannot be served, before any process is started or any engine is built."""
+    if args.checkpoint_every is not None:
+        if args.checkpoint_every < 1:
+            raise RuntimeError(f"--checkpoint_every must be at least 1 (got {args.checkpoint_every})")
+        if not args.checkpoint:
+            raise RuntimeError("--checkpoint_every needs --checkpoint")
+    if not args.restart:
+        return
+    for bad, what in ((args.warmup, "--warmup (one step from the initial condition)"),
+                      (args.test_pressure_solver, "--test_pressure_solver (no time loop)")):
+        if bad:
+            raise RuntimeError(f"--restart does not go with {what}")
+    files = [args.restart] if args.gpus == 1 else [f"{args.restart}.{r}" for r in range(args.gpus)]
+    for path in files:
+        if not os.path.isfile(path):
+            raise RuntimeError(f"--restart: no checkpoint file {path}")
 
 
 def tracer_initial(m):
@@ -306,6 +337,7 @@ def main(argv=None):
     check_multi_gpu(args)
     check_particles(args)
     check_tracers(args)
+    check_checkpoint(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
     ranks = _Ranks(args)
@@ -415,7 +447,12 @@ def _run(args, ranks):
     if args.particles:
         kw["particles"] = read_points_inside(args.particles, eng, "particle seed")
         kw["particle_every"] = args.particle_every
+    if args.checkpoint:
+        kw["checkpoint"], kw["checkpoint_every"] = args.checkpoint, args.checkpoint_every or 0
+    if args.restart:
+        kw["restart"] = args.restart
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
+    state_digest = eng.state_digest()  # of this rank's strip
     if args.diagnostics:
         report_solver_events(eng.solver_events())
         if ranks.rank == 0:
@@ -431,6 +468,8 @@ def _run(args, ranks):
             print(f"{q.name()}: integral = {integral!r}, half square integral = {half_sq!r}")
         print()
     log_summary()
+    print(f"state digest = {state_digest[0]:016x}{state_digest[1]:016x}")
+    print()
     if args.problem in ("shear", "kelvinhelmholtz"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here
         # with an AttributeError); write the final fields

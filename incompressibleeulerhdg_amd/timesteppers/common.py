@@ -3,6 +3,7 @@
 Same class surface as the reference; the bodies call the HIP engine through the ctypes C-ABI.
 """
 
+import os
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -159,8 +160,9 @@ class IncompressibleEuler(ABC):
     _callback_names = (None, None)  # names of the velocity and pressure Functions handed to callbacks
     _result_names = ("velocity", "pressure")  # ... and of those solve() returns
 
-    def _begin_solve(self):
-        """After the state is set, before the recorders start."""
+    def _begin_solve(self, restarted=False):
+        """After the state is set, before the recorders start.  ``restarted``: the state came from a checkpoint and must
+        stay what it is (no reconstruction, no reset of the engine's statistics)."""
 
     def _advance(self, k, f_rhs, tracer):
         """Step k (forcing included); returns the time reached, which the callbacks are given."""
@@ -176,28 +178,83 @@ class IncompressibleEuler(ABC):
     def _functions(self, Q, p, names):
         return Function(self._V_Q, Q, names[0]), Function(self._V_p, p, names[1])
 
-    def _solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, **requests):
-        """The time loop of every stepper; ``requests``: the per-step outputs asked for, by the names of RECORDERS (each
-        class there says what counts as asked for) and ``particle_every``.  Each one asked for leaves its dict in the attribute of its name."""
+    def _rank_path(self, path):
+        """The checkpoint file of this rank: PATH on one rank, PATH.<rank> on strips."""
+        return path if self._engine.nranks == 1 else f"{path}.{self._engine.rank}"
+
+    def _write_checkpoint(self, path, step, t):
+        """The engine's state after `step` steps, written under a temporary name and moved into place: a run that is killed
+        never leaves half a file."""
+        path = self._rank_path(path)
+        blob = self._engine.save_checkpoint(step, t)
+        tmp = f"{path}.tmp"
+        with open(tmp, "wb") as f:
+            f.write(blob)
+        os.replace(tmp, path)
+
+    def _restart(self, path, nt, warmup, requests):
+        """Load the checkpoint; returns (steps done, time reached, whether a tracer is advected).  A request that disagrees
+        with what the saved run had switched on is a ValueError, raised before the engine is touched."""
         eng = self._engine
-        tracer = self._init_tracer(q_initial)
+        if warmup:
+            raise ValueError("restart: a warm-up run takes one step from the initial condition; it cannot continue a checkpoint")
+        with open(self._rank_path(path), "rb") as f:
+            blob = f.read()
+        saved = Engine.checkpoint_info(blob)
+        for name, make in RECORDERS:
+            if make.requested(requests[name]) != saved[name]:
+                raise ValueError(f"restart: the checkpoint was written {'with' if saved[name] else 'without'} {name}, "
+                                 f"this run asks for it {'on' if make.requested(requests[name]) else 'off'}")
+        for name, n in (("probes", saved["n_probes"]), ("particles", saved["n_particles"])):
+            if saved[name] and len(np.asarray(requests[name], dtype=float).reshape(-1, 2)) != n:
+                raise ValueError(f"restart: the checkpoint records {n} {name}, this run asks for "
+                                 f"{len(np.asarray(requests[name], dtype=float).reshape(-1, 2))}")
+        if saved["step"] > nt:
+            raise ValueError(f"restart: the checkpoint was written after step {saved['step']}, this run ends after step {nt}")
+        k0, t0 = eng.load_checkpoint(blob)
+        if saved["tracer"]:
+            self._tracer_function()
+        else:
+            self.q_tracer, self.q_tracers = None, []
+        return k0, t0, saved["tracer"]
+
+    def _solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, checkpoint=None, checkpoint_every=0, restart=None,
+               **requests):
+        """The time loop of every stepper; ``requests``: the per-step outputs asked for, by the names of RECORDERS (each
+        class there says what counts as asked for) and ``particle_every``.  Each one asked for leaves its dict in the attribute of its name.
+
+        ``checkpoint=PATH`` writes the engine's state (Engine.save_checkpoint) after every ``checkpoint_every``-th step
+        (0: never in between) and after the last one; ``restart=PATH`` continues such a file: the state, the tracers and the
+        recorders are the saved ones (the initial-condition arguments are ignored and may be None) and the loop runs from
+        the saved step to the end, so the run is the uninterrupted one bit for bit."""
+        eng = self._engine
         nt = self.get_timesteps(T_final, warmup)
+        if checkpoint is not None and int(checkpoint_every) < 0:
+            raise ValueError(f"checkpoint_every must be >= 0 (got {checkpoint_every})")
         self._forcing_profile = None
-        eng.set_state(self._as_nodal_velocity(Q_initial), self._as_nodal_pressure(p_initial))
-        self._begin_solve()
+        k0, t0 = 0, 0
+        if restart is None:
+            tracer = self._init_tracer(q_initial)
+            eng.set_state(self._as_nodal_velocity(Q_initial), self._as_nodal_pressure(p_initial))
+        else:
+            k0, t0, tracer = self._restart(restart, nt, warmup, requests)
+        self._begin_solve(restarted=restart is not None)
         recorders = []
         for name, make in RECORDERS:
             setattr(self, name, None)
             if make.requested(requests[name]):
                 recorders.append((name, make(requests[name], self._dt, requests["particle_every"])))
-                recorders[-1][1].start(eng, nt)
+                if restart is None:  # a restored engine goes on recording into the logs the checkpoint holds
+                    recorders[-1][1].start(eng, nt)
         for callback in self.callbacks:
             callback.reset()
-            callback(*self._functions(*self._current(), self._callback_names), 0,
+            callback(*self._functions(*self._current(), self._callback_names), t0,
                      q_tracer=self.q_tracers if len(self.q_tracers) > 1 else self.q_tracer)
-        for k in range(nt):
+        for k in range(k0, nt):
             with PerformanceLog("timestep"):
                 t = self._advance(k, f_rhs, tracer)
+            if checkpoint is not None and (k + 1 == nt or (checkpoint_every and (k + 1) % int(checkpoint_every) == 0)):
+                self._write_checkpoint(checkpoint, k + 1, t)
             if self.callbacks:
                 Q, p = self._current()
                 qt = self._tracer_function() if tracer else None
@@ -213,7 +270,7 @@ class IncompressibleEuler(ABC):
 
     @abstractmethod
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1):
+              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""
 
 

@@ -110,7 +110,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
 
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1):
+              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final with nt timesteps; returns (Q, p).
 
         ``fused=True`` runs each step as one device-resident ``hdg_step`` call instead of the
@@ -122,22 +122,29 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         ``particles=xy`` ((n, 2) seeds) advects Lagrangian particles through the velocity of every step on the device
         (Heun's method) and stores ``self.particles`` (dict: ``t``, ``xy`` (rows, n, 2): the seeds and the positions after
         every ``particle_every``-th step, ``clamped``, ``lost``).
+        ``checkpoint=PATH`` writes the engine's whole state after every ``checkpoint_every``-th step (0: not in between)
+        and after the last one (strips: each rank writes ``PATH.<rank>``); ``restart=PATH`` continues such a file to
+        T_final -- the run is then the uninterrupted one bit for bit, recorded series included; the initial-condition
+        arguments are ignored and may be None.
         """
         self._fused = fused
         return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
-                           particles=particles, particle_every=particle_every)
+                           particles=particles, particle_every=particle_every, checkpoint=checkpoint,
+                           checkpoint_every=checkpoint_every, restart=restart)
 
     _callback_names = _result_names = ("Q", "p")
 
     def _averagers(self):
         return self.niter_tentative, self.niter_pressure, self.niter_final_pressure, self.niter_pressure_reconstruction
 
-    def _begin_solve(self):
-        self._reconstruct_trace()
+    def _begin_solve(self, restarted=False):
         for a in self._averagers():
             a.reset()
-        self._engine.iteration_stats(reset=True)
         self._engine.timers(reset=True)
+        if restarted:  # the trace and the statistics are the checkpoint's
+            return
+        self._reconstruct_trace()
+        self._engine.iteration_stats(reset=True)
 
     def _advance(self, k, f_rhs, tracer):
         eng, s = self._engine, self.nstages

@@ -34,11 +34,12 @@ class IncompressibleEulerHDGImplicit(IncompressibleEuler):
                             b_impl=[1], c_expl=[0])
 
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1):
-        """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``, ``particles``: see
-        IncompressibleEulerHDGIMEX.solve."""
+              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
+        """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``, ``particles``, ``checkpoint``,
+        ``checkpoint_every``, ``restart``: see IncompressibleEulerHDGIMEX.solve."""
         return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
-                           particles=particles, particle_every=particle_every)
+                           particles=particles, particle_every=particle_every, checkpoint=checkpoint,
+                           checkpoint_every=checkpoint_every, restart=restart)
 
     def _advance(self, k, f_rhs, tracer):
         self._set_forcing(0, f_rhs, k * self._dt)  # forcing at the START of the step (hdg_implicit.py:100)
