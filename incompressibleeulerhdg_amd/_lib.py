@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("HDG_LIB_PATH") or os.path.join(_HERE, "libhdg_mi355x.
 SRC = os.path.join(_HERE, "csrc", "hdg_engine.hip")
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_mi355x.h"))
 CHECKPOINT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_checkpoint.h"))
+TRANSFER_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_transfer.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -88,7 +89,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -186,6 +187,12 @@ CHECKPOINT_SIGNATURES = {
     "hdg_digest_vector": [_h, _dp, C.c_long, _ullp],
 }
 
+# transfer between engines: the symbols include/hdg_transfer.h declares, in a table of their own like the checkpoint's
+TRANSFER_SIGNATURES = {
+    "hdg_transfer_state": [_h, _h, C.c_int],
+    "hdg_transfer_difference": [_h, _h, _dp, _dp, _dp],
+}
+
 
 def load_library():
     """Load libhdg_mi355x.so; raise loudly when it has not been built."""
@@ -198,7 +205,7 @@ def load_library():
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -456,6 +463,7 @@ class Engine:
         """q: (N_p,) with one tracer, (n_tracers, N_p) with several (Engine(n_tracers=...)); None switches all of them off."""
         q = None if q is None else _arr(q, self.shape_q)
         self._ck(self.lib.hdg_set_tracer(self.h, _ptr(q)))
+        self._tracer_on = q is not None
 
     def get_tracer(self):
         q = np.empty(self.shape_q)
@@ -710,6 +718,7 @@ class Engine:
         self._ck(self.lib.hdg_checkpoint_load(self.h, buf.ctypes.data_as(C.c_void_p), len(buf), C.byref(step), C.byref(t)))
         info = self.checkpoint_info(blob)
         self._n_probes, self._n_particles = info["n_probes"], info["n_particles"]  # the shapes of probes() / particles()
+        self._tracer_on = info["tracer"]
         return step.value, t.value
 
     def state_digest(self):
@@ -724,6 +733,25 @@ class Engine:
         out = (C.c_ulonglong * 2)()
         self._ck(self.lib.hdg_digest_vector(self.h, _ptr(v) if v.size else None, v.size, out))
         return int(out[0]), int(out[1])
+
+    # --- transfer between engines on nested meshes (include/hdg_transfer.h)
+    def transfer_from(self, src, tracers=False):
+        """Take the state of the engine `src` (another mesh size and degree on a nested mesh): the L2 projection of its velocity,
+        pressure and, with tracers=True, its tracers onto this engine's spaces, on the device.  Afterwards this engine is as
+        after set_state (and set_tracer) with the transferred fields.  Raises HDGError naming the cause for a pair that does
+        not fit (HDG_ERR_ARG; general meshes and strips HDG_ERR_UNSUPPORTED) and then leaves both engines as they were."""
+        self._ck(self.lib.hdg_transfer_state(self.h, src.h, 1 if tracers else 0))
+        if tracers:
+            self._tracer_on = True
+
+    def difference_norms(self, other):
+        """{"Q", "p", "q"}: the L2 norms of the differences of the current states of this engine and `other`, exact on the
+        common refinement of the two meshes; "q" is an array of n_tracers norms when both carry tracers, else None."""
+        nq, npv = C.c_double(0.0), C.c_double(0.0)
+        both = getattr(self, "_tracer_on", False) and getattr(other, "_tracer_on", False)
+        q = np.zeros(self.n_tracers) if both else None
+        self._ck(self.lib.hdg_transfer_difference(self.h, other.h, C.byref(nq), C.byref(npv), _ptr(q)))
+        return {"Q": nq.value, "p": npv.value, "q": q}
 
     def time_kernel(self, kernel, reps):
         ms = C.c_double()

@@ -29,6 +29,7 @@
 
 #include "../../include/hdg_mi355x.h"
 #include "../../include/hdg_checkpoint.h"
+#include "../../include/hdg_transfer.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -50,6 +51,8 @@
 #include "hdg_row_log.hpp"
 #include "hdg_checkpoint.hpp"
 #include "hdg_digest.hpp"
+#include "hdg_transfer.hpp"
+#include "hdg_transfer_kernels.hpp"
 
 namespace hdg {
 
@@ -4415,6 +4418,88 @@ struct Engine {
     if (t) *t = B.header.t;
   }
 
+  // ------------------------------------------------------------------ transfer between engines
+  // L2 projection of another engine's state onto this engine's spaces on a nested structured mesh, and the L2 norm of the
+  // difference of two engines' states (hdg_transfer.hpp: tables, hdg_transfer_kernels.hpp: kernels).  Used once per run: the
+  // table of the pair is built and uploaded per call and freed again, and no step ever sees any of this.
+  //
+  // Stream ordering: every engine owns a stream.  The other engine's stream is drained (hipStreamSynchronize) before the
+  // first kernel that reads its vectors is put on the stream the call works on -- a transfer happens between steps, where
+  // that stream is idle anyway, so an event would save nothing.
+  template <class F> static void by_degree_pair(int k1, int k2, F&& f) {
+    with_int<1, 2, 3, 4>(k1, "degree", [&](auto a) { with_int<1, 2, 3, 4>(k2, "degree", [&](auto b) { f(a, b); }); });
+  }
+  // what a pair must satisfy, each refusal naming its cause; HDG_ERR_UNSUPPORTED cases come back as false with `unsupported`
+  // set, the others throw (HDG_ERR_ARG).  Returns the ratio through r (always >= 1).
+  static void transfer_pair_check(const Engine& A, const Engine& B, const char* call, std::string& unsupported, int& r) {
+    unsupported.clear();
+    r = 1;
+    const std::string c(call);
+    if (A.general || B.general) { unsupported = c + ": general meshes are not supported (nested structured meshes only)"; return; }
+    if (A.comm->size > 1 || B.comm->size > 1) { unsupported = c + ": engines with more than one rank are not supported"; return; }
+    if (A.periodic != B.periodic) throw c + ": different mesh kind (unit square and doubly periodic square)";
+    if (A.Ldom != B.Ldom) throw c + ": different L (" + std::to_string(A.Ldom) + " and " + std::to_string(B.Ldom) + ")";
+    if (A.cfg.device != B.cfg.device) throw c + ": different device (" + std::to_string(A.cfg.device) + " and " + std::to_string(B.cfg.device) + ")";
+    if (A.g.ny != A.g.nx || B.g.ny != B.g.nx) throw c + ": ny = nx is required";
+    const int hi = std::max(A.g.nx, B.g.nx), lo = std::min(A.g.nx, B.g.nx);
+    if (hi % lo != 0) throw c + ": the meshes are not nested (non-integer ratio " + std::to_string(hi) + " / " + std::to_string(lo) + ")";
+    r = hi / lo;
+    if (r > transfer::MAX_RATIO) throw c + ": ratio r = " + std::to_string(r) + " > " + std::to_string(transfer::MAX_RATIO);
+    if (A.step_open || B.step_open) throw c + ": a step is open (between hdg_begin_step and the end of the step) on " +
+        (A.step_open ? (B.step_open ? "both engines" : "the first engine") : "the second engine");
+  }
+  // the velocity table of (coarse degree kc, fine degree kf) on the device; the caller frees it
+  double* transfer_table(int kc, int kf, int r) { return const_cast<double*>(upload(transfer::child_tables(kc + 1, kf + 1, r))); }
+  void transfer_from(Engine& S, int r, bool with_tracers) {
+    if (with_tracers && (!S.tracer_on || S.n_tr != n_tr))
+      throw std::string("hdg_transfer_state: tracer mismatch: the source ") +
+          (S.tracer_on ? "carries " + std::to_string(S.n_tr) + " tracer(s), this engine " + std::to_string(n_tr) : "has no tracer switched on");
+    HIPCHECK(hipStreamSynchronize(S.stream));  // stream ordering: see above
+    const bool prolong = g.nx >= S.g.nx;
+    double* T = prolong ? transfer_table(S.K, K, r) : transfer_table(K, S.K, r);
+    if (with_tracers) { cg_setup(); tracer_alloc(); }
+    auto launch = [&](auto vel, const double* src, long sstride, double* dst, long dstride, int nfields) {
+      dim3 grid = cell_grid();
+      grid.y = (unsigned)nfields;
+      tally(LC_OTHER, (vel() ? 16.0 : 8.0) * nfields * (2.0 * g.nx * g.ny * (vel() ? NU : NP) + 2.0 * S.g.nx * S.g.ny * (vel() ? S.NU : S.NP)));
+      by_degree_pair(S.K, K, [&](auto ks, auto kd) {
+        if (prolong) k_xfer_prolong<ks(), kd(), vel()><<<grid, bs(), 0, stream>>>(g, S.g, r, T, src, sstride, dst, dstride);
+        else k_xfer_restrict<ks(), kd(), vel()><<<grid, bs(), 0, stream>>>(g, S.g, r, T, src, sstride, dst, dstride);
+      });
+    };
+    // velocity and scalars are separate launches (pair planes / scalar planes); the tracers are one launch, grid.y apart
+    launch(std::true_type{}, S.curQ, 0, curQ, 0, 1);
+    launch(std::false_type{}, S.curP, 0, curP, 0, 1);
+    if (with_tracers) { launch(std::false_type{}, S.q_cur, S.NPv, q_cur, NPv, n_tr); tracer_on = true; }
+    shift(curP, nullptr);  // as hdg_set_state: p_0 -= mean
+    particles_refresh();
+    HIPCHECK(hipStreamSynchronize(stream));
+    dfree(T);
+  }
+  // norms of the differences of the current states of A and B (n_q: tracer norms wanted, needs the same tracers on both)
+  static void transfer_difference(Engine& A, Engine& B, int r, double* norm_Q, double* norm_p, double* norm_q) {
+    if (norm_q && (!A.tracer_on || !B.tracer_on || A.n_tr != B.n_tr))
+      throw std::string("hdg_transfer_difference: tracer mismatch: tracer norms need the same tracers switched on in both engines");
+    Engine& F = A.g.nx >= B.g.nx ? A : B;  // the work runs on the finer mesh's engine and stream
+    Engine& C = &F == &A ? B : A;
+    HIPCHECK(hipStreamSynchronize(C.stream));  // stream ordering: see above
+    HIPCHECK(hipStreamSynchronize(F.stream));
+    const int km = std::max(C.K, F.K);
+    double* T = F.transfer_table(C.K, km, r);
+    auto norm = [&](auto vel, const double* coarse, const double* fine) {
+      F.tally(LC_OTHER, 0.0);
+      by_degree_pair(C.K, F.K, [&](auto kc, auto kf) {
+        k_xfer_diff<kc(), kf(), vel()><<<F.cell_grid(), F.bs(), 0, F.stream>>>(F.g, C.g, r, T, coarse, fine, F.wP1);
+      });
+      return std::sqrt(F.dot(F.g.Nc, F.wP1, F.ones_c, KC));  // the two-stage deterministic reduction over the owned cells
+    };
+    if (norm_Q) *norm_Q = norm(std::true_type{}, C.curQ, F.curQ);
+    if (norm_p) *norm_p = norm(std::false_type{}, C.curP, F.curP);
+    if (norm_q)
+      for (int t = 0; t < A.n_tr; t++) norm_q[t] = norm(std::false_type{}, C.q_cur + t * C.NPv, F.q_cur + t * F.NPv);
+    F.dfree(T);
+  }
+
   // ------------------------------------------------------------------ host <-> device fields
   long n_edges() const {
     if (general) return gm->ne;
@@ -5178,6 +5263,34 @@ int hdg_digest_vector(hdg_handle* h, const double* v, long n, unsigned long long
   HDG_API_BEGIN(h)
   E.digest_host_vector(v, n, out);
   HDG_API_END(h)
+}
+
+// ---- transfer between engines (include/hdg_transfer.h)
+// the checks of a pair that end in HDG_ERR_UNSUPPORTED, or in HDG_ERR_ARG before an engine is looked at; 0: go on
+static int transfer_pair_gate(hdg_handle* a, const hdg_handle* b, const char* call, bool same_allowed, int* r) {
+  if (!a || !a->eng) return HDG_ERR_ARG;
+  if (!b || !b->eng) { a->err = std::string(call) + ": null engine"; return HDG_ERR_ARG; }
+  if (a == b && !same_allowed) { a->err = std::string(call) + ": dst == src (an engine cannot be transferred onto itself)"; return HDG_ERR_ARG; }
+  try {
+    std::string unsupported;
+    hdg::Engine::transfer_pair_check(*a->eng, *b->eng, call, unsupported, *r);
+    if (!unsupported.empty()) { a->err = unsupported; return HDG_ERR_UNSUPPORTED; }
+  } catch (const std::string& e) { a->err = e; return HDG_ERR_ARG; }
+  return HDG_OK;
+}
+int hdg_transfer_state(hdg_handle* dst, const hdg_handle* src, int with_tracers) {
+  int r = 1;
+  if (const int rc = transfer_pair_gate(dst, src, "hdg_transfer_state", false, &r)) return rc;
+  HDG_API_BEGIN(dst)
+  E.transfer_from(*src->eng, r, with_tracers != 0);
+  HDG_API_END(dst)
+}
+int hdg_transfer_difference(hdg_handle* a, hdg_handle* b, double* norm_Q, double* norm_p, double* norm_q) {
+  int r = 1;
+  if (const int rc = transfer_pair_gate(a, b, "hdg_transfer_difference", true, &r)) return rc;
+  HDG_API_BEGIN(a)
+  hdg::Engine::transfer_difference(E, *b->eng, r, norm_Q, norm_p, norm_q);
+  HDG_API_END(a)
 }
 
 }  // extern "C"

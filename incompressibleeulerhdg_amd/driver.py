@@ -17,6 +17,10 @@ and writes their positions to ``--particle_output`` (``particles.npz``).
 each rank writes and reads ``FILE.<rank>``.  The final printout carries ``state digest``, 16 bytes that are equal exactly when
 two runs ended in the same engine state.
 
+``--start_from FILE`` starts the run at t = 0 from the state a ``--checkpoint`` FILE of another resolution holds: a second
+timestepper with ``--start_nx``, ``--start_degree`` and ``--start_dt`` (each defaults to the run's own value) loads FILE, and its
+state is L2 projected onto the run's spaces on the device; the meshes must be nested.
+
 ``--gpus N`` (N > 1) runs the two structured problems on N strips (one process per rank, include/hdg_mi355x.h:
 hdg_create_distributed): the driver starts ``python -m torch.distributed.run --nproc-per-node=N`` with the same arguments
 as a child process and returns its exit status.  Each rank chooses RCCL when every rank has a device of its own and the
@@ -108,6 +112,14 @@ def build_parser():
                         help="with --checkpoint: write after every M-th step (default: after the last step only)")
     parser.add_argument("--restart", metavar="FILE", type=str, default=None,
                         help="continue the run whose --checkpoint FILE this is, to --tfinal")
+    parser.add_argument("--start_from", metavar="FILE", type=str, default=None,
+                        help="start at t = 0 from the state of the --checkpoint FILE of a run of another mesh size or degree, "
+                             "projected onto this run's spaces (nested meshes; --problem shear)")
+    parser.add_argument("--start_nx", metavar="N", type=int, default=None, help="with --start_from: the nx of the run that wrote FILE (default: --nx)")
+    parser.add_argument("--start_degree", metavar="K", type=int, default=None,
+                        help="with --start_from: the degree of the run that wrote FILE (default: --degree)")
+    parser.add_argument("--start_dt", metavar="DT", type=float, default=None,
+                        help="with --start_from: the timestep size of the run that wrote FILE (default: --dt)")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -167,6 +179,36 @@ def check_checkpoint(args):
     for path in files:
         if not os.path.isfile(path):
             raise RuntimeError(f"--restart: no checkpoint file {path}")
+
+
+MAX_START_RATIO = 16  # csrc/hdg_transfer.hpp: MAX_RATIO
+
+
+def check_start_from(args):
+    """Refuse a --start_from request that cannot be served, before any process is started or any engine is built."""
+    if not args.start_from:
+        for name in ("start_nx", "start_degree", "start_dt"):
+            if getattr(args, name) is not None:
+                raise RuntimeError(f"--{name} needs --start_from")
+        return
+    refused = [
+        (args.problem == "taylorgreen", "--problem taylorgreen (forcing and exact solution are tied to the absolute time)"),
+        (args.problem == "kelvinhelmholtz", "--problem kelvinhelmholtz (general meshes are not transferred)"),
+        (args.gpus > 1, f"--gpus {args.gpus} (the transfer is single-rank)"),
+        (bool(args.restart), "--restart (a restart continues its own checkpoint)"),
+        (args.warmup, "--warmup (one step from the initial condition)"),
+        (args.test_pressure_solver, "--test_pressure_solver (no time loop)"),
+    ]
+    for bad, what in refused:
+        if bad:
+            raise RuntimeError(f"--start_from does not go with {what}")
+    if not os.path.isfile(args.start_from):
+        raise RuntimeError(f"--start_from: no checkpoint file {args.start_from}")
+    nx0 = args.nx if args.start_nx is None else args.start_nx
+    hi, lo = max(nx0, args.nx), min(nx0, args.nx)
+    if lo < 1 or hi % lo != 0 or hi // lo > MAX_START_RATIO:
+        raise RuntimeError(f"--start_nx {nx0} and --nx {args.nx} are not nested (one must be r times the other, "
+                           f"1 <= r <= {MAX_START_RATIO})")
 
 
 def tracer_initial(m):
@@ -338,6 +380,7 @@ def main(argv=None):
     check_particles(args)
     check_tracers(args)
     check_checkpoint(args)
+    check_start_from(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
     ranks = _Ranks(args)
@@ -349,6 +392,46 @@ def main(argv=None):
         ranks.close()
 
 
+def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
+    """The timestepper the arguments ask for, on the given mesh with the given degree and timestep size."""
+    several = {"n_tracers": args.tracers} if args.tracers > 1 else {}
+    if args.discretisation == "dg":
+        # driver.py:203-213
+        assert not args.use_projection_method, "Can not use projection method with DG discretsation"
+        if args.timestepper != "implicit":
+            raise RuntimeError(f"Invalid timestepping method for DG discretisation: '{args.timestepper}'")
+        return IncompressibleEulerDGImplicit(mesh, degree, dt, flux=args.flux, callbacks=callbacks, device=args.device, **several)
+    if args.timestepper == "implicit":
+        return IncompressibleEulerHDGImplicit(  # driver.py:220-228 (passes n_richardson: SURVEY C-1)
+            mesh, degree, dt, flux=args.flux, use_projection_method=args.use_projection_method,
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
+    if args.timestepper in TIMESTEPPERS:
+        return TIMESTEPPERS[args.timestepper](
+            mesh, degree, dt, flux=args.flux, use_projection_method=args.use_projection_method,
+            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
+    raise RuntimeError(f"Invalid timestepping method for HDG discretisation: '{args.timestepper}'")
+
+
+def start_from(args, ranks, timestepper):
+    """--start_from: (Q, p, q) on the run's spaces from the checkpoint of a run of another mesh size and degree.  A second
+    timestepper with the start values (otherwise the run's arguments) loads the file, its state is transferred on the device,
+    and it is closed again."""
+    nx0 = args.nx if args.start_nx is None else args.start_nx
+    k0 = args.degree if args.start_degree is None else args.start_degree
+    dt0 = args.dt if args.start_dt is None else args.start_dt
+    mesh0 = PeriodicSquareMesh(nx0, nx0, L=2 * np.pi, quadrilateral=False)
+    source = make_timestepper(args, ranks, mesh0, k0, dt0, None)
+    try:
+        with open(args.start_from, "rb") as f:
+            _, t0 = source._engine.load_checkpoint(f.read())
+        fields = timestepper.state_from(source)
+    finally:
+        source._engine.close()
+    print(f"start: transferred nx = {nx0}, degree = {k0}, t = {t0!r} -> nx = {args.nx}, degree = {args.degree}")
+    print()
+    return fields
+
+
 def _run(args, ranks):
     callbacks = [AnimationCallback("evolution.pvd")] if args.animation else None  # driver.py:187
     if args.problem == "shear":
@@ -357,24 +440,7 @@ def _run(args, ranks):
         mesh = UnitDiskMesh(refinement_level=args.refinement)  # driver.py:184-185
     else:
         mesh = UnitSquareMesh(args.nx, args.nx, quadrilateral=False)  # driver.py:181
-    several = {"n_tracers": args.tracers} if args.tracers > 1 else {}
-    if args.discretisation == "dg":
-        # driver.py:203-213
-        assert not args.use_projection_method, "Can not use projection method with DG discretsation"
-        if args.timestepper != "implicit":
-            raise RuntimeError(f"Invalid timestepping method for DG discretisation: '{args.timestepper}'")
-        timestepper = IncompressibleEulerDGImplicit(mesh, args.degree, args.dt, flux=args.flux, callbacks=callbacks,
-                                                    device=args.device, **several)
-    elif args.timestepper == "implicit":
-        timestepper = IncompressibleEulerHDGImplicit(  # driver.py:220-228 (passes n_richardson: SURVEY C-1)
-            mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
-    elif args.timestepper in TIMESTEPPERS:
-        timestepper = TIMESTEPPERS[args.timestepper](
-            mesh, args.degree, args.dt, flux=args.flux, use_projection_method=args.use_projection_method,
-            n_richardson=args.richardson, callbacks=callbacks, **ranks.kwargs, **several)
-    else:
-        raise RuntimeError(f"Invalid timestepping method for HDG discretisation: '{args.timestepper}'")
+    timestepper = make_timestepper(args, ranks, mesh, args.degree, args.dt, callbacks)
 
     print("+-------------------------------------------------+")
     print("! timesteppers for incompressible Euler equations !")
@@ -439,6 +505,10 @@ def _run(args, ranks):
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None
     if args.tracers > 1:
         q_0 = [tracer_initial(m) for m in range(args.tracers)]
+    if args.start_from:
+        Q_0, p_0, q_start = start_from(args, ranks, timestepper)
+        if args.tracer_advection and q_start is not None:
+            q_0 = q_start
     kw = {"fused": True} if (args.fused and args.timestepper != "implicit") else {}
     if args.diagnostics:
         kw["diagnostics"] = True

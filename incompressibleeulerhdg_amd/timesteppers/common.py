@@ -144,6 +144,23 @@ class IncompressibleEuler(ABC):
                                             None if p is None else self._as_nodal_pressure(p),
                                             None if q is None else self._as_nodal_pressure(q))
 
+    # -- transfer between runs of different mesh size and degree (include/hdg_transfer.h) ----------
+    def state_from(self, other):
+        """The current state of the timestepper `other` (another nx and degree on a nested mesh, any stepper family), L2
+        projected onto this timestepper's spaces on the device: (Q, p, q) as Functions, fit to be passed as Q_initial,
+        p_initial, q_initial of solve.  q is None when `other` advects no tracer (or another number of them), else one
+        Function or the list of several, as q_tracer(s) is."""
+        eng, src = self._engine, other._engine
+        tracers = bool(getattr(src, "_tracer_on", False)) and src.n_tracers == eng.n_tracers
+        eng.transfer_from(src, tracers=tracers)
+        Q, p = self._functions(*self._current(), self._result_names)
+        return Q, p, (self._tracer_function() if tracers else None)
+
+    def difference(self, other):
+        """{"Q", "p", "q"}: L2 norms of the differences of the current states of this timestepper and `other`, exact on the
+        common refinement of the two meshes (Engine.difference_norms)."""
+        return self._engine.difference_norms(other._engine)
+
     # -- forcing -------------------------------------------------------------------------------
     def _set_forcing(self, slot, f_rhs, t):
         if f_rhs is None or (isinstance(f_rhs, (int, float)) and f_rhs == 0):  # SURVEY.md C-6
