@@ -17,6 +17,7 @@ SRC = os.path.join(_HERE, "csrc", "hdg_engine.hip")
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_mi355x.h"))
 CHECKPOINT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_checkpoint.h"))
 TRANSFER_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_transfer.h"))
+TRACER_DIFFUSION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_diffusion.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -89,7 +90,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -193,6 +194,13 @@ TRANSFER_SIGNATURES = {
     "hdg_transfer_difference": [_h, _h, _dp, _dp, _dp],
 }
 
+# tracer diffusion: the symbols include/hdg_tracer_diffusion.h declares, in a table of their own like the two above
+TRACER_DIFFUSION_SIGNATURES = {
+    "hdg_set_tracer_diffusivity": [_h, C.c_int, _dp],
+    "hdg_get_tracer_diffusion_number": [_h, _dp],
+    "hdg_apply_tracer_diffusion": [_h, _dp, _dp],
+}
+
 
 def load_library():
     """Load libhdg_mi355x.so; raise loudly when it has not been built."""
@@ -205,7 +213,8 @@ def load_library():
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
+            list(TRACER_DIFFUSION_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -483,6 +492,27 @@ class Engine:
         q, u = _arr(q, self.shape_p), _arr(u, self.shape_Q)
         out = np.empty(self.shape_p)
         self._ck(self.lib.hdg_apply_tracer_advection(self.h, _ptr(q), _ptr(u), 1 if project else 0, _ptr(out)))
+        return out
+
+    # --- tracer diffusion (include/hdg_tracer_diffusion.h)
+    def set_tracer_diffusivity(self, kappa):
+        """kappa: one value for every tracer or a sequence of n_tracers values, finite and >= 0; None or zeros: off."""
+        if kappa is not None:
+            kappa = np.asarray(kappa, dtype=np.float64)
+            kappa = np.full(self.n_tracers, float(kappa)) if kappa.ndim == 0 else np.ascontiguousarray(kappa.reshape(-1))
+        self._ck(self.lib.hdg_set_tracer_diffusivity(self.h, 0 if kappa is None else len(kappa), _ptr(kappa)))
+
+    def tracer_diffusion_number(self):
+        """(Lambda, kappa_max dt Lambda): Lambda is an upper bound of the spectral radius of M^-1 D."""
+        out = np.zeros(2)
+        self._ck(self.lib.hdg_get_tracer_diffusion_number(self.h, _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def apply_tracer_diffusion(self, q):
+        """M^-1 D q of one nodal DG_k field, without kappa (test hook)."""
+        q = _arr(q, self.shape_p)
+        out = np.empty(self.shape_p)
+        self._ck(self.lib.hdg_apply_tracer_diffusion(self.h, _ptr(q), _ptr(out)))
         return out
 
     def cg_size(self):

@@ -275,6 +275,69 @@ __global__ __launch_bounds__(128) void k_tracer_adv(Geo g, DevTables T, int nt, 
     if (b < nb) store_cell<NP>(out + (t0 + b) * tstride, g.Nc, c, F[b]);
 }
 
+// Tracer diffusion: out_t += kappa_t M^-1 D q_t, the symmetric interior-penalty form with no-flux walls
+// in the orthonormal modal basis.  On the structured mesh M^-1 D is seven NP x NP blocks per element shape (hdg_tables.hpp,
+// TracerDiffusionTables::packed: Vol, Own[0..2], Nbr[0..2]); the shape is uniform over a workgroup, so the blocks arrive
+// through scalar loads.  A cell's row is  Vol q_K + sum_{e with a neighbour} (Own[e] q_K + Nbr[e] q_K'); a wall edge adds nothing.
+// Thread <-> cell mapping, tracer blocks (gridDim.y), the choice of TB and the short last block are those of k_tracer_adv, which
+// has just run on the same q (so the ghost rows of the periodic square are filled) and has written out.  Per tracer the
+// floating-point operations and their order are those of one tracer alone, whatever TB and whatever the other tracers'
+// kappa; a tracer with kappa_t = 0 is neither read back nor written.
+template <int K, int TB>
+__global__ __launch_bounds__(128) void k_tracer_diff(Geo g, const double* __restrict__ tab, const double* __restrict__ kappa, int nt,
+                                                      long tstride, const double* __restrict__ q, double* __restrict__ out) {
+  constexpr int NP = Dim<K>::NP, BL = NP * NP;
+  HDG_CELL_PROLOGUE
+  const int t0 = blockIdx.y * TB;
+  const int nb = nt - t0 < TB ? nt - t0 : TB;
+  const double* __restrict__ T = tab + (long)s * 7 * BL;
+  double qc[TB][NP], F[TB][NP];
+#pragma unroll
+  for (int b = 0; b < TB; b++) {
+    if (b < nb) load_cell<NP>(q + (t0 + b) * tstride, g.Nc, c, qc[b]);
+#pragma unroll
+    for (int r = 0; r < NP; r++) { F[b][r] = 0.0; if (b >= nb) qc[b][r] = 0.0; }
+  }
+  auto apply = [&](const double* __restrict__ A, const double (&x)[TB][NP]) {
+#pragma unroll
+    for (int r = 0; r < NP; r++)
+#pragma unroll
+      for (int m = 0; m < NP; m++) {
+        const double a = A[r * NP + m];
+#pragma unroll
+        for (int b = 0; b < TB; b++) F[b][r] = fma(a, x[b][m], F[b][r]);
+      }
+  };
+  apply(T, qc);
+#pragma unroll
+  for (int e = 0; e < 3; e++) {
+    long cn;
+    if (!nbr(s, e, i, j, g, cn)) continue;
+    double qn[TB][NP];
+#pragma unroll
+    for (int b = 0; b < TB; b++) {
+      if (b < nb) load_cell<NP>(q + (t0 + b) * tstride, g.Nc, cn, qn[b]);
+      else {
+#pragma unroll
+        for (int r = 0; r < NP; r++) qn[b][r] = 0.0;
+      }
+    }
+    apply(T + (1 + e) * BL, qc);
+    apply(T + (4 + e) * BL, qn);
+  }
+#pragma unroll
+  for (int b = 0; b < TB; b++) {
+    if (b >= nb) continue;
+    const double kap = kappa[t0 + b];
+    if (kap == 0.0) continue;
+    double o[NP];
+    load_cell<NP>(out + (t0 + b) * tstride, g.Nc, c, o);
+#pragma unroll
+    for (int r = 0; r < NP; r++) o[r] = fma(kap, F[b][r], o[r]);
+    store_cell<NP>(out + (t0 + b) * tstride, g.Nc, c, o);
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------
 // Jacobi-preconditioned CG on the continuous-space mass matrix for TWO right-hand sides at once (the two components of the

@@ -30,6 +30,7 @@
 #include "../../include/hdg_mi355x.h"
 #include "../../include/hdg_checkpoint.h"
 #include "../../include/hdg_transfer.h"
+#include "../../include/hdg_tracer_diffusion.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -3222,7 +3223,7 @@ struct Engine {
     const double dtt = cfg.dt;
     if (tracer_on) {  // hdg_implicit.py:93-96: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
-      tracer_adv(q_cur, uproj, q_t, n_tr);
+      tracer_tendency(q_cur, uproj, q_t);
     }
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
@@ -3356,7 +3357,7 @@ struct Engine {
     const double dtt = cfg.dt;
     if (tracer_on) {  // dg_implicit.py:117-120: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
-      tracer_adv(q_cur, uproj, q_t, n_tr);
+      tracer_tendency(q_cur, uproj, q_t);
     }
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
     lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
@@ -3707,6 +3708,90 @@ struct Engine {
       });
     });
   }
+  // ---- tracer diffusion: every tracer tendency gains kappa_t M^-1 D q_t, the symmetric interior-penalty
+  // form with no-flux walls.  Structured meshes: seven NP x NP blocks per element shape, built once on the host
+  // (hdg_tables.hpp: TracerDiffusionTables) and applied by k_tracer_diff right after k_tracer_adv on the same q; general
+  // meshes: M^-1 D assembled once (hdg_general.hpp: assemble_tracer_diffusion) and applied per tracer by the CSR kernel.
+  // Both are built on the first use.  kappa is configuration like dt: it stays when the tracers are switched off and on.
+  std::vector<double> tr_kappa;  // n_tr values while the feature is on (some kappa_t != 0), empty while it is off
+  double* d_kappa = nullptr;     // n_tr values, then a 1.0 (hdg_apply_tracer_diffusion)
+  const double* d_difftab = nullptr;
+  DevCsr gdiff;
+  double diff_lambda = -1.0;  // upper bound of rho(M^-1 D); < 0: not built
+  void diff_setup() {
+    if (diff_lambda >= 0.0) return;
+    if (comm->size > 1) cg_setup();  // a strip: the tracer error of hdg_set_tracer
+    d_kappa = dalloc(HDG_MAX_TRACERS + 1);
+    std::vector<double> k0(HDG_MAX_TRACERS + 1, 0.0);
+    k0[HDG_MAX_TRACERS] = 1.0;
+    HIPCHECK(hipMemcpy(d_kappa, k0.data(), sizeof(double) * k0.size(), hipMemcpyHostToDevice));
+    if (general) {
+      double lam = 0.0;
+      gdiff = upload_csr(assemble_tracer_diffusion(*gtab, *gm, lam));
+      diff_lambda = lam;
+    } else {
+      const TracerDiffusionTables D(K, g.h);
+      d_difftab = upload(D.packed());
+      diff_lambda = D.lambda;
+    }
+  }
+  void set_tracer_diffusivity(int n, const double* kappa) {
+    if (comm->size > 1) cg_setup();  // a strip: the tracer error of hdg_set_tracer
+    if (step_open) throw std::string("hdg_set_tracer_diffusivity: a step is open (between hdg_begin_step and the end of the step)");
+    bool any = false;
+    if (kappa) {
+      if (n != n_tr) throw std::string("hdg_set_tracer_diffusivity: " + std::to_string(n) + " value(s) for " + std::to_string(n_tr) + " tracer(s)");
+      for (int t = 0; t < n; t++) {
+        if (!(kappa[t] >= 0.0) || !std::isfinite(kappa[t]))
+          throw std::string("hdg_set_tracer_diffusivity: kappa[" + std::to_string(t) + "] = " + std::to_string(kappa[t]) + " is not a finite value >= 0");
+        any = any || kappa[t] != 0.0;
+      }
+    }
+    if (!any) { tr_kappa.clear(); return; }
+    diff_setup();
+    tr_kappa.assign(kappa, kappa + n);
+    HIPCHECK(hipMemcpyAsync(d_kappa, tr_kappa.data(), sizeof(double) * n, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  // out_t += kap_t M^-1 D q_t for n tracers, tracer-major (kap: device values for the kernel, host values for the CSR path);
+  // structured meshes read the ghost rows of q, which the caller has filled (tracer_adv on the same q, or halo_rows)
+  void tracer_diff(const double* q, const double* kap_dev, const double* kap_host, double* out, int n) {
+    if (general) {
+      for (int t = 0; t < n; t++)
+        if (kap_host[t] != 0.0) csr(gdiff, q + t * NPv, kap_host[t], 1.0, out + t * NPv);
+      return;
+    }
+    tally(LC_OTHER, 3.0 * n * bP());
+    by_degree([&](auto k) {
+      constexpr int KK = decltype(k)::value;
+      by_tracer_block<TracerBlock<KK>::TB>(n, [&](auto tb) {
+        constexpr int TB = decltype(tb)::value;
+        dim3 grid = cell_grid();
+        grid.y = (unsigned)((n + TB - 1) / TB);
+        k_tracer_diff<KK, TB><<<grid, bs(), 0, stream>>>(g, d_difftab, kap_dev, n, NPv, q, out);
+      });
+    });
+  }
+  // the tendency of every tracer: transport, plus diffusion when some kappa_t != 0
+  void tracer_tendency(const double* q, const double* u, double* out) {
+    tracer_adv(q, u, out, n_tr);
+    if (!tr_kappa.empty()) tracer_diff(q, d_kappa, tr_kappa.data(), out, n_tr);
+  }
+  // test hook: out = M^-1 D q for one field (q, out in the device layout), without kappa
+  void apply_tracer_diffusion(double* q, double* out) {
+    diff_setup();
+    if (!general) halo_rows(q, (long)g.R * g.nx, g.nx, NP * 2, 1);
+    zero(out, NPv);
+    const double one = 1.0;
+    tracer_diff(q, d_kappa + HDG_MAX_TRACERS, &one, out, 1);
+  }
+  void tracer_diffusion_number(double* out2) {
+    diff_setup();
+    double kmax = 0.0;
+    for (double x : tr_kappa) kmax = std::max(kmax, x);
+    out2[0] = diff_lambda;
+    out2[1] = kmax * cfg.dt * diff_lambda;
+  }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
     if (!tracer_on) return;
@@ -3714,7 +3799,7 @@ struct Engine {
     copy(q_fin, q_cur, NTv());
     if (cfg.b_expl[0] != 0.0) {
       cg_project(stQ[0], uproj);
-      tracer_adv(q_st[0], uproj, q_t, n_tr);
+      tracer_tendency(q_st[0], uproj, q_t);
       axpby(NTv(), cfg.dt * cfg.b_expl[0], q_t, 1.0, q_fin);
     }
   }
@@ -3726,11 +3811,11 @@ struct Engine {
     copy(q_st[i], q_st[0], NTv());
     for (int j = 0; j < i; j++)
       if (cfg.a_expl[i * s + j] != 0.0) {
-        tracer_adv(q_st[j], uproj, q_t, n_tr);
+        tracer_tendency(q_st[j], uproj, q_t);
         axpby(NTv(), cfg.dt * cfg.a_expl[i * s + j], q_t, 1.0, q_st[i]);
       }
     if (cfg.b_expl[i] != 0.0) {
-      tracer_adv(q_st[i], uproj, q_t, n_tr);
+      tracer_tendency(q_st[i], uproj, q_t);
       axpby(NTv(), cfg.dt * cfg.b_expl[i], q_t, 1.0, q_fin);
     }
   }
@@ -4258,6 +4343,7 @@ struct Engine {
     f.add("periodic", (long)cfg.periodic); f.add("length", cfg.length);
     f.add("dg_rtol", cfg.dg_rtol); f.add("dg_restart", (long)cfg.dg_restart); f.add("dg_maxit", (long)cfg.dg_maxit);
     f.add("n_tracers", (long)cfg.n_tracers);
+    for (size_t t = 0; t < tr_kappa.size(); t++) f.add("tracer_kappa[" + std::to_string(t) + "]", tr_kappa[t]);  // only with some kappa != 0
     if (general) {
       f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
       f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
@@ -5291,6 +5377,31 @@ int hdg_transfer_difference(hdg_handle* a, hdg_handle* b, double* norm_Q, double
   HDG_API_BEGIN(a)
   hdg::Engine::transfer_difference(E, *b->eng, r, norm_Q, norm_p, norm_q);
   HDG_API_END(a)
+}
+
+
+// ---- tracer diffusion (include/hdg_tracer_diffusion.h)
+int hdg_set_tracer_diffusivity(hdg_handle* h, int n, const double* kappa) {
+  HDG_API_BEGIN(h)
+  E.set_tracer_diffusivity(n, kappa);
+  HDG_API_END(h)
+}
+int hdg_get_tracer_diffusion_number(hdg_handle* h, double out2[2]) {
+  HDG_API_BEGIN(h)
+  if (!out2) throw std::string("null argument");
+  E.tracer_diffusion_number(out2);
+  HDG_API_END(h)
+}
+int hdg_apply_tracer_diffusion(hdg_handle* h, const double* q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!q || !out) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_apply_tracer_diffusion: a step is open");
+  E.diff_setup();
+  E.tracer_alloc();
+  E.put_P(q, E.wP1);
+  E.apply_tracer_diffusion(E.wP1, E.q_t);
+  E.get_P(E.q_t, out);
+  HDG_API_END(h)
 }
 
 }  // extern "C"

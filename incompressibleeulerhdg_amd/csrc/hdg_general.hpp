@@ -810,6 +810,101 @@ inline void assemble_cg(const GeneralTables& T, const GMesh& M, const GeneralOps
   C.R.val.assign((size_t)nc * nu, 1.0);
 }
 
+// ------------------------------------------------------------------------------------------
+// Tracer diffusion on a general triangulation (the form and its blocks: hdg_tables.hpp,
+// TracerDiffusionTables): M^-1 D assembled once in the orthonormal modal basis psi = Dub / sqrt(detJ) of DG_k, rows and columns
+// c * np + m, with eta_e = (k+1)(k+2)/4 max(P_K / |K|) from the actual perimeters and areas of the two cells of an edge.
+// Boundary edges carry no term.  lambda: the infinity norm of the assembled operator (symmetric in this basis, so >= rho).
+// ------------------------------------------------------------------------------------------
+inline Csr assemble_tracer_diffusion(const GeneralTables& T, const GMesh& M, double& lambda) {
+  const int k = T.k, np = T.np, nc = M.nc;
+  Dubiner U(k);
+  CsrBuilder A(nc * np, nc * np);
+  // reference integrals of the gradient products: Gg[rho][sig][r][m] = int_ref d_rho Dub_r d_sig Dub_m   (exact to degree 2k)
+  std::vector<real> Gg((size_t)4 * np * np, 0), val(np), gx(np), gy(np);
+  {
+    const int mc = k + 1;
+    std::vector<real> xa, wa, xb, wb;
+    gaussJacobi(mc, 0, 0, xa, wa);
+    gaussJacobi(mc, 1, 0, xb, wb);
+    for (int i = 0; i < mc; i++)
+      for (int j = 0; j < mc; j++) {
+        const real eta = (xb[j] + 1) / 2, xi = (xa[i] + 1) / 2 * (1 - eta), w = wa[i] * wb[j] / 8;
+        U.eval(xi, eta, val.data(), gx.data(), gy.data());
+        for (int r = 0; r < np; r++)
+          for (int m = 0; m < np; m++) {
+            Gg[((size_t)0 * np + r) * np + m] += w * gx[r] * gx[m];
+            Gg[((size_t)1 * np + r) * np + m] += w * gx[r] * gy[m];
+            Gg[((size_t)2 * np + r) * np + m] += w * gy[r] * gx[m];
+            Gg[((size_t)3 * np + r) * np + m] += w * gy[r] * gy[m];
+          }
+      }
+  }
+  std::vector<real> ratio((size_t)nc);  // P_K / |K|
+  for (int c = 0; c < nc; c++) {
+    real per = 0;
+    for (int l = 0; l < 3; l++) per += (real)M.elen[(size_t)M.cedge[3 * (size_t)c + l]];
+    ratio[(size_t)c] = per / ((real)M.detJ[c] / 2);
+    // - int_K grad psi_r . grad psi_m = - sum_{rho, sig} (Ji_rho . Ji_sig) Gg[rho][sig]   (detJ of the weights against 1 / detJ)
+    const double* Ji = &M.Jinv[4 * (size_t)c];
+    for (int r = 0; r < np; r++)
+      for (int m = 0; m < np; m++) {
+        real acc = 0;
+        for (int rho = 0; rho < 2; rho++)
+          for (int sig = 0; sig < 2; sig++)
+            acc += ((real)Ji[rho * 2] * Ji[sig * 2] + (real)Ji[rho * 2 + 1] * Ji[sig * 2 + 1]) * Gg[((size_t)(rho * 2 + sig) * np + r) * np + m];
+        A.add(c * np + r, c * np + m, (double)-acc);
+      }
+  }
+  std::vector<real> tq, wq;
+  gaussLegendre01(T.nqe, tq, wq);
+  std::vector<real> v[2], dn[2];
+  for (int sd = 0; sd < 2; sd++) { v[sd].resize(np); dn[sd].resize(np); }
+  std::vector<real> blk[2][2];
+  for (int e = 0; e < M.ne; e++) {
+    if (M.ecell[2 * (size_t)e + 1] < 0) continue;  // a wall: no flux, no term
+    const int cell[2] = {M.ecell[2 * (size_t)e], M.ecell[2 * (size_t)e + 1]};
+    const int loc[2] = {M.elocal[2 * (size_t)e], M.elocal[2 * (size_t)e + 1]};
+    const real sg = (real)M.csig[3 * (size_t)cell[0] + loc[0]], nx = sg * (real)M.enx[e], ny = sg * (real)M.eny[e];  // out of cell[0], the '+' cell
+    const real eta_e = (real)(k + 1) * (k + 2) / 4 * std::max(ratio[(size_t)cell[0]], ratio[(size_t)cell[1]]);
+    const real sign[2] = {1, -1};
+    for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) blk[a][b].assign((size_t)np * np, 0);
+    for (int q = 0; q < T.nqe; q++) {
+      for (int sd = 0; sd < 2; sd++) {
+        const int c = cell[sd];
+        real xi, eta;
+        GMesh::edge_ref(loc[sd], M.cflip[3 * (size_t)c + loc[sd]], tq[q], xi, eta);
+        U.eval(xi, eta, val.data(), gx.data(), gy.data());
+        const real is = 1 / std::sqrt((real)M.detJ[c]);
+        const double* Ji = &M.Jinv[4 * (size_t)c];
+        for (int m = 0; m < np; m++) {
+          v[sd][m] = is * val[m];
+          dn[sd][m] = is * (nx * ((real)Ji[0] * gx[m] + (real)Ji[2] * gy[m]) + ny * ((real)Ji[1] * gx[m] + (real)Ji[3] * gy[m]));
+        }
+      }
+      const real w = wq[q] * (real)M.elen[e];
+      for (int a = 0; a < 2; a++)    // test function on side a
+        for (int b = 0; b < 2; b++)  // trial function on side b
+          for (int r = 0; r < np; r++)
+            for (int m = 0; m < np; m++)
+              blk[a][b][(size_t)r * np + m] += w * (sign[a] * v[a][r] * dn[b][m] / 2 + sign[b] * v[b][m] * dn[a][r] / 2 -
+                                                    sign[a] * sign[b] * eta_e * v[a][r] * v[b][m]);
+    }
+    for (int a = 0; a < 2; a++)
+      for (int b = 0; b < 2; b++)
+        for (int r = 0; r < np; r++)
+          for (int m = 0; m < np; m++) A.add(cell[a] * np + r, cell[b] * np + m, (double)blk[a][b][(size_t)r * np + m]);
+  }
+  Csr out = A.build();
+  lambda = 0.0;
+  for (int r = 0; r < out.nrows; r++) {
+    double sum = 0.0;
+    for (int q = out.rowptr[(size_t)r]; q < out.rowptr[(size_t)r + 1]; q++) sum += std::fabs(out.val[(size_t)q]);
+    lambda = std::max(lambda, sum);
+  }
+  return out;
+}
+
 // element block-Jacobi of the tentative-velocity operator,  (I + gamma sum_e alpha / len_e N_e^T N_e)^-1  per cell
 inline Csr assemble_block_jacobi(const GeneralTables& T, const GMesh& M, const std::vector<CellLocal>& loc, double gamma) {
   const int n2 = T.n2, ne = T.ne;

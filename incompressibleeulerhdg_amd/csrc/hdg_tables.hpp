@@ -18,6 +18,7 @@
 //   global edge directions  H: +x,  V: +y,  D: (x_{i+1},y_j) -> (x_i,y_{j+1})
 //   fixed edge normals n_e  H: (0,1), D: (1,1)/sqrt2, V: (1,0); outward sign L: (-,+,-), U: (+,-,+)
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
@@ -613,6 +614,113 @@ struct Tables {
             D[r * n2 + c] += (real)gamma * alpha / elen[e] * N[s][e][a * n2 + r] * N[s][e][a * n2 + c];
     invert(n2, D);
     return dvec(D.begin(), D.end());
+  }
+};
+
+// ------------------------------------------------------------------------------------------
+// Tracer diffusion: the symmetric interior-penalty form on DG_k with no-flux walls,
+//   D(chi, q) = - sum_K int_K grad chi . grad q + sum_{interior e} int_e ( [chi]{grad q . n} + [q]{grad chi . n} - eta [chi][q] ),
+//   [v] = v+ - v-, {g} = (g+ + g-)/2, n out of the '+' cell, eta = (k+1)(k+2)/4 max(P_K / |K|)  (P = perimeter),
+// in the orthonormal modal basis of DG_k (mass = identity, so these ARE the blocks of M^-1 D), np x np row-major, for mesh
+// width h.  On the structured mesh every cell has P / |K| = 2 (2 + sqrt 2) / h.  Seen from a cell of shape s ('+' = this cell):
+//   Vol[s]     - int_K grad psi_r . grad psi_m
+//   Own[s][e]  int_e ( psi_r dn psi_m / 2 + psi_m dn psi_r / 2 - eta psi_r psi_m ),     this cell's modes on both sides
+//   Nbr[s][e]  int_e ( psi_r dn psi'_m / 2 - psi'_m dn psi_r / 2 + eta psi_r psi'_m ),  psi' = the modes of the neighbour, which
+//              is local edge e of shape 1 - s; dn = the derivative along this cell's outward normal
+// A cell's row of M^-1 D q is Vol q_K + sum_{e with a neighbour} (Own[e] q_K + Nbr[e] q_K').  The volume rule is exact to degree
+// 2k (k + 1 collapsed Gauss-Jacobi points a side), the edge rule is the advection form's (ceil((3k+4)/2) points, exact to 3k+3).
+// lambda: the largest absolute row sum over both shapes and every set of edges with a neighbour; the operator is symmetric in
+// this basis, so lambda >= rho(M^-1 D) on every mesh these cells tile.
+// ------------------------------------------------------------------------------------------
+struct TracerDiffusionTables {
+  int k, np;
+  double h, eta, lambda;
+  dvec Vol[2], Own[2][3], Nbr[2][3];
+
+  TracerDiffusionTables(int k_, double h_) : k(k_), np(n_scalar(k_)), h(h_) {
+    const real rh = h, s2 = std::sqrt((real)2);
+    const real eta_ = (real)(k + 1) * (k + 2) / 4 * 2 * (2 + s2) / rh;
+    eta = (double)eta_;
+    const real nfix[3][2] = {{0, 1}, {1 / s2, 1 / s2}, {1, 0}};
+    const real sg[2][3] = {{-1, 1, -1}, {1, -1, 1}}, elen_[3] = {rh, s2 * rh, rh};
+    Dubiner U(k);
+    std::vector<real> val(np), gx(np), gy(np), vn(np), nx_(np), ny_(np), dno(np), dnn(np);
+    auto edge_ref = [](int s, int e, real t, real& xi, real& et) {  // as in Tables: the point with GLOBAL edge parameter t
+      if (s == 0) {
+        if (e == 0) { xi = t; et = 0; }
+        else if (e == 1) { xi = 1 - t; et = t; }
+        else { xi = 0; et = t; }
+      } else {
+        if (e == 0) { xi = 1 - t; et = 0; }
+        else if (e == 1) { xi = t; et = 1 - t; }
+        else { xi = 0; et = 1 - t; }
+      }
+    };
+    // volume: grad_x psi = sgn / h^2 grad_xi Dub, |K| weights h^2 w: the same block for both shapes
+    {
+      const int mc = k + 1;
+      std::vector<real> xa, wa, xb, wb, V((size_t)np * np, 0);
+      gaussJacobi(mc, 0, 0, xa, wa);
+      gaussJacobi(mc, 1, 0, xb, wb);
+      for (int i = 0; i < mc; i++)
+        for (int j = 0; j < mc; j++) {
+          const real et = (xb[j] + 1) / 2, xi = (xa[i] + 1) / 2 * (1 - et), w = wa[i] * wb[j] / 8;
+          U.eval(xi, et, val.data(), gx.data(), gy.data());
+          for (int r = 0; r < np; r++)
+            for (int m = 0; m < np; m++) V[(size_t)r * np + m] -= w * (gx[r] * gx[m] + gy[r] * gy[m]) / (rh * rh);
+        }
+      for (int s = 0; s < 2; s++) Vol[s].assign(V.begin(), V.end());
+    }
+    const int nqe = (3 * k + 4 + 1) / 2;
+    std::vector<real> tq, wq;
+    gaussLegendre01(nqe, tq, wq);
+    for (int s = 0; s < 2; s++) {
+      const real sgn = s == 0 ? 1 : -1;
+      for (int e = 0; e < 3; e++) {
+        const real nx = sg[s][e] * nfix[e][0], ny = sg[s][e] * nfix[e][1];  // this cell's outward normal
+        std::vector<real> O((size_t)np * np, 0), N((size_t)np * np, 0);
+        for (int q = 0; q < nqe; q++) {
+          real xi, et;
+          edge_ref(s, e, tq[q], xi, et);
+          U.eval(xi, et, val.data(), gx.data(), gy.data());
+          for (int m = 0; m < np; m++) { val[m] /= rh; dno[m] = sgn * (nx * gx[m] + ny * gy[m]) / (rh * rh); }
+          edge_ref(1 - s, e, tq[q], xi, et);
+          U.eval(xi, et, vn.data(), nx_.data(), ny_.data());
+          for (int m = 0; m < np; m++) { vn[m] /= rh; dnn[m] = -sgn * (nx * nx_[m] + ny * ny_[m]) / (rh * rh); }
+          const real w = wq[q] * elen_[e];
+          for (int r = 0; r < np; r++)
+            for (int m = 0; m < np; m++) {
+              O[(size_t)r * np + m] += w * (val[r] * dno[m] / 2 + val[m] * dno[r] / 2 - eta_ * val[r] * val[m]);
+              N[(size_t)r * np + m] += w * (val[r] * dnn[m] / 2 - vn[m] * dno[r] / 2 + eta_ * val[r] * vn[m]);
+            }
+        }
+        Own[s][e].assign(O.begin(), O.end());
+        Nbr[s][e].assign(N.begin(), N.end());
+      }
+    }
+    lambda = 0.0;
+    for (int s = 0; s < 2; s++)
+      for (int mask = 0; mask < 8; mask++)
+        for (int r = 0; r < np; r++) {
+          double sum = 0.0;
+          for (int m = 0; m < np; m++) {
+            double d = Vol[s][(size_t)r * np + m];
+            for (int e = 0; e < 3; e++)
+              if (mask >> e & 1) { d += Own[s][e][(size_t)r * np + m]; sum += std::fabs(Nbr[s][e][(size_t)r * np + m]); }
+            sum += std::fabs(d);
+          }
+          lambda = std::max(lambda, sum);
+        }
+  }
+  // device layout: per shape s the seven blocks Vol, Own[0..2], Nbr[0..2], each np x np row-major
+  dvec packed() const {
+    dvec out;
+    for (int s = 0; s < 2; s++) {
+      out.insert(out.end(), Vol[s].begin(), Vol[s].end());
+      for (int e = 0; e < 3; e++) out.insert(out.end(), Own[s][e].begin(), Own[s][e].end());
+      for (int e = 0; e < 3; e++) out.insert(out.end(), Nbr[s][e].begin(), Nbr[s][e].end());
+    }
+    return out;
   }
 };
 

@@ -82,6 +82,9 @@ def build_parser():
     parser.add_argument("--animation", action="store_true", default=False,
                         help="save velocity and pressure fields at the end of each timestep as an animation")
     parser.add_argument("--tracer_advection", action="store_true", default=False, help="advect tracer field")
+    parser.add_argument("--tracer_diffusivity", metavar="K", type=float, nargs="+", default=None,
+                        help="molecular diffusivity of the tracers (with --tracer_advection): one value for all of them or "
+                             "exactly --tracers values; explicit in time, see the printed diffusion number")
     parser.add_argument("--tracers", metavar="N", type=int, default=1,
                         help="number of passive tracers advected through the one flow (with --tracer_advection); tracer m "
                              "starts from sin(2 pi (m+1) x) sin(2 pi (m+1) y)")
@@ -160,6 +163,15 @@ def check_tracers(args):
         raise RuntimeError(f"--tracers must be in 1 .. {HDG_MAX_TRACERS} (got {args.tracers})")
     if args.tracers > 1 and not args.tracer_advection:
         raise RuntimeError(f"--tracers {args.tracers} needs --tracer_advection")
+    kappa = args.tracer_diffusivity
+    if kappa is not None:
+        if not args.tracer_advection:
+            raise RuntimeError("--tracer_diffusivity needs --tracer_advection")
+        if len(kappa) not in (1, args.tracers):
+            raise RuntimeError(f"--tracer_diffusivity takes one value or --tracers = {args.tracers} values (got {len(kappa)})")
+        for m, x in enumerate(kappa):
+            if not (np.isfinite(x) and x >= 0):
+                raise RuntimeError(f"--tracer_diffusivity: value {m} ({x}) is not a finite number >= 0")
 
 
 def check_checkpoint(args):
@@ -395,6 +407,9 @@ def main(argv=None):
 def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     """The timestepper the arguments ask for, on the given mesh with the given degree and timestep size."""
     several = {"n_tracers": args.tracers} if args.tracers > 1 else {}
+    if args.tracer_diffusivity is not None:
+        kappa = args.tracer_diffusivity
+        several["tracer_diffusivity"] = kappa[0] if len(kappa) == 1 else kappa
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
@@ -463,6 +478,9 @@ def _run(args, ranks):
     print(f"advect tracer = {args.tracer_advection}")
     if args.tracers > 1:
         print(f"number of tracers = {args.tracers}")
+    if args.tracer_diffusivity is not None:
+        print(f"tracer diffusivity = {' '.join(repr(x) for x in args.tracer_diffusivity)}")
+        print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g} (limit {timestepper.diffusion_limit:.6g})")
     print(f"timestepping method = {timestepper.label}")
     print()
 

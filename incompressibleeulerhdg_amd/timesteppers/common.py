@@ -4,6 +4,7 @@ Same class surface as the reference; the bodies call the HIP engine through the 
 """
 
 import os
+import warnings
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -13,6 +14,42 @@ from ..auxilliary.logging import PerformanceLog
 from ..mesh import Function, FunctionSpace
 
 __all__ = ["IncompressibleEuler"]
+
+
+def explicit_stability_limit(a_expl, b_expl):
+    """The real-axis stability limit of an explicit tableau: the right end x of the interval [0, x] on which
+    |R(-x)| <= 1, R(z) = 1 + z b^T (I - z A)^-1 1 (a polynomial, A being strictly lower triangular).  Forward Euler: 2."""
+    b = np.asarray(b_expl, dtype=float).reshape(-1)
+    A = np.asarray(a_expl, dtype=float).reshape(len(b), len(b))
+    coef, v = [1.0], np.ones(len(b))
+    for m in range(len(b)):  # R(-x) = sum_m (-x)^m b^T A^(m-1) 1
+        coef.append((-1.0) ** (m + 1) * float(b @ v))
+        v = A @ v
+    p = np.array(coef)  # ascending powers of x
+    while len(p) > 1 and p[-1] == 0.0:
+        p = p[:-1]
+    if len(p) == 1:
+        return float("inf")
+    roots = []
+    for target in (1.0, -1.0):  # where R(-x) meets 1 (the root x = 0 divided out) and -1
+        r = p.copy()
+        r[0] -= target
+        if target > 0:
+            r = r[1:]
+        roots += [z.real for z in np.atleast_1d(np.roots(r[::-1])) if abs(z.imag) <= 1e-12 * max(1.0, abs(z)) and z.real > 0]
+    for x in sorted(roots):  # the first one behind which |R| has left [0, 1] (a root where it only touches 1 is passed over)
+        if abs(np.polyval(p[::-1], x * (1 + 1e-6))) > 1.0:
+            return float(x)
+    return float("inf")
+
+
+def warn_if_diffusion_unstable(number, limit, what="tracer diffusion"):
+    """The explicit diffusion term is stable while kappa_max dt rho(M^-1 D) <= limit; `number` is built from an upper bound of
+    the spectral radius, so exceeding the limit is a warning, not an error."""
+    if number > limit:
+        warnings.warn(f"{what}: the diffusion number kappa_max dt Lambda = {number:.4g} exceeds the stability limit {limit:.4g} of "
+                      "the explicit tableau (Lambda is an upper bound of the spectral radius): the run may blow up; reduce dt "
+                      "or the diffusivity", RuntimeWarning, stacklevel=3)
 
 
 class IncompressibleEuler(ABC):
@@ -28,6 +65,8 @@ class IncompressibleEuler(ABC):
         self.degree = degree
         self._dt = dt
         self._label = label
+        # tracer_diffusivity=: kappa of every tracer (a scalar or n_tracers values); None: no call at all
+        self._tracer_diffusivity = engine_options.pop("tracer_diffusivity", None)
         self._engine_options = engine_options
         self._engine = None
         # common.py:72-73
@@ -56,6 +95,10 @@ class IncompressibleEuler(ABC):
             V._engine = self._engine  # device operations on a Function (vorticity callback)
         self._V_trace = ("DGT", k, self._engine.n_edges * self._engine.n_l)
         self._V = (self._V_Q, self._V_p, self._V_trace)
+        if self._tracer_diffusivity is not None:
+            self._engine.set_tracer_diffusivity(self._tracer_diffusivity)
+            self.diffusion_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
+            warn_if_diffusion_unstable(self._engine.tracer_diffusion_number()[1], self.diffusion_limit)
         return self._engine
 
     def _as_nodal_velocity(self, Q):
