@@ -35,6 +35,8 @@
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
 #include "hdg_kernels.hpp"
+#include "hdg_vertex_levels.hpp"
+#include "hdg_vertex_mg.hpp"
 #include "hdg_schur_mfma.hpp"
 #include "hdg_trace_tile.hpp"
 #include "hdg_trace_tile3.hpp"
@@ -140,7 +142,6 @@ struct Engine {
   const DevTables& pdt() const { return psets[cur_pset].dt; }
   void use_pset(int i) { cur_pset = i; cheb_lmin = psets[i].lmin; cheb_lmax = psets[i].lmax; }
   // multigrid levels (vertex grids)
-  std::vector<int> mg_n;
   std::vector<double*> mg_x, mg_b, mg_r;
   // stats
   double it_sum[4] = {0, 0, 0, 0};
@@ -2215,129 +2216,162 @@ struct Engine {
       rho = rn;
     }
   }
+  // ---- vertex-grid V-cycle.  Which form a level runs as is decided in ONE place, the level plan (hdg_vertex_levels.hpp, built
+  // in setup_trace_solver); the kernels of every form are in hdg_vertex_mg.hpp, each for both grids (PER: the periodic square).
+  VertexPlan vplan;
+  // trace_cg_sr with the tile preconditioner: the half of the update nothing reads before the next update (p, x) rides on the
+  // leg launches of the V-cycle (k_p1_down / k_p1_up side jobs, hdg_vertex_mg.hpp: SideXP), a share of the pairs per leg by
+  // weight (VertexPlan::side_weight_sum); what the legs did not take (no Legs level, rounding of the shares) is done by
+  // finish() as a launch of its own.  (A second stream underneath the cycle was measured and removed: DESIGN.md section 9.)
+  // The CG sets pending and x, trace_precond brackets the cycle with begin / finish, the V-cycle takes its slices.
+  struct XpRide {
+    Engine* e;
+    bool pending = false;  // the CG has queued the p / x half of its update
+    double* x = nullptr;   // the iterate it updates
+    long done = 0;         // pairs already handed to side jobs
+    double wsum = 0.0;     // sum of the leg weights of one cycle
+    bool riding = false;
+    void begin(const VertexPlan& pl) {
+      done = 0; riding = false;
+      if (!pending) return;
+      // strips: the finest level is distributed (vcycle_distributed_top launches its legs itself); the replicated levels carry the update
+      wsum = pl.side_weight_sum(e->mg_distributed() ? 1 : 0, e->opt.cg_xp_w0);
+      riding = wsum > 0.0;
+    }
+    SideXP slice(int lev, int nt, int& extra_rows) {
+      extra_rows = 0;
+      SideXP sj{};
+      if (!riding) return sj;
+      const long total = e->NLv >> 1;
+      long cnt = (long)std::ceil((double)total * VertexPlan::side_weight(lev, e->opt.cg_xp_w0) / wsum);
+      cnt = std::min(cnt, total - done);
+      if (cnt <= 0) return sj;
+      sj = SideXP{e->d_cgs, e->cg_z, e->tr_one, e->cg_p, x, done, done + cnt};
+      done += cnt;
+      const long blocks = (cnt + HDG_P1_THREADS - 1) / HDG_P1_THREADS;
+      extra_rows = (int)((blocks + nt - 1) / nt);
+      return sj;
+    }
+    void finish() {
+      if (!pending) return;
+      pending = false;
+      const long taken = riding ? done : 0;
+      riding = false; done = 0;
+      const long NLv = e->NLv;
+      if (taken < (NLv >> 1) || (NLv & 1))
+        k_cg_sr_update_xp<<<e->vec_blocks(NLv - 2 * taken), 256, 0, e->stream>>>(NLv, e->d_cgs, e->cg_z, e->tr_one, e->cg_p, x, taken);
+    }
+  };
+  XpRide xp{this};
+  template <bool PER>
   void p1_smooth(int lev, int sweeps, bool reverse) {
-    int n = mg_n[lev];
-    dim3 grid((n + 1 + 63) / 64, n + 1);
+    const VLevel& v = vplan.lev[lev];
+    const dim3 grid((v.pitch + 63) / 64, v.pitch);
     for (int sw = 0; sw < sweeps; sw++) {
-      k_p1_rbgs<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], reverse ? 1 : 0);
-      k_p1_rbgs<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], reverse ? 0 : 1);
+      k_p1_rbgs<PER><<<grid, 64, 0, stream>>>(v.n, mg_x[lev], mg_b[lev], reverse ? 1 : 0);
+      k_p1_rbgs<PER><<<grid, 64, 0, stream>>>(v.n, mg_x[lev], mg_b[lev], reverse ? 0 : 1);
     }
   }
-  void vcycle(int lev) {
-    int n = mg_n[lev];
-    long nv = (long)(n + 1) * (n + 1);
-    const int nsw = opt.mg_sweeps, ncoarse = opt.mg_coarse;
-    if (opt.mg_tail && n <= 32) {
-      // all remaining levels fit one workgroup's LDS: run the tail of the V-cycle in a single kernel
-      P1Tail tl;
-      tl.nlev = 0;
-      long tot = 0;
-      for (int l = lev; l < (int)mg_n.size() && tl.nlev < 8; l++) { tl.n[tl.nlev++] = mg_n[l]; tot += (long)(mg_n[l] + 1) * (mg_n[l] + 1); }
-      if (tot <= HDG_P1_TAIL_MAX && lev + tl.nlev == (int)mg_n.size()) {
-        tally(LC_MG, 16.0 * tot);
-        if (tail_M && lev == tail_lev) {  // the same linear map as one dense matrix (k_p1_dense_tail)
-          const int N = (n + 1) * (n + 1);
-          k_p1_dense_tail<<<(N + 3) / 4, 256, 0, stream>>>(N, tail_pitch, tail_M, mg_b[lev], mg_x[lev]);
-          return;
-        }
-        k_p1_vcycle_tail<<<1, 1024, 0, stream>>>(tl, mg_b[lev], mg_x[lev], nsw, ncoarse);
+  static P1Tail tail_levels(const VertexPlan& pl) {
+    P1Tail tl;
+    tl.nlev = 0;
+    for (int l = pl.size() - pl.tail_nlev; l < pl.size(); l++) tl.n[tl.nlev++] = pl.lev[l].n;
+    return tl;
+  }
+  // one V(nsw,nsw) cycle from level `lev` down: right-hand side mg_b[lev], result mg_x[lev].  `pl` has the hierarchy of vplan
+  // (the buffers are per level); `ride`: the side jobs the legs carry (null: none)
+  void vcycle(const VertexPlan& pl, int lev, XpRide* ride) {
+    with_bool(pl.periodic, [&](auto per) { vcycle_on<decltype(per)::value>(pl, lev, ride); });
+  }
+  template <bool PER>
+  void vcycle_on(const VertexPlan& pl, int lev, XpRide* ride) {
+    const VLevel& v = pl.lev[lev];
+    const int n = v.n, nsw = opt.mg_sweeps, ncoarse = opt.mg_coarse;
+    const dim3 grid((v.pitch + 63) / 64, v.pitch);
+    switch (v.form) {
+      case VForm::DenseTail: {  // the rest of the cycle as one dense matrix (build_dense_tail)
+        if (!tail_M || lev != pl.dense_lev) throw std::string("vertex-grid V-cycle: dense tail entered at a level it was not built for");
+        const int N = (int)v.nv;
+        tally(LC_MG, 16.0 * (PER ? (long)N : pl.tail_vertices()));
+        k_p1_dense_tail<<<(N + 3) / 4, 256, 0, stream>>>(N, tail_pitch, tail_M, mg_b[lev], mg_x[lev]);
+        return;
+      }
+      case VForm::TailKernel: {  // all remaining levels fit one workgroup's LDS: the rest of the cycle in a single kernel
+        if (PER || lev != pl.size() - pl.tail_nlev) throw std::string("vertex-grid V-cycle: one-workgroup tail entered at a level it does not start at");
+        tally(LC_MG, 16.0 * pl.tail_vertices());
+        k_p1_vcycle_tail<<<1, 1024, 0, stream>>>(tail_levels(pl), mg_b[lev], mg_x[lev], nsw, ncoarse);
+        return;
+      }
+      case VForm::Coarsest:
+        zero(mg_x[lev], v.nv);
+        p1_smooth<PER>(lev, ncoarse, false);
+        p1_smooth<PER>(lev, ncoarse, true);
+        return;
+      case VForm::Legs: {  // one kernel per leg (LDS tiles with recomputed halos), bit-identical to the per-level launches
+        const int nt = (v.pitch + HDG_P1_TS - 1) / HDG_P1_TS;
+        auto leg = [&](bool down) {
+          // down: reads b, writes the pre-smoothed x and the coarse right-hand side; up: reads the coarse x, b, the pre-smoothed x, writes x
+          tally(LC_MG, 8.0 * v.nv * (down ? 2.25 : 3.25));
+          int extra = 0;
+          const SideXP sj = ride ? ride->slice(lev, nt, extra) : SideXP{};
+          const dim3 gl(nt, nt + extra);
+          const int period = side_row_period(nt, extra);  // hdg_side_rows.hpp
+          auto launch = [&](auto s) {
+            constexpr int NSW = decltype(s)::value;
+            if (down) k_p1_down<NSW, PER><<<gl, HDG_P1_THREADS, 0, stream>>>(n, mg_b[lev], mg_r[lev], mg_b[lev + 1], 0, extra, period, sj);
+            else k_p1_up<NSW, PER><<<gl, HDG_P1_THREADS, 0, stream>>>(n, mg_x[lev + 1], mg_b[lev], mg_r[lev], mg_x[lev], 0, extra, period, sj);
+          };
+          if constexpr (PER) with_int<2>(nsw, "smoothing sweeps of a fused leg (periodic square)", launch);
+          else with_int<1, 2, 3>(nsw, "smoothing sweeps of a fused leg", launch);
+        };
+        leg(true);
+        vcycle_on<PER>(pl, lev + 1, ride);
+        leg(false);
+        return;
+      }
+      case VForm::PerLevel: {
+        const VLevel& c = pl.lev[lev + 1];
+        zero(mg_x[lev], v.nv);
+        p1_smooth<PER>(lev, nsw, false);
+        k_p1_residual<PER><<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], mg_r[lev]);
+        k_p1_restrict<PER><<<dim3((c.pitch + 63) / 64, c.pitch), 64, 0, stream>>>(c.n, mg_r[lev], mg_b[lev + 1]);
+        vcycle_on<PER>(pl, lev + 1, ride);
+        k_p1_prolong_add<PER><<<grid, 64, 0, stream>>>(c.n, mg_x[lev + 1], mg_x[lev]);
+        p1_smooth<PER>(lev, nsw, true);
         return;
       }
     }
-    if (lev == (int)mg_n.size() - 1) {
-      zero(mg_x[lev], nv);
-      p1_smooth(lev, ncoarse, false);
-      p1_smooth(lev, ncoarse, true);
-      return;
-    }
-    if (opt.mg_fuse && nsw >= 1 && nsw <= HDG_P1_MAXSW && (n & 1) == 0) {
-      // one kernel per leg (LDS tiles with recomputed halos), bit-identical to the launches below
-      const int nt = (n + 1 + HDG_P1_TS - 1) / HDG_P1_TS;
-      auto down = [&](auto tag) {
-        constexpr int NSW = decltype(tag)::value;
-        tally(LC_MG, 8.0 * nv * 2.25);  // reads b, writes the pre-smoothed x and the coarse right-hand side
-        int extra = 0;
-        const SideXP sj = xp_side_slice(lev, nt, extra);
-        k_p1_down<NSW><<<dim3(nt, nt + extra), HDG_P1_THREADS, 0, stream>>>(n, mg_b[lev], mg_r[lev], mg_b[lev + 1], 0, extra, xp_period(nt, extra), sj);
-      };
-      auto up = [&](auto tag) {
-        constexpr int NSW = decltype(tag)::value;
-        tally(LC_MG, 8.0 * nv * 3.25);  // reads the coarse x, b, the pre-smoothed x, writes x
-        int extra = 0;
-        const SideXP sj = xp_side_slice(lev, nt, extra);
-        k_p1_up<NSW><<<dim3(nt, nt + extra), HDG_P1_THREADS, 0, stream>>>(n, mg_x[lev + 1], mg_b[lev], mg_r[lev], mg_x[lev], 0, extra, xp_period(nt, extra), sj);
-      };
-      with_int<1, 2, 3>(nsw, "smoothing sweeps of a fused leg", down);
-      vcycle(lev + 1);
-      with_int<1, 2, 3>(nsw, "smoothing sweeps of a fused leg", up);
-      return;
-    }
-    zero(mg_x[lev], nv);
-    p1_smooth(lev, nsw, false);
-    dim3 grid((n + 1 + 63) / 64, n + 1);
-    k_p1_residual<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], mg_r[lev]);
-    int nc = mg_n[lev + 1];
-    dim3 gridc((nc + 1 + 63) / 64, nc + 1);
-    k_p1_restrict<<<gridc, 64, 0, stream>>>(nc, mg_r[lev], mg_b[lev + 1]);
-    vcycle(lev + 1);
-    k_p1_prolong_add<<<grid, 64, 0, stream>>>(nc, mg_x[lev + 1], mg_x[lev]);
-    p1_smooth(lev, nsw, true);
   }
-  void run_vcycle() { if (periodic) vcycle_periodic(0); else vcycle(0); }
-  // Dense form of the V-cycle tail (k_p1_dense_tail): column c of M = the tail kernel applied to the c-th unit vector.
-  // Built once per engine (one launch: a workgroup per unit vector); HDG_MG_NO_DENSE_TAIL keeps the tail kernel.
+  // Dense form of the V-cycle tail (k_p1_dense_tail), built once per engine where the plan has one: column c of M = the tail
+  // applied to the c-th unit vector.  Unit square: one launch of the tail kernel, a workgroup per unit vector.  Periodic
+  // square: the per-level cycle from the tail's level applied to each unit vector in turn (n^2 <= 1024 columns of ~45 small
+  // launches, a few tenths of a second), through a plan of the same hierarchy with the legs and the dense tail switched off.
   double* tail_M = nullptr;
-  int tail_lev = -1, tail_pitch = 0;
+  int tail_pitch = 0;
   void build_dense_tail() {
-    if (!opt.mg_dense_tail || periodic || general || mg_n.empty()) return;
-    int lev = 0;
-    while (lev < (int)mg_n.size() && mg_n[lev] > 32) lev++;
-    if (lev >= (int)mg_n.size() - 1) return;  // no tail, or a single level: nothing to gain
-    long tot = 0;
-    for (int l = lev; l < (int)mg_n.size(); l++) tot += (long)(mg_n[l] + 1) * (mg_n[l] + 1);
-    if (tot > HDG_P1_TAIL_MAX || (int)mg_n.size() - lev > 8) return;
-    const int N = (mg_n[lev] + 1) * (mg_n[lev] + 1), pitch = (N + 1) & ~1;
+    const int lev = vplan.dense_lev;
+    if (lev < 0) return;
+    const int N = (int)vplan.lev[lev].nv, pitch = (N + 1) & ~1;
     double* MT = dalloc((long)N * pitch);
     double* M = dalloc((long)N * pitch);
-    {
-      // every column in one launch: workgroup c applies the tail kernel to the c-th unit vector
-      P1Tail tl;
-      tl.nlev = 0;
-      for (int l = lev; l < (int)mg_n.size(); l++) tl.n[tl.nlev++] = mg_n[l];
-      k_p1_vcycle_tail<<<N, 1024, 0, stream>>>(tl, nullptr, MT, opt.mg_sweeps, opt.mg_coarse, pitch);
+    if (!periodic) k_p1_vcycle_tail<<<N, 1024, 0, stream>>>(tail_levels(vplan), nullptr, MT, opt.mg_sweeps, opt.mg_coarse, pitch);
+    else {
+      Options per_level = opt;
+      per_level.mg_fuse = false; per_level.mg_dense_tail_periodic = false;
+      const VertexPlan pl = vertex_plan(g.nx, true, per_level);
+      const double one = 1.0;
+      for (int c = 0; c < N; c++) {
+        zero(mg_b[lev], N);
+        HIPCHECK(hipMemcpyAsync(mg_b[lev] + c, &one, sizeof(double), hipMemcpyHostToDevice, stream));
+        vcycle(pl, lev, nullptr);
+        HIPCHECK(hipMemcpyAsync(MT + (long)c * pitch, mg_x[lev], sizeof(double) * N, hipMemcpyDeviceToDevice, stream));
+      }
     }
     k_transpose_sq<<<dim3((N + 255) / 256, N), 256, 0, stream>>>(N, pitch, MT, M);
     HIPCHECK(hipStreamSynchronize(stream));
     HIPCHECK(hipFree(MT));
     allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)MT));
-    tail_M = M; tail_lev = lev; tail_pitch = pitch;
-  }
-  // periodic vertex grids: column c of the tail's matrix = the per-level V-cycle from the first level with n <= 32 applied to the
-  // c-th unit vector (n^2 <= 1024 columns of ~45 small launches each, once per engine: a few tenths of a second)
-  bool building_tail = false;
-  void build_dense_tail_periodic() {
-    if (!opt.mg_dense_tail_periodic || !periodic || mg_n.empty()) return;
-    int lev = 0;
-    while (lev < (int)mg_n.size() && mg_n[lev] > 32) lev++;
-    if (lev == 0 || lev >= (int)mg_n.size() - 1) return;  // no level above the tail (nothing fused), or a single level: nothing to gain
-    const int n = mg_n[lev], N = n * n, pitch = (N + 1) & ~1;
-    if (N > 1024) return;
-    double* MT = dalloc((long)N * pitch);
-    double* M = dalloc((long)N * pitch);
-    building_tail = true;
-    const double one = 1.0;
-    for (int c = 0; c < N; c++) {
-      zero(mg_b[lev], N);
-      HIPCHECK(hipMemcpyAsync(mg_b[lev] + c, &one, sizeof(double), hipMemcpyHostToDevice, stream));
-      vcycle_periodic(lev);
-      HIPCHECK(hipMemcpyAsync(MT + (long)c * pitch, mg_x[lev], sizeof(double) * N, hipMemcpyDeviceToDevice, stream));
-    }
-    building_tail = false;
-    k_transpose_sq<<<dim3((N + 255) / 256, N), 256, 0, stream>>>(N, pitch, MT, M);
-    HIPCHECK(hipStreamSynchronize(stream));
-    HIPCHECK(hipFree(MT));
-    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)MT));
-    tail_M = M; tail_lev = lev; tail_pitch = pitch;
+    tail_M = M; tail_pitch = pitch;
   }
   // ---- strip partition: the finest vertex grid stays distributed, the rest of the V-cycle is replicated.
   // The replicated cycle (every rank gathers the whole (nx+1)^2 right-hand side, 8.4 MB at C3, and runs every level)
@@ -2352,12 +2386,13 @@ struct Engine {
   // Needs ny a multiple of 32 and >= 64 (C3 on 8 ranks: 128); otherwise the replicated cycle is used.
   static constexpr int MG_HALO = 40;
   bool mg_distributed() const {
-    return !opt.mg_replicated && opt.mg_fuse && opt.mg_sweeps == 2 && mg_gather && comm->size > 1 && !periodic && halo_on && mg_n.size() >= 2 &&
-           mg_n[0] > 32 && (g.ny % HDG_P1_TS) == 0 && g.ny >= 2 * HDG_P1_TS && (g.nx & 1) == 0 &&
+    // (a Legs level 0 means: fused legs on, a coarser level exists, n even; the distributed legs are built for two sweeps)
+    return !opt.mg_replicated && opt.mg_sweeps == 2 && mg_gather && comm->size > 1 && !periodic && halo_on && !vplan.lev.empty() &&
+           vplan.lev[0].form == VForm::Legs && vplan.lev[0].n > 32 && (g.ny % HDG_P1_TS) == 0 && g.ny >= 2 * HDG_P1_TS &&
            (size_t)(MG_HALO + 1) * (g.nx + 1) <= cap_halo;
   }
   void vcycle_distributed_top() {
-    const int n = mg_n[0], st = n + 1, J0 = g.joff, J1 = g.joff + g.ny;
+    const int n = vplan.lev[0].n, st = n + 1, J0 = g.joff, J1 = g.joff + g.ny;
     const bool has_lo = comm->rank > 0, has_hi = comm->rank < comm->size - 1;
     // halo of the level-0 right-hand side: lower message = rows J0 .. J0+40 (partial cut row first), upper = rows J1-40 .. J1
     const size_t nmsg = (size_t)(MG_HALO + 1) * st;
@@ -2372,55 +2407,12 @@ struct Engine {
     const dim3 gt(nt, t1 - t0);
     k_p1_down<2><<<gt, HDG_P1_THREADS, 0, stream>>>(n, mg_b[0], mg_r[0], mg_b[1], t0);
     // level-1 right-hand side: every rank contributes its ny/2 + 1 coarse rows (the cut rows are computed twice, identically)
-    const int nc = mg_n[1], stc = nc + 1, nyc2 = g.ny / 2;
+    const int nc = vplan.lev[1].n, stc = nc + 1, nyc2 = g.ny / 2;
     comm->allgather(mg_b[1] + (long)(J0 / 2) * stc, mg_gather, (size_t)(nyc2 + 1) * stc, stream);
     n_gather++;
     k_p1_assemble<<<vec_blocks((long)stc * stc), 256, 0, stream>>>(comm->size, nyc2, stc, mg_gather, mg_b[1], 0);
-    vcycle(1);
+    vcycle(vplan, 1, &xp);
     k_p1_up<2><<<gt, HDG_P1_THREADS, 0, stream>>>(n, mg_x[1], mg_b[0], mg_r[0], mg_x[0], t0);
-  }
-  // the same V(2,2) cycle on the periodic vertex grids (per-level kernels)
-  void vcycle_periodic(int lev) {
-    const int n = mg_n[lev];
-    const long nv = (long)n * n;
-    const int nsw = opt.mg_sweeps, ncoarse = opt.mg_coarse;
-    const dim3 grid((n + 63) / 64, n);
-    auto sweeps = [&](int cnt, bool reverse) {
-      for (int sw = 0; sw < cnt; sw++) {
-        k_p1p_rbgs<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], reverse ? 1 : 0);
-        k_p1p_rbgs<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], reverse ? 0 : 1);
-      }
-    };
-    // second half of round 4: the fused LDS-tile legs (k_p1_down / k_p1_up, PER = true: wrapped loads, every vertex interior) for
-    // n > 32 and the tail n <= 32 as one dense product (build_dense_tail_periodic), as on the unit square; the legs carry the
-    // p / x half of the CG update as side jobs there too.  HDG_MG_NO_FUSE / HDG_MG_NO_DENSE_TAIL: the per-level kernels below.
-    if (tail_M && lev == tail_lev) {
-      const int N = n * n;
-      tally(LC_MG, 16.0 * N);
-      k_p1_dense_tail<<<(N + 3) / 4, 256, 0, stream>>>(N, tail_pitch, tail_M, mg_b[lev], mg_x[lev]);
-      return;
-    }
-    if (opt.mg_fuse && nsw == 2 && n > 32 && lev + 1 < (int)mg_n.size() && !building_tail) {
-      const int nt = (n + HDG_P1_TS - 1) / HDG_P1_TS;
-      int extra = 0;
-      SideXP sj = xp_side_slice(lev, nt, extra);
-      tally(LC_MG, 8.0 * nv * 2.25);
-      k_p1_down<2, true><<<dim3(nt, nt + extra), HDG_P1_THREADS, 0, stream>>>(n, mg_b[lev], mg_r[lev], mg_b[lev + 1], 0, extra, xp_period(nt, extra), sj);
-      vcycle_periodic(lev + 1);
-      sj = xp_side_slice(lev, nt, extra);
-      tally(LC_MG, 8.0 * nv * 3.25);
-      k_p1_up<2, true><<<dim3(nt, nt + extra), HDG_P1_THREADS, 0, stream>>>(n, mg_x[lev + 1], mg_b[lev], mg_r[lev], mg_x[lev], 0, extra, xp_period(nt, extra), sj);
-      return;
-    }
-    zero(mg_x[lev], nv);
-    if (lev == (int)mg_n.size() - 1) { sweeps(ncoarse, false); sweeps(ncoarse, true); return; }
-    sweeps(nsw, false);
-    k_p1p_residual<<<grid, 64, 0, stream>>>(n, mg_x[lev], mg_b[lev], mg_r[lev]);
-    const int nc = mg_n[lev + 1];
-    k_p1p_restrict<<<dim3((nc + 63) / 64, nc), 64, 0, stream>>>(nc, mg_r[lev], mg_b[lev + 1]);
-    vcycle_periodic(lev + 1);
-    k_p1p_prolong_add<<<grid, 64, 0, stream>>>(nc, mg_x[lev + 1], mg_x[lev]);
-    sweeps(nsw, true);
   }
   // z = M r for the condensed system
   // LDS-tiled form of the two smoother applications (hdg_trace_tile.hpp): single rank, non-periodic structured mesh,
@@ -2458,7 +2450,7 @@ struct Engine {
     if (periodic) {  // (row -1 of `res` comes from the pre kernel's ghost rows)
       k_trace_to_p1p<<<corner_grid(), bs(), 0, stream>>>(g, NL, res, mg_b[0], dt.elen[0], dt.elen[2], dt.elen[1]);
       gather_periodic_rhs();
-      run_vcycle();
+      vcycle(vplan, 0, &xp);
       return;
     }
     k_trace_to_p1<<<corner_grid_all(), bs(), 0, stream>>>(g_all, NL, res, mg_b[0], dt.elen[0], dt.elen[2], dt.elen[1], partial);
@@ -2471,7 +2463,7 @@ struct Engine {
       const long nvtx = ((long)comm->size * g.ny + 1) * (g.nx + 1);
       k_p1_assemble<<<vec_blocks(nvtx), 256, 0, stream>>>(comm->size, g.ny, g.nx + 1, mg_gather, mg_b[0], partial);
     }
-    run_vcycle();
+    vcycle(vplan, 0, &xp);
   }
   // returns true when w_out has received T z (the operator application the single-reduction CG needs next); with
   // dots_out set as well, d_res then holds (z,n), (z,r), (z,z), (z,w), (n,r) (the multi-dot of that CG: *dots_out = true)
@@ -2481,47 +2473,6 @@ struct Engine {
   // instead of k_reduce_parts + k_cg_sr_scalars)
   bool defer_tile_reduce = false;
   int tile_nblk_deferred = 0;
-  // trace_cg_sr with the tile preconditioner: the half of the update nothing reads before the next update (p, x) rides on the
-  // leg launches of the V-cycle (k_p1_down / k_p1_up side jobs, hdg_kernels.hpp: SideXP), a share of the pairs per leg by
-  // weight (opt.cg_xp_w0); what the legs did not take (no fused legs, odd tail entry) is done by
-  // xp_launch() as a launch of its own.  (A second stream underneath the cycle was measured and removed: DESIGN.md section 9.)
-  bool xp_pending = false;
-  double* xp_x = nullptr;
-  long xp_done = 0;      // pairs already handed to side jobs
-  double xp_wsum = 0.0;  // sum of the leg weights of one cycle
-  bool xp_riding = false;
-  void xp_ride_begin() {
-    xp_done = 0; xp_riding = false;
-    if (!xp_pending || general || mg_n.empty() || !opt.mg_fuse) return;
-    // strips: the finest level is distributed (vcycle_distributed_top launches its legs itself); the replicated levels carry the update
-    const size_t l0 = mg_distributed() ? 1 : 0;
-    xp_wsum = 0.0;
-    for (size_t l = l0; l + 1 < mg_n.size() && mg_n[l] > 32 && (mg_n[l] & 1) == 0; l++) xp_wsum += 2.0 * (l == 0 ? opt.cg_xp_w0 : 1.0);
-    xp_riding = xp_wsum > 0.0;
-  }
-  SideXP xp_side_slice(int lev, int nt, int& extra_rows) {
-    extra_rows = 0;
-    SideXP sj{};
-    if (!xp_riding) return sj;
-    const long total = NLv >> 1;
-    long cnt = (long)std::ceil((double)total * (lev == 0 ? opt.cg_xp_w0 : 1.0) / xp_wsum);
-    cnt = std::min(cnt, total - xp_done);
-    if (cnt <= 0) return sj;
-    sj = SideXP{d_cgs, cg_z, tr_one, cg_p, xp_x, xp_done, xp_done + cnt};
-    xp_done += cnt;
-    const long blocks = (cnt + HDG_P1_THREADS - 1) / HDG_P1_THREADS;
-    extra_rows = (int)((blocks + nt - 1) / nt);
-    return sj;
-  }
-  static int xp_period(int nt, int extra) { return side_row_period(nt, extra); }  // hdg_side_rows.hpp
-  void xp_launch() {
-    if (!xp_pending) return;
-    xp_pending = false;
-    const long done = xp_riding ? xp_done : 0;
-    xp_riding = false; xp_done = 0;
-    const int nvb = vec_blocks(NLv - 2 * done);
-    if (done < (NLv >> 1) || (NLv & 1)) k_cg_sr_update_xp<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_p, xp_x, done);
-  }
   bool trace_precond(const double* r, double* z, double* w_out = nullptr, bool* dots_out = nullptr) {
     if (dots_out) *dots_out = false;
     if (cfg.trace_precond == 0) {
@@ -2554,10 +2505,10 @@ struct Engine {
         typedef TraceTile3<KK> T3;
         if (tile3()) k_trace_pre_tile3<KK><<<grid_pre, T3::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
         else k_trace_pre_tile<KK><<<grid_pre, TT::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
-        xp_ride_begin();  // the deferred half of the CG update: on the legs of the vertex-grid cycle ...
-        if (!xp_riding) xp_launch();  // ... or, where no leg can carry it, as a launch of its own
+        xp.begin(vplan);  // the deferred half of the CG update: on the legs of the vertex-grid cycle ...
+        if (!xp.riding) xp.finish();  // ... or, where no leg can carry it, as a launch of its own
         coarse_correction(wL2);
-        xp_launch();  // what the legs did not take; the post kernel overwrites z
+        xp.finish();  // what the legs did not take; the post kernel overwrites z
         tally(LC_TRACE_SMOOTH, (w_out ? 4 : 3) * bL() + nvtx);
         const long nblk = (long)ntx * nty;
         double* part = nullptr;
@@ -2605,7 +2556,7 @@ struct Engine {
       halo_L(wL2);
       k_trace_to_p1p<<<corner_grid(), bs(), 0, stream>>>(g, NL, wL2, mg_b[0], dt.elen[0], dt.elen[2], dt.elen[1]);
       gather_periodic_rhs();
-      run_vcycle();
+      vcycle(vplan, 0, &xp);
       k_p1p_to_trace<<<corner_grid(), bs(), 0, stream>>>(g, NL, mg_x[0], z, 1.0, dt.elen[0], dt.elen[2], dt.elen[1]);
       fl.set(z, 0);  // owned rows only: the wrapped ghost rows are stale
       cheb_smooth(r, z, false, nsm);
@@ -2628,16 +2579,10 @@ struct Engine {
     if (cfg.trace_precond == 1 && general) setup_general_amg(gops.S, gsets[0].amg);
     else if (cfg.trace_precond == 1) {
       if (comm->size > 1 || opt.force_rccl) mg_gather = dalloc((long)comm->size * (g.ny + 1) * (g.nx + 1));
-      int n = g.nx;
-      while (true) {
-        mg_n.push_back(n);
-        long nv = periodic ? (long)n * n : (long)(n + 1) * (n + 1);
-        mg_x.push_back(dalloc(nv)); mg_b.push_back(dalloc(nv)); mg_r.push_back(dalloc(nv));
-        if (n % 2 != 0 || n <= 2 || (periodic && (n / 2) % 2 != 0)) break;  // periodic red-black sweeps need an even n
-        n /= 2;
-      }
+      vplan = vertex_plan(g.nx, periodic, opt);  // the hierarchy and the form of every level
+      for (const VLevel& v : vplan.lev) { mg_x.push_back(dalloc(v.nv)); mg_b.push_back(dalloc(v.nv)); mg_r.push_back(dalloc(v.nv)); }
+      build_dense_tail();
     }
-    if (cfg.trace_precond == 1) { build_dense_tail(); build_dense_tail_periodic(); }
     psets.push_back(PSet{dt, 0.0, 0.0, cfg.tau});
     estimate_cheb(0);
     use_pset(0);
@@ -2778,7 +2723,7 @@ struct Engine {
   // Returns the number of iterations the convergence test needed (the extra step is not counted).
   int trace_cg_sr(double* b, double* x, double rtol, int maxit, bool strict) {
     auto leave = [&]() {  // a deferred p / x update left over at the exit is the step beyond the tested iterate: dropped
-      xp_pending = false;
+      xp.pending = false;
       defer_tile_reduce = false; tile_nblk_deferred = 0;
     };
     try {
@@ -2826,7 +2771,7 @@ struct Engine {
     bool restart = true, true_residual = true;  // the first pass starts from r = b - T x as well
     const double floor_c = opt.cg_floor_c;
     auto replace_residual = [&](const char* why, double at, bool is_breakdown) {
-      xp_launch();  // the true residual needs the current iterate
+      xp.finish();  // the true residual needs the current iterate
       if (drifts >= 2) throw NotConverged{std::string("trace CG: ") + why + " after two residual replacements that confirmed a drifted recurrence"};
       replaced++;
       trigger_nrm = at; trigger_breakdown = is_breakdown;
@@ -2855,7 +2800,7 @@ struct Engine {
       if (split) {
         // r first (the next preconditioner application waits for it); p and x when that application reaches its V-cycle
         k_cg_sr_update_r<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_Ap, s_cur, r_cur);
-        xp_pending = true; xp_x = x;
+        xp.pending = true; xp.x = x;
       } else
         k_cg_sr_update<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_Ap, cg_p, s_cur, x, r_cur);
       fl.set(s_cur, restart ? fl.get(cg_Ap) : std::min(fl.get(s_cur), fl.get(cg_Ap)));
@@ -2868,7 +2813,7 @@ struct Engine {
       const bool breakdown = h_cgs[6] == 1.0;  // alpha was set to 0: the update just queued leaves x alone
       double zz = h_cgs[4];
       if (h_cgs[6] == 2.0) {  // z almost parallel to the null vector: measure the projected norm explicitly
-        xp_launch();  // (the deferred update reads the unprojected z)
+        xp.finish();  // (the deferred update reads the unprojected z)
         axpby(NLv, -h_cgs[3], tr_one, 1.0, cg_z);
         fl.set(cg_z, 0);
         zz = dot(NLv, cg_z, cg_z, KL);
@@ -2882,7 +2827,7 @@ struct Engine {
       if (cg_floor > 0.0 && nrm <= cg_floor) return its;  // backward-error stop (experiment, see pressure_solve)
       if (was_true && replaced > 0) {
         // the true preconditioned residual after a replacement: at its rounding floor?
-        xp_launch();
+        xp.finish();
         const double xn = std::sqrt(std::max(dot(NLv, x, x, KL), 0.0));
         if (debug_cg()) fprintf(stderr, "[cg] it %d: true |z| %.3e, floor %.3e (|x| %.3e)\n", its, nrm, floor_c * 2.220446049250313e-16 * xn, xn);
         if (nrm <= floor_c * 2.220446049250313e-16 * xn) { ev_cg_floor_exits++; return its; }

@@ -1,4 +1,4 @@
-// Rows of a V-cycle leg launch that carries side jobs (hdg_kernels.hpp: SideXP, HDG_P1_SIDE_JOB; Engine::xp_side_slice).
+// Rows of a V-cycle leg launch that carries side jobs (hdg_vertex_mg.hpp: SideXP, HDG_P1_SIDE_JOB; Engine::XpRide::slice).
 // A leg launch over nt tile rows gets `extra` more rows of workgroups; each workgroup of such a SIDE row updates 1024 sixteen-byte
 // pairs of the condensed CG's p and x instead of a tile.  The rows are interleaved: the less numerous kind of row (side rows for
 // period > 0, tile rows for period < 0) takes the last row of every group of |period| rows until it is used up, so that the

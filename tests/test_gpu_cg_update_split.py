@@ -1,5 +1,5 @@
 """The update of the condensed single-reduction CG in two halves (Engine::trace_cg_sr, one rank, tile preconditioner): r and s
-at once, p and x as side jobs of the V-cycle's leg launches (hdg_kernels.hpp: SideXP, HDG_P1_SIDE_JOB), and the second
+at once, p and x as side jobs of the V-cycle's leg launches (hdg_vertex_mg.hpp: SideXP, HDG_P1_SIDE_JOB), and the second
 reduction stage fused with the CG scalars (k_cg_sr_reduce_scalars).  Same arithmetic per
 entry as the one-launch update k_cg_sr_update (HDG_CG_NO_SPLIT_UPDATE / HDG_CG_NO_FUSED_SCALARS, read when an engine is built);
 the only difference is that the step beyond the tested iterate is not taken: fields agree far below the solver tolerance

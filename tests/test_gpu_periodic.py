@@ -140,6 +140,30 @@ def test_periodic_fused_vcycle_legs_equal_the_per_level_kernels(hip_lib, tmp_pat
     assert np.all(np.abs(res["fused"]["its"][1:] - res["levels"]["its"][1:]) <= 1.0), (res["fused"]["its"], res["levels"]["its"])
 
 
+@pytest.mark.parametrize("k,nx", [(1, 64), (2, 80)])
+def test_periodic_fused_vcycle_legs_are_bitwise_equal_to_the_per_level_launches(hip_lib, tmp_path, k, nx):
+    """The periodic analogue of the unit square's bitwise test: with the dense tail off on both sides (HDG_MG_NO_DENSE_TAIL:
+    the levels n <= 32 run as per-level kernels either way) only the legs differ between the default and HDG_MG_NO_FUSE, and
+    the legs compute every vertex value by the function the per-level kernels call (csrc/hdg_vertex_mg.hpp), so two steps
+    agree bit for bit: Q, p, lambda and the iteration counts with np.array_equal.  64: two tiles that wrap onto each other,
+    one leg level; 80: 2.5 tiles, the wrap falls inside a halo, legs on two levels.  (Measured before the kernels were
+    merged, with the hand-kept twins k_p1p_*: bitwise equal there as well, both cases.)"""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    res = {}
+    for tag, env in (("fused", {"HDG_MG_NO_DENSE_TAIL": "1"}), ("levels", {"HDG_MG_NO_DENSE_TAIL": "1", "HDG_MG_NO_FUSE": "1"})):
+        out = str(tmp_path / f"{tag}.npz")
+        r = subprocess.run([sys.executable, os.path.join(here, "periodic_worker.py"), str(k), str(nx), "2", out], env=dict(os.environ, **env),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        assert r.returncode == 0, r.stdout.decode()[-2000:]
+        res[tag] = np.load(out)
+    for name in ("Q", "p", "lam", "its"):
+        assert np.array_equal(res["fused"][name], res["levels"][name]), name
+
+
 @pytest.mark.parametrize("k,nx", [(1, 4), (2, 4), (3, 4), (2, 6)])
 def test_periodic_continuous_space_tracer_operator_vorticity(hip_lib, k, nx):
     """CG_{k+1} on the periodic square (nx x ny corners, indices wrap): projection (common.py:119-122), tracer transport

@@ -531,6 +531,16 @@ def test_row_log_counts_rows_and_drops(tmp_path):
     _host_check(tmp_path, "row_log_check")
 
 
+def test_vertex_grid_level_plan_states_the_form_of_every_level(tmp_path):
+    """csrc/hdg_vertex_levels.hpp (plain C++, compiled here with g++), the one place that decides which form a level of the
+    vertex-grid V-cycle runs as: the hierarchy and the forms (fused legs, per-level kernels, one-workgroup tail, dense tail,
+    coarsest-level sweeps) of unit squares 1024, 96, 66, 65, 24, 2 and periodic squares 256, 80, 48, 16, 18 equal literal
+    plans derived by hand from the rules the engine followed before; so do the plans with the fused legs, the tail or the
+    dense tail switched off and with three smoothing sweeps (the unit square keeps its legs, the periodic one loses them);
+    the side-job weights of the condensed CG at unit 1024 sum to 2 * 1.6 + 2 * 4 = 11.2."""
+    _host_check(tmp_path, "vertex_levels_check")
+
+
 def test_new_host_headers_compile_alone(tmp_path):
     """Each host-only header of csrc/ compiles on its own with g++ -Wall -Wextra -Werror: no HIP header behind it."""
     import shutil
@@ -540,7 +550,8 @@ def test_new_host_headers_compile_alone(tmp_path):
     if gxx is None:
         pytest.skip("no g++")
     csrc = os.path.join(ROOT, "incompressibleeulerhdg_amd", "csrc")
-    for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_row_log.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp"):
+    for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_row_log.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp",
+              "hdg_vertex_levels.hpp"):
         assert "hip" not in open(os.path.join(csrc, h)).read().split("#pragma once")[1].split("namespace hdg")[0], h
         tu = tmp_path / (h + ".cpp")
         tu.write_text(f'#include "{h}"\n')
