@@ -44,6 +44,8 @@
 #include "hdg_tables.hpp"
 #include "hdg_mfma_pack.hpp"
 #include "hdg_small_dense.hpp"
+#include "hdg_krylov_host.hpp"
+#include "hdg_tent_policy.hpp"
 #include "hdg_stage_coeffs.hpp"
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
@@ -686,6 +688,7 @@ struct Engine {
       if (i < s - 1 || s == 1) Qstar.push_back(dalloc(NQ));
     }
     for (int i = 0; i <= s; i++) { brhs.push_back(dalloc(NQ)); bscale.push_back(1.0); bsep.push_back(0); }
+    ch.assign((size_t)s + 1, ChebStage{});
     profile = dalloc(NQ);
     updU = dalloc(NQ); updP = dalloc(NPv); updL = dalloc(NLv); recP = dalloc(NPv); recL = dalloc(NLv);
     wQ1 = dalloc(NQ); wQ2 = dalloc(NQ); wQ3 = dalloc(NQ); wQ4 = dalloc(NQ);
@@ -1624,8 +1627,11 @@ struct Engine {
     HIPCHECK(hipStreamSynchronize(stream));
     dinv_gamma[idx] = gamma;
   }
+  // one tentative-velocity system (I - gamma F(Q*)) x = b of stage didx (whose preconditioner tables ensure_dinv has built)
+  struct TentSystem { const double* qstar; double gamma; int didx; const double* b; };
   // z = M r  (tentative-velocity preconditioner)
-  void tent_precond(int didx, const double* r, double* z) {
+  void tent_precond(const TentSystem& S, const double* r, double* z) {
+    const int didx = S.didx;
     if (general) {
       if (cfg.tent_precond == 2 && g_hyb[(size_t)didx]) {
         g_lift_apply(g_hyb[(size_t)didx], r, z);  // z = r + (I - Dinv) Lift d(r): one matrix-free kernel
@@ -1655,11 +1661,12 @@ struct Engine {
   // x_{n+1} on exit, x_ = x_n is only read (owned rows only: the ghost rows are refreshed by the next operator
   // application); z is written to `zout` only when it is needed
   // cell_norm (hybrid preconditioner only): instead of z the kernel writes |z_K|^2 per cell into cell_ss
-  void tent_precond_cheb(int didx, const double* r, double* zout, double* d_, double* x_, double c1, double c2,
+  void tent_precond_cheb(const TentSystem& S, const double* r, double* zout, double* d_, double* x_, double c1, double c2,
                          bool cell_norm = false) {
+    const int didx = S.didx;
     if (general) {  // assembled preconditioner, then the step as a vector kernel
       double* zz = zout ? zout : wQ1;  // (tent_precond uses wQ3 / wQ4 as its own scratch; wQ1 is the solver's z buffer)
-      tent_precond(didx, r, zz);
+      tent_precond(S, r, zz);
       cheb_update(d_, zz, x_, c1, c2);
       return;
     }
@@ -1677,134 +1684,127 @@ struct Engine {
       bdm_hybrid(r, zout, hybg0[didx], hybg1[didx], d_, x_, c1, c2, cell_norm ? cell_ss : nullptr);
     }
   }
-  // solve (I - gamma F(Q*)) x = b with left-preconditioned GMRES(m); x holds the initial guess.
+  // Krylov solvers of a tentative-velocity system S, left-preconditioned; x holds the initial guess.
   // Convergence: ||M r|| <= rtol * ||M r0||  (PETSc default for the SNES-ksponly linear solve the
-  // reference performs: relative to the residual at the warm start)
-  // ritz != nullptr: run ONE cycle of at most m_cycle iterations, return the eigenvalues of
-  // its Hessenberg matrix (Ritz values of the preconditioned operator) and the initial / final
-  // preconditioned residual norms through *beta_first / *beta_last (beta_last is the Arnoldi estimate).
-  int gmres(const double* qstar, double gamma, int didx, const double* b, double* x, double rtol = -1.0,
-            int maxit = -1, bool strict = true, std::vector<std::complex<double>>* ritz = nullptr, int m_cycle = 0,
-            double* beta_first = nullptr, double* beta_last = nullptr, double beta0_given = -1.0, int first_cycle = 4) {
-    // Round 4: a WHOLE strict solve (the fully implicit stepper at k >= 2, wide-ellipse stages that the Chebyshev iteration
-    // declines, general meshes at k = 1) runs as s-step minimal-residual cycles -- the same Krylov spaces as GMRES(6) without the
-    // Gram-Schmidt passes, which cost more than the operator (sstep_mr; two weak cycles come back here in Arnoldi form).  The
-    // Arnoldi form stays for the Ritz estimate, the inexact inner solves of the monolithic preconditioner, the fall-backs after a
-    // growing / stalled Chebyshev iteration; HDG_GMRES_ARNOLDI restores it everywhere.
-    if (!opt.gmres_arnoldi && !arnoldi_only && !ritz && strict && m_cycle == 0 && first_cycle == 4 && gm_V.size() >= 4)
-      return sstep_mr(qstar, gamma, didx, b, x, rtol < 0 ? cfg.tent_rtol : rtol, beta0_given, -1.0);
+  // reference performs: relative to the residual at the warm start); beta0 = ||M r0|| where the caller
+  // has measured it, < 0: the norm of the first residual of the call.
+  //
+  // tent_krylov: where a solve, or the rest of one, that the Chebyshev iteration does not take goes.
+  // Round 4: a WHOLE strict solve (the fully implicit stepper at k >= 2, wide-ellipse stages that the Chebyshev iteration
+  // declines, general meshes at k = 1) runs as s-step minimal-residual cycles -- the same Krylov spaces as GMRES(6) without the
+  // Gram-Schmidt passes, which cost more than the operator (sstep_mr; two weak cycles come back in Arnoldi form).  The
+  // Arnoldi form stays for the Ritz estimate, the inexact inner solves of the monolithic preconditioner, the fall-backs after a
+  // growing / stalled Chebyshev iteration (they call arnoldi_solve themselves); HDG_GMRES_ARNOLDI restores it everywhere.
+  int tent_krylov(const TentSystem& S, double* x, double rtol, int maxit, bool strict, double beta0 = -1.0) {
+    if (strict && !opt.gmres_arnoldi && gm_V.size() >= 4) return sstep_mr(S, x, rtol, beta0, -1.0);
+    return arnoldi_solve(S, x, rtol, maxit, strict, beta0, 4);
+  }
+  // w = M(b - A x) in wQ1 (t = b - A x in wQ2): the norm of w
+  double tent_residual(const TentSystem& S, const double* x) {
+    adv_apply(x, S.qstar, wQ2, S.gamma, S.b);    // t = b - A x  (residual fused into the operator kernel)
+    tent_precond(S, wQ2, wQ1);
+    return std::sqrt(dot(NQ, wQ1, wQ1, KQ));
+  }
+  // GMRES(m): restarted Arnoldi cycles, the first of first_cycle iterations.  strict: throws at maxit.
+  int arnoldi_solve(const TentSystem& S, double* x, double rtol, int maxit, bool strict, double beta0, int first_cycle) {
     FlowScope flow_(*this);
-    flow_fixed_Q(qstar);
-    flow_fixed_Q(b);
+    flow_fixed_Q(S.qstar);
+    flow_fixed_Q(S.b);
     const int m = std::min(std::max(1, cfg.gmres_restart), MAXV - 1);  // allocated basis / Hessenberg stride
     // adaptive cycle length: short cycles keep the Krylov-basis traffic low (the preconditioned operator
     // is benign: GMRES(4) needs 45.5 iterations where GMRES(30) needs 42.5 at C3); a cycle that reduces
     // the residual by less than 2x doubles the length, up to the configured restart
     int mcur = std::min(m, std::max(1, first_cycle));
-    if (ritz) mcur = std::min(m, std::max(1, m_cycle));
     double beta_prev = -1.0;
-    std::vector<double> Hraw;
-    if (rtol < 0) rtol = cfg.tent_rtol;
-    if (maxit < 0) maxit = cfg.tent_maxit;
     int its = 0;
-    double beta0 = beta0_given;
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), gv(m + 1);
-    double* w = wQ1;
-    double* t = wQ2;
-    const int nvb = vec_blocks(NQ);
+    GivensLsq lsq(m);
     while (true) {
-      adv_apply(x, qstar, t, gamma, b);    // t = b - A x  (residual fused into the operator kernel)
-      tent_precond(didx, t, w);
-      double beta = std::sqrt(dot(NQ, w, w, KQ));
+      const double beta = tent_residual(S, x);
       if (beta0 < 0) beta0 = beta;
-      if (beta_first) *beta_first = beta;
-      if (beta_last) *beta_last = beta;
       if (!(beta == beta)) throw NotConverged{"GMRES: NaN residual"};
       if (beta <= rtol * beta0 || beta == 0.0) return its;
-      if (!ritz && beta_prev > 0 && beta > 0.5 * beta_prev) mcur = std::min(m, 2 * mcur);
+      if (beta_prev > 0 && beta > 0.5 * beta_prev) mcur = std::min(m, 2 * mcur);
       beta_prev = beta;
-      gs_update(w, Coefs(), 0, 1.0 / beta, gm_V[0]);
-      std::fill(gv.begin(), gv.end(), 0.0);
-      gv[0] = beta;
-      int j = 0;
-      bool done = false;
-      for (; j < mcur; j++) {
-        adv_apply(gm_V[j], qstar, t, gamma);
-        tent_precond(didx, t, w);
-        // one pass: h_l = (w, V_l), l <= j, and (w, w); then ||w - V h||^2 = (w,w) - sum h_l^2
-        std::vector<double> h(j + 2);
-        multidot_basis(w, j + 1, h.data());
-        double ww = h[j + 1], s2 = 0.0;
-        for (int l = 0; l <= j; l++) s2 += h[l] * h[l];
-        double hn2 = ww - s2;
-        Coefs hc;
-        for (int l = 0; l <= j; l++) hc.c[l] = h[l];
-        double hn;
-        if (hn2 > 1e-6 * ww) {
-          hn = std::sqrt(hn2);
-          gs_update(w, hc, j + 1, 1.0 / hn, gm_V[j + 1]);
-        } else {
-          // severe cancellation: orthogonalise explicitly and measure the norm (safe path)
-          gs_update(w, hc, j + 1, 1.0, gm_V[j + 1]);
-          hn = std::sqrt(dot(NQ, gm_V[j + 1], gm_V[j + 1], KQ));
-          if (hn > 0) gs_update(w, hc, j + 1, 1.0 / hn, gm_V[j + 1]);  // once more with the norm (writes every copy of the vector)
-        }
-        for (int l = 0; l <= j; l++) H[(size_t)l * m + j] = h[l];
-        H[(size_t)(j + 1) * m + j] = hn;
-        if (ritz) {
-          if (Hraw.empty()) Hraw.assign((size_t)m * m, 0.0);
-          for (int l = 0; l <= j; l++) Hraw[(size_t)l * m + j] = h[l];
-          if (j + 1 < m) Hraw[(size_t)(j + 1) * m + j] = hn;
-        }
-        for (int l = 0; l < j; l++) {
-          double a1 = H[(size_t)l * m + j], a2 = H[(size_t)(l + 1) * m + j];
-          H[(size_t)l * m + j] = cs[l] * a1 + sn[l] * a2;
-          H[(size_t)(l + 1) * m + j] = -sn[l] * a1 + cs[l] * a2;
-        }
-        double a1 = H[(size_t)j * m + j], a2 = H[(size_t)(j + 1) * m + j];
-        double rr = std::hypot(a1, a2);
-        cs[j] = (rr == 0) ? 1.0 : a1 / rr;
-        sn[j] = (rr == 0) ? 0.0 : a2 / rr;
-        H[(size_t)j * m + j] = rr;
-        H[(size_t)(j + 1) * m + j] = 0.0;
-        gv[j + 1] = -sn[j] * gv[j];
-        gv[j] = cs[j] * gv[j];
-        its++;
-        double res = std::fabs(gv[j + 1]);
-        if (beta_last) *beta_last = res;
-        if (debug_on()) fprintf(stderr, "[gmres]   it %d (cycle start %.3e)  estimate %.3e  hn %.3e\n", its, beta / beta0, res / beta0, hn);
-        if (res <= rtol * beta0 || hn == 0.0) { j++; done = true; break; }
-        if (its >= maxit) { j++; done = false; break; }
-      }
-      Coefs yc;
-      std::vector<double> y(j, 0.0);
-      for (int l = j - 1; l >= 0; l--) {
-        double acc = gv[l];
-        for (int q = l + 1; q < j; q++) acc -= H[(size_t)l * m + q] * y[q];
-        y[l] = acc / H[(size_t)l * m + l];
-      }
-      for (int l = 0; l < j; l++) yc.c[l] = y[l];
-      tally(LC_VEC, bQ() * (j + 2));
-      if (big(NQ)) k_basis_axpy<MAXV, true><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
-      else k_basis_axpy<MAXV, false><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
-      {
-        int d = fl.get(x);
-        for (int l = 0; l < j; l++) d = std::min(d, fl.get(gm_V[l]));
-        fl.set(x, d);
-      }
-      if (ritz) {
-        // Ritz values: eigenvalues of the leading j x j block of the (unrotated) Hessenberg matrix
-        std::vector<double> Hs((size_t)j * j);
-        for (int a = 0; a < j; a++) for (int c = 0; c < j; c++) Hs[(size_t)a * j + c] = Hraw[(size_t)a * m + c];
-        *ritz = hessenberg_eig(Hs, j);
-        return its;
-      }
-      if (done) return its;
+      if (arnoldi_cycle(S, x, lsq, mcur, beta, beta0, rtol, maxit, its).done) return its;
       if (its >= maxit) {
         if (strict) throw NotConverged{"tentative-velocity GMRES reached max iterations"};
         return its;
       }
     }
+  }
+  // ONE Arnoldi cycle of at most m_cycle iterations from x: the eigenvalues of its Hessenberg matrix (Ritz values of the
+  // preconditioned operator) and the initial / final preconditioned residual norms (beta_last is the Arnoldi estimate).
+  // No Ritz values where x had converged already.
+  struct RitzEstimate { int its = 0; double beta_first = 0.0, beta_last = 0.0; std::vector<std::complex<double>> ritz; };
+  RitzEstimate ritz_cycle(const TentSystem& S, double* x, int m_cycle) {
+    FlowScope flow_(*this);
+    flow_fixed_Q(S.qstar);
+    flow_fixed_Q(S.b);
+    const int m = std::min(std::max(1, cfg.gmres_restart), MAXV - 1);
+    RitzEstimate e;
+    const double beta = e.beta_first = e.beta_last = tent_residual(S, x);
+    if (!(beta == beta)) throw NotConverged{"GMRES: NaN residual"};
+    if (beta <= cfg.tent_rtol * beta || beta == 0.0) return e;
+    GivensLsq lsq(m, true);
+    const ArnoldiCycle c = arnoldi_cycle(S, x, lsq, std::min(m, std::max(1, m_cycle)), beta, beta, cfg.tent_rtol, cfg.tent_maxit, e.its);
+    e.beta_last = c.res;
+    // Ritz values: eigenvalues of the leading j x j block of the (unrotated) Hessenberg matrix
+    e.ritz = hessenberg_eig(lsq.unrotated(c.j), c.j);
+    return e;
+  }
+  // One Arnoldi cycle of at most mcur iterations from the preconditioned residual tent_residual left in wQ1 (norm beta), and
+  // the update of x at its end.  j: columns built; done: the estimate met the tolerance, or the Krylov space is exhausted;
+  // res: the Arnoldi estimate of the new |M r|
+  struct ArnoldiCycle { int j; bool done; double res; };
+  ArnoldiCycle arnoldi_cycle(const TentSystem& S, double* x, GivensLsq& lsq, int mcur, double beta, double beta0, double rtol,
+                             int maxit, int& its) {
+    double* w = wQ1;
+    double* t = wQ2;
+    const int nvb = vec_blocks(NQ);
+    gs_update(w, Coefs(), 0, 1.0 / beta, gm_V[0]);
+    lsq.start(beta);
+    int j = 0;
+    bool done = false;
+    double res = beta;
+    for (; j < mcur; j++) {
+      adv_apply(gm_V[j], S.qstar, t, S.gamma);
+      tent_precond(S, t, w);
+      // one pass: h_l = (w, V_l), l <= j, and (w, w); then ||w - V h||^2 = (w,w) - sum h_l^2
+      std::vector<double> h(j + 2);
+      multidot_basis(w, j + 1, h.data());
+      double ww = h[j + 1], s2 = 0.0;
+      for (int l = 0; l <= j; l++) s2 += h[l] * h[l];
+      double hn2 = ww - s2;
+      Coefs hc;
+      for (int l = 0; l <= j; l++) hc.c[l] = h[l];
+      double hn;
+      if (hn2 > 1e-6 * ww) {
+        hn = std::sqrt(hn2);
+        gs_update(w, hc, j + 1, 1.0 / hn, gm_V[j + 1]);
+      } else {
+        // severe cancellation: orthogonalise explicitly and measure the norm (safe path)
+        gs_update(w, hc, j + 1, 1.0, gm_V[j + 1]);
+        hn = std::sqrt(dot(NQ, gm_V[j + 1], gm_V[j + 1], KQ));
+        if (hn > 0) gs_update(w, hc, j + 1, 1.0 / hn, gm_V[j + 1]);  // once more with the norm (writes every copy of the vector)
+      }
+      res = lsq.add_column(j, h.data(), hn);
+      its++;
+      if (debug_on()) fprintf(stderr, "[gmres]   it %d (cycle start %.3e)  estimate %.3e  hn %.3e\n", its, beta / beta0, res / beta0, hn);
+      if (res <= rtol * beta0 || hn == 0.0) { j++; done = true; break; }
+      if (its >= maxit) { j++; done = false; break; }
+    }
+    const std::vector<double> y = lsq.solve(j);
+    Coefs yc;
+    for (int l = 0; l < j; l++) yc.c[l] = y[l];
+    tally(LC_VEC, bQ() * (j + 2));
+    if (big(NQ)) k_basis_axpy<MAXV, true><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
+    else k_basis_axpy<MAXV, false><<<nvb, 256, 0, stream>>>(NQ, x, d_gmV, yc, j);
+    {
+      int d = fl.get(x);
+      for (int l = 0; l < j; l++) d = std::min(d, fl.get(gm_V[l]));
+      fl.set(x, d);
+    }
+    return ArnoldiCycle{j, done, res};
   }
 
   // s-step minimal-residual cycles on the left-preconditioned operator B = M (I - gamma F(Q*)) (hdg_kernels.hpp: k_gram,
@@ -1820,12 +1820,11 @@ struct Engine {
   // (the cycle length is chosen from the reduction still needed: 1.7 iterations per decade + 1, GMRES's observed 5-6 for 3-4
   // decades).  Two cycles in a row that gain less than a factor 2 hand the solve to GMRES (which throws at its iteration limit).
   long n_sstep_cycles = 0, n_sstep_fallbacks = 0;
-  bool arnoldi_only = false;  // set while a fall-back of the s-step cycles runs
   double *d_gram = nullptr, *h_gram = nullptr;
-  int sstep_mr(const double* qstar, double gamma, int didx, const double* b, double* x, double rtol, double beta0, double cur0) {
+  int sstep_mr(const TentSystem& S, double* x, double rtol, double beta0, double cur0) {
     FlowScope flow_(*this);
-    flow_fixed_Q(qstar);
-    flow_fixed_Q(b);
+    flow_fixed_Q(S.qstar);
+    flow_fixed_Q(S.b);
     const int smax = std::max(2, std::min(std::min(opt.sstep_max, HDG_SSTEP_MAXV - 1), (int)gm_V.size() - 1));
     if (!d_gram) {
       d_gram = dalloc(64);
@@ -1835,26 +1834,23 @@ struct Engine {
     const RowMask mk = mask_for(KQ);
     double target = rtol * beta0;  // beta0 <= 0: the norm of the first residual of this call (a whole solve by s-step cycles)
     const bool direct = comm->size == 1 && direct_host();
-    auto length_for = [&](double from) {  // iterations for the reduction from -> target at GMRES's observed tail rate
-      return (int)std::ceil(opt.sstep_per_decade * std::log10(std::max(from / target, 1.0)));
-    };
     int its = 0, weak = 0;
     double cur = cur0;
     bool have_r = false;
     while (true) {
       if (!have_r) {
-        adv_apply(x, qstar, t, gamma, b);  // t = b - A x
-        tent_precond(didx, t, gm_V[0]);
+        adv_apply(x, S.qstar, t, S.gamma, S.b);  // t = b - A x
+        tent_precond(S, t, gm_V[0]);
       }
       int built = 0;
-      int want = cur > 0.0 ? std::max(2, std::min(smax, length_for(cur) + 1)) : std::min(6, smax);
+      int want = sstep_first_length(cur, target, opt.sstep_per_decade, smax);
       std::vector<long double> G, yv;
       int nv = 0, rank = 0;
       double k0n = 0.0, rho = 0.0;
       while (true) {
         for (int i = built + 1; i <= want; i++) {
-          adv_apply(gm_V[i - 1], qstar, t, gamma);
-          tent_precond(didx, t, gm_V[i]);
+          adv_apply(gm_V[i - 1], S.qstar, t, S.gamma);
+          tent_precond(S, t, gm_V[i]);
           its++;
         }
         built = want;
@@ -1889,9 +1885,8 @@ struct Engine {
         if (k0n <= target || k0n == 0.0) return its;  // the iterate the cycle started from had converged already
         rank = sstep_ls(G, nv, nv - 1, yv, rho);
         if (debug_on()) fprintf(stderr, "[sstep]   basis of %d (rank %d): |Mr|/|Mr0| %.3e, predicted %.3e\n", built, rank, k0n / beta0, rho / beta0);
-        // enough (with a margin for the accuracy of the prediction), rank deficient, or no room left: take the step
-        if (rho <= 0.7 * target || rank < built || built >= smax) break;
-        want = std::min(smax, built + std::max(1, length_for(rho / 0.7)));
+        want = sstep_extend(rho, target, built, rank, smax, opt.sstep_per_decade);
+        if (want == built) break;  // take the step
       }
       n_sstep_cycles++;
       const int nvu = built + 1;  // update list: K_0 .. K_built
@@ -1927,9 +1922,7 @@ struct Engine {
       if (weak >= 2 || rank == 0) {
         n_sstep_fallbacks++;
         if (debug_on()) fprintf(stderr, "[sstep] two weak cycles: GMRES takes over\n");
-        struct Guard { bool& f; ~Guard() { f = false; } } guard_{arnoldi_only};
-        arnoldi_only = true;  // the Arnoldi form (gmres() would otherwise hand a whole solve back to the s-step cycles)
-        return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0);
+        return its + arnoldi_solve(S, x, rtol, cfg.tent_maxit, true, beta0, 4);
       }
       cur = rn;
       have_r = true;
@@ -1943,93 +1936,57 @@ struct Engine {
   // iteration).  Spectral bounds come from the Ritz values of the opening GMRES cycle of THIS solve
   // (merged with the bounds seen so far for the stage), with safety factors; if the iteration stalls or
   // grows, the solve is finished by GMRES.  Same stopping rule as GMRES: ||M r|| <= rtol ||M r_0||.
-  std::vector<double> ch_lmin, ch_lmax;
-  std::vector<long> ch_count;
-  std::vector<double> ch_widen;
-  std::vector<int> ch_last;   // iterations of the last converged Chebyshev solve of the stage (check schedule)
-  std::vector<char> ch_slow;  // the last Chebyshev solve of the stage was slow: GMRES until the next re-estimate
-  std::vector<int> ch_hand;   // learnt hand-over point of the stage: the check after which the Chebyshev rate last turned slow
+  // The decisions -- interval, ellipse, method selection, check schedule, guards -- are hdg_tent_policy.hpp's; ch is what
+  // each stage remembers between solves.
+  std::vector<ChebStage> ch;
   double* chd = nullptr;
   // x: the engine's pointer to the iterate (Qtent[.]).  The solve may end with the iterate in the second buffer; the two
   // pointers are then exchanged instead of the vector copied, so x is a reference and every reader goes through the member.
-  int cheb_gmres(const double* qstar, double gamma, int didx, const double* b, double*& x) {
+  int cheb_gmres(const TentSystem& S, double*& x) {
     FlowScope flow_(*this);
-    flow_fixed_Q(qstar);
-    flow_fixed_Q(b);
+    flow_fixed_Q(S.qstar);
+    flow_fixed_Q(S.b);
     const double rtol = cfg.tent_rtol;
-    if ((int)ch_lmin.size() < s + 1) { ch_lmin.assign(s + 1, -1.0); ch_lmax.assign(s + 1, -1.0); }
+    const int didx = S.didx;
+    const bool hyb = cfg.tent_precond == 2;
+    ChebStage& st = ch[(size_t)didx];
     if (!chd) chd = dalloc(NQ);
-    if ((int)ch_count.size() < s + 1) ch_count.assign(s + 1, 0);
-    if ((int)ch_widen.size() < s + 1) ch_widen.assign(s + 1, 1.0);
-    if ((int)ch_slow.size() < s + 1) ch_slow.assign(s + 1, 0);
-    if ((int)ch_last.size() < s + 1) ch_last.assign(s + 1, 0);
-    if ((int)ch_hand.size() < s + 1) ch_hand.assign(s + 1, 0);
-    std::vector<std::complex<double>> ritz;
-    double beta0 = 0.0, beta = 0.0, lo, hi;
+    double beta0 = 0.0, beta = 0.0;
     int its = 0;
-    // re-estimate period opt.cheb_every: a wrong interval is caught by the growth guard below, which re-estimates at once
-    const bool estimate = ch_lmin[didx] <= 0 || (ch_count[didx] % opt.cheb_every) == 0;
-    ch_count[didx]++;
+    // re-estimate period opt.cheb_every: a wrong interval is caught by the growth guard, which re-estimates at once
+    const bool estimate = st.lmin <= 0 || (st.count % opt.cheb_every) == 0;
+    st.count++;
     if (estimate) {
-      ch_hand[didx] = 0;  // the hand-over point is learnt anew with the bounds
-      its = gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, &ritz, opt.cheb_m, &beta0, &beta);
+      st.hand = 0;  // the hand-over point is learnt anew with the bounds
+      const RitzEstimate e = ritz_cycle(S, x, opt.cheb_m);
+      its = e.its; beta0 = e.beta_first; beta = e.beta_last;
       if (beta <= rtol * beta0 || beta0 == 0.0) return its;
-      lo = 1e300; hi = -1e300;
-      for (auto v : ritz) { lo = std::min(lo, v.real()); hi = std::max(hi, v.real()); }
-      if (!(lo > 0) || !(hi > lo)) return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0);
-      // Ritz values lie inside the spectrum: widen; keep the widest interval seen for this stage
-      // (the hybrid preconditioner's real spectrum starts at 1 -- the non-conforming part is reproduced exactly
-      //  -- but its upper end, 4.2-5.5 for k = 1..3, is underestimated by 6 Arnoldi steps, ~3.2; the ellipse of
-      //  convergence is larger than the interval, so 1.3 is enough for k >= 2 (1.5 for k = 1), and a stage whose Chebyshev
-      //  iteration had to fall back to GMRES widens its own factor for all later solves: ch_widen)
-      const bool hyb = cfg.tent_precond == 2;
-      const double e_lo = opt.cheb_flo, e_hi = opt.cheb_fhi;
-      const double f_lo = e_lo > 0 ? e_lo : (hyb ? 0.9 : 0.8);
-      const double f_hi = (e_hi > 0 ? e_hi : (hyb ? (cfg.degree == 1 ? 1.5 : 1.3) : 1.15)) * ch_widen[didx];
-      lo *= f_lo; hi *= f_hi;
-      if (ch_lmin[didx] > 0) { lo = std::min(lo, ch_lmin[didx]); hi = std::max(hi, ch_lmax[didx]); }
-      ch_lmin[didx] = lo; ch_lmax[didx] = hi;
+      if (!ritz_interval(e.ritz, st, opt, hyb, cfg.degree)) return its + tent_krylov(S, x, rtol, cfg.tent_maxit, true, beta0);
       if (debug_on()) {
         fprintf(stderr, "[cheb] stage %d ritz:", didx);
-        for (auto v : ritz) fprintf(stderr, " %.3f%+.3fi", v.real(), v.imag());
-        fprintf(stderr, "  -> interval [%.3f, %.3f], after GMRES cycle residual %.2e of %.2e\n", lo, hi, beta, beta0);
+        for (auto v : e.ritz) fprintf(stderr, " %.3f%+.3fi", v.real(), v.imag());
+        fprintf(stderr, "  -> interval [%.3f, %.3f], after GMRES cycle residual %.2e of %.2e\n", st.lmin, st.lmax, beta, beta0);
       }
     } else {
-      // bounds of this stage are known (refreshed every 16th solve): start the Chebyshev iteration at once
-      lo = ch_lmin[didx]; hi = ch_lmax[didx];
-      adv_apply(x, qstar, wQ2, gamma, b);
-      tent_precond(didx, wQ2, wQ1);
-      beta0 = beta = std::sqrt(dot(NQ, wQ1, wQ1, KQ));
+      // bounds of this stage are known (refreshed every opt.cheb_every-th solve): start the Chebyshev iteration at once
+      beta0 = beta = tent_residual(S, x);
       if (!(beta0 == beta0)) throw NotConverged{"Chebyshev: NaN residual"};
       if (beta0 == 0.0) return 0;
     }
-    // Chebyshev for a spectrum inside the ellipse with centre theta, real half-axis a and imaginary
-    // half-axis bim: foci at theta +- delta, delta^2 = a^2 - bim^2.  The additive preconditioner (SPD)
-    // gives a nearly real spectrum (bim = 0 is best); the hybrid one is non-symmetric and its spectrum fills
-    // a fat ellipse (at 128^2: real [1, 4.8] / [1, 4.2] / [1, 5.5], |imag| <= 1.2 / 1.4 / 2.2 for k = 1 / 2 / 3):
-    // bim = 0.5 a is within a few iterations of the best value for k = 1, 2 (measured scan), while
-    // bim = 0 loses 10+ iterations.
-    const double ell = opt.cheb_ell;
-    // k = 2: a THIN ellipse (0.3) for the bulk, then the hand-over to GMRES below; k = 1 (operator so cheap that a GMRES
-    // iteration costs 3-4 Chebyshev iterations): the wider ellipse that converges on its own (scans: DESIGN.md section 9)
-    const double frac = ell >= 0 ? ell : (cfg.tent_precond == 2 ? (cfg.degree >= 2 ? 0.3 : 0.5) : 0.0);
-    const double theta = 0.5 * (hi + lo), aax = 0.5 * (hi - lo), bim = frac * aax;
-    const double delta = std::sqrt(std::max(aax * aax - bim * bim, 1e-24)), sigma = theta / delta;
+    const double lo = st.lmin, hi = st.lmax;
+    const ChebEllipse el(lo, hi, cheb_ellipse_frac(opt, hyb, cfg.degree));
+    const double theta = el.theta, delta = el.delta, sigma = el.sigma;
     double rho = 1.0 / sigma;
 
     double* t = wQ2;
     double* z = wQ1;
-    const int nvb = vec_blocks(NQ);
-    // expected iterations for the remaining reduction (asymptotic rate on the ellipse), used as a stall guard
-    const double rate = (aax + bim) / (theta + std::sqrt(std::max(theta * theta - delta * delta, 0.0)));
-    const int expected = (int)(std::log(std::max(rtol * beta0 / beta, 1e-300)) / std::log(std::min(rate, 0.999))) + 8;
+    const int expected = el.expected(rtol * beta0 / beta);
     // Method selection: a wide / fat ellipse (large implicit weight or CFL: ARS3(4,4,3), the implicit tableau,
     // dt > 0.25/nx) predicts a slow Chebyshev iteration; GMRES then needs 40-80 iterations where Chebyshev
     // needs 100-160 and is as fast or faster in wall time (tools/robustness_sweep.py) and has no parameters.
-    const int cheb_max_expected = opt.cheb_max_expected;
-    if (expected > cheb_max_expected || (!estimate && ch_slow[didx])) {
+    if (expected > opt.cheb_max_expected || (!estimate && st.slow)) {
       if (debug_on()) fprintf(stderr, "[cheb] stage %d: %d iterations predicted on [%.3f, %.3f] -> GMRES\n", didx, expected, lo, hi);
-      return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0);
+      return its + tent_krylov(S, x, rtol, cfg.tent_maxit, true, beta0);
     }
     // Two iterate buffers, no direction vector: the step writes x_{n+1} over x_{n-1} (k_edge_lift epilogue /
     // k_cheb_update), then the roles swap.  `cur` holds the newest iterate; x receives it when the solve ends.
@@ -2041,103 +1998,43 @@ struct Engine {
       else copy(x, cur, NQ);
     };
     if (estimate) {
-      adv_apply(cur, qstar, t, gamma, b);
-      tent_precond_cheb(didx, t, nullptr, oth, cur, 0.0, 1.0 / theta);
+      adv_apply(cur, S.qstar, t, S.gamma, S.b);
+      tent_precond_cheb(S, t, nullptr, oth, cur, 0.0, 1.0 / theta);
     } else {
       // z = M(b - A x) of the unchanged iterate is already in wQ1 (= z) from the norm evaluation above
       cheb_update(oth, z, cur, 0.0, 1.0 / theta);
     }
     std::swap(cur, oth);
-    const int ch_head = its;  // iterations of the opening GMRES cycle (0 without an estimate)
+    // (its: the iterations of the opening GMRES cycle, 0 without an estimate)
+    ChebMonitor mon(st, its, expected, opt, cheb_handover_rate(opt, hyb, cfg.degree), rtol * beta0, beta, cfg.tent_maxit);
     int k = 1;
     its++;
-    double last = beta, stall_ref = beta, nz_prev = 0.0;
-    int stall_checks = 0, k_prev = 0;
     while (true) {
-      // The norm of z_k = M(b - A x_k) is only evaluated at check points (z is written out only then: a check
-      // costs a vector store, a dot product and a host sync, ~1/4 of an iteration).  With the Chebyshev count
-      // of the previous solve of this stage known: every 8th iteration up to 4 before it (enough to catch
-      // growth), every 2nd from there on; without history every 4th.
-      const int kfine = ch_last[didx] > 0 ? std::max(4, (ch_last[didx] - ch_head - 4) & ~1) : 0;
-      const int fine_step = opt.cheb_fine_step;
-      const double handover_env = opt.cheb_handover;
-      // k = 2: 0.3 with the s-step tail of round 4 (scan at C3, ms/step: 0.1-0.3: 85.5-85.8, 0.35: 91.2, 0.45: 95.6, 0.6: 95.1, 0.8:
-      // 100.8; with the GMRES(8) tail of round 3 the optimum was 0.6); k >= 3: 0.4 (no sensitivity between 0.25 and 0.6); k = 1: off
-      const double handover = handover_env >= 0.0 ? handover_env : (cfg.tent_precond == 2 ? (cfg.degree >= 3 ? 0.4 : (cfg.degree == 2 ? (opt.tail_gmres ? 0.6 : 0.3) : 0.0)) : 0.0);
-      const bool check = kfine > 0 ? (k < kfine ? (k % 8 == 0) : ((k - kfine) % fine_step == 0)) : (k % 4 == 0);
+      const bool check = mon.check_at(k);
       const double rn = 1.0 / (2.0 * sigma - rho);
-      adv_apply(cur, qstar, t, gamma, b);
+      adv_apply(cur, S.qstar, t, S.gamma, S.b);
       // hybrid preconditioner: the lift kernel emits |z_K|^2 per cell (N_c doubles) instead of z (N_Q doubles)
-      const bool cell_norm = check && cfg.tent_precond == 2 && !use_mfma_lift() && !general;
-      tent_precond_cheb(didx, t, (check && !cell_norm) ? z : nullptr, oth, cur, rn * rho, 2.0 * rn / delta, cell_norm);
+      const bool cell_norm = check && hyb && !use_mfma_lift() && !general;
+      tent_precond_cheb(S, t, (check && !cell_norm) ? z : nullptr, oth, cur, rn * rho, 2.0 * rn / delta, cell_norm);
       std::swap(cur, oth);
       rho = rn;
       k++;
       its++;
-      if (check) {
-        double nz = cell_norm ? std::sqrt(dot(g.Nc, cell_ss, ones_c, KC)) : std::sqrt(dot(NQ, z, z, KQ));
-        if (!(nz == nz)) throw NotConverged{"Chebyshev: NaN residual"};
-        if (debug_on()) fprintf(stderr, "[cheb]   k=%d  |Mr|/|Mr0| = %.3e\n", k, nz / beta0);
-        if (nz <= rtol * beta0) {
-          // z belongs to the iterate BEFORE the step just taken; that iterate had converged, and the
-          // extra Chebyshev step only reduces the error further
-          ch_slow[didx] = its > cheb_max_expected + cheb_max_expected / 2;  // the prediction was optimistic
-          ch_last[didx] = its;
-          finish_in_x();
-          return its;
-        }
-        // Guards.  Growth (an eigenvalue outside the ellipse of convergence): finish with GMRES and estimate
-        // more generously from now on.  No progress over 8 checks (32 iterations), or far beyond the predicted
-        // count: finish with GMRES but do NOT widen -- slow convergence is not a wrong interval, and widening on
-        // it made every following solve slower still (CFL 1 sweep, tools/robustness_sweep.py).
-        const bool growing = nz > 1e2 * last;
-        if (nz < 0.5 * stall_ref) { stall_ref = nz; stall_checks = 0; } else stall_checks++;
-        // Slow tail: an isolated eigenvalue outside the ellipse (seen at 2048^2: one near 0.3 with a 1e-6 share of
-        // the residual) makes the iteration crawl at its own rate (0.87 instead of 0.55 per iteration) once the
-        // bulk has converged.  GMRES removes such outliers in a few iterations: hand over when the rate observed
-        // since the previous check would need more than 24 further iterations.
-        bool tail = false;
-        if (k_prev > 0 && k > k_prev && nz < nz_prev && nz > rtol * beta0) {
-          const double obs = std::pow(nz / nz_prev, 1.0 / (k - k_prev));
-          const double remaining = std::log(rtol * beta0 / nz) / std::log(obs);
-          tail = k >= 16 && obs > 0.75 && remaining > 24.0;
-          // Deliberate hand-over (HDG_CHEB_HANDOVER = rate threshold, 0 = off): the iteration on a THIN ellipse takes
-          // the bulk of the spectrum down at 0.25-0.3 per iteration and then crawls on the few eigenvalues with large
-          // imaginary parts that the ellipse leaves out; a GMRES iteration costs 2-3 Chebyshev iterations (Krylov basis
-          // traffic) but removes exactly those.  Hand over as soon as the observed rate is worse than what GMRES buys per
-          // unit of cost, unless the end is a few iterations away anyway.
-          if (handover > 0.0 && k >= opt.cheb_min_k && obs > handover && remaining > 6.0) tail = true;
-          if (tail) ch_hand[didx] = k_prev;  // the segment (k_prev, k] was the slow one: hand over at k_prev next time
-        }
-        // round 4: with the s-step tail (an iteration of which costs what a Chebyshev iteration costs) the solves that follow
-        // hand over AT the learnt point instead of spending two more iterations on confirming the slow rate again
-        if (!tail && !opt.tail_gmres && handover > 0.0 && ch_hand[didx] > 0 && k >= ch_hand[didx] &&
-            nz > rtol * beta0)
-          tail = true;
-        k_prev = k; nz_prev = nz;
-        const bool stalled = tail || stall_checks >= 8 || k > 6 * expected + 64;
-        if (growing || stalled || its >= cfg.tent_maxit) {
-          if (growing) {
-            ch_lmin[didx] = ch_lmax[didx] = -1.0;  // wrong interval: re-estimate at the next solve of this stage,
-            ch_widen[didx] = std::min(ch_widen[didx] * 1.25, 4.0);  // more generously
-          } else if (!tail) {
-            ch_slow[didx] = true;  // right interval, slow iteration: GMRES until the periodic re-estimate
-          } else {
-            ch_last[didx] = its;  // the next solve of this stage starts its fine checks shortly before this point
-          }
-          if (debug_on())
-            fprintf(stderr, "[cheb]   falling back to GMRES at k=%d (%s; |Mr| %.2e, best %.2e)\n", k,
-                    growing ? "growing" : (tail ? "slow tail" : "stalled"), nz, last);
-          finish_in_x();
-          // the tail after a hand-over is 3-4 decades = 5-7 GMRES iterations: one cycle of 8, no restart in between
-          // round 4: the tail as s-step minimal-residual cycles (no Gram-Schmidt passes); HDG_TAIL_GMRES restores the GMRES cycle
-          if (tail && !opt.tail_gmres) return its + sstep_mr(qstar, gamma, didx, b, x, rtol, beta0, nz);
-          struct Guard { bool& f; bool old; ~Guard() { f = old; } } guard_{arnoldi_only, arnoldi_only};
-          arnoldi_only = true;  // robustness path after a growing / stalled iteration: the Arnoldi form
-          return its + gmres(qstar, gamma, didx, b, x, rtol, cfg.tent_maxit, true, nullptr, 0, nullptr, nullptr, beta0, tail ? opt.cheb_hand_cycle : 4);
-        }
-        last = std::min(last, nz);
-      }
+      if (!check) continue;
+      double nz = cell_norm ? std::sqrt(dot(g.Nc, cell_ss, ones_c, KC)) : std::sqrt(dot(NQ, z, z, KQ));
+      if (!(nz == nz)) throw NotConverged{"Chebyshev: NaN residual"};
+      if (debug_on()) fprintf(stderr, "[cheb]   k=%d  |Mr|/|Mr0| = %.3e\n", k, nz / beta0);
+      const ChebVerdict v = mon.observe(k, its, nz);
+      if (v == ChebVerdict::Continue) continue;
+      if (v != ChebVerdict::Converged && debug_on())
+        fprintf(stderr, "[cheb]   falling back to GMRES at k=%d (%s; |Mr| %.2e, best %.2e)\n", k, verdict_name(v), nz, mon.last);
+      finish_in_x();
+      if (v == ChebVerdict::Converged) return its;
+      // the tail after a hand-over is 3-4 decades = 5-7 GMRES iterations: one cycle of 8, no restart in between
+      // round 4: the tail as s-step minimal-residual cycles (no Gram-Schmidt passes); HDG_TAIL_GMRES restores the GMRES cycle
+      if (mon.tail && !opt.tail_gmres) return its + sstep_mr(S, x, rtol, beta0, nz);
+      // robustness path after a growing / stalled iteration: the Arnoldi form
+      return its + arnoldi_solve(S, x, rtol, cfg.tent_maxit, true, beta0, mon.tail ? opt.cheb_hand_cycle : 4);
     }
   }
 
@@ -2158,8 +2055,8 @@ struct Engine {
       lincomb(NQ, ri, wQ3);
       pgrad(wQ3, 1.0, wQ4, -1.0, stP[i], stL[i], gamma, rhs);
     }
-    int its = cfg.tent_solver == 0 ? gmres(Qstar[i - 1], gamma, i, rhs, Qtent[i])
-                                   : cheb_gmres(Qstar[i - 1], gamma, i, rhs, Qtent[i]);
+    const TentSystem S{Qstar[i - 1], gamma, i, rhs};
+    int its = cfg.tent_solver == 0 ? tent_krylov(S, Qtent[i], cfg.tent_rtol, cfg.tent_maxit, true) : cheb_gmres(S, Qtent[i]);
     it_sum[0] += its; it_cnt[0]++;
     return its;
   }
@@ -2934,7 +2831,7 @@ struct Engine {
   }
   void mono_precond(const V3& r, const double* qstar, double gamma, int didx, int psidx, V3& z) {
     zero(z.u, NQ);
-    gmres(qstar, gamma, didx, r.u, z.u, cfg.unsplit_inner_rtol, 200, false);
+    tent_krylov(TentSystem{qstar, gamma, didx, r.u}, z.u, cfg.unsplit_inner_rtol, 200, false);
     gamma_psi(z.u, nullptr, nullptr, wP1);
     axpby(NPv, 1.0, r.p, -1.0, wP1);
     gamma_mu(z.u, nullptr, nullptr, wL2);
@@ -2972,7 +2869,8 @@ struct Engine {
       while ((int)Zb.size() < m) { Zb.emplace_back(); alloc_block(Zb.back()); }
       alloc_block(r); alloc_block(w);
     }
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), gv(m + 1);
+    GivensLsq lsq(m);
+    std::vector<double> h((size_t)m);
     int its = 0;
     double beta0 = -1.0;
     while (true) {
@@ -2984,44 +2882,24 @@ struct Engine {
       if (beta <= rtol * beta0 || beta == 0.0) return its;
       copy_block(Vb[0], r);
       axpby_block(0.0, r, 1.0 / beta, Vb[0]);
-      std::fill(gv.begin(), gv.end(), 0.0);
-      gv[0] = beta;
+      lsq.start(beta);
       int j = 0;
       bool done = false;
       for (; j < m; j++) {
         precond(Vb[j], Zb[j]);
         apply(Zb[j], w);
         for (int l = 0; l <= j; l++) {  // modified Gram-Schmidt
-          double h = dot_block(w, Vb[l]);
-          H[(size_t)l * m + j] = h;
-          axpby_block(-h, Vb[l], 1.0, w);
+          h[l] = dot_block(w, Vb[l]);
+          axpby_block(-h[l], Vb[l], 1.0, w);
         }
         double hn = std::sqrt(dot_block(w, w));
-        H[(size_t)(j + 1) * m + j] = hn;
         if (hn > 0) { copy_block(Vb[j + 1], w); axpby_block(0.0, w, 1.0 / hn, Vb[j + 1]); }
-        for (int l = 0; l < j; l++) {
-          double a1 = H[(size_t)l * m + j], a2 = H[(size_t)(l + 1) * m + j];
-          H[(size_t)l * m + j] = cs[l] * a1 + sn[l] * a2;
-          H[(size_t)(l + 1) * m + j] = -sn[l] * a1 + cs[l] * a2;
-        }
-        double a1 = H[(size_t)j * m + j], a2 = H[(size_t)(j + 1) * m + j];
-        double rr = std::hypot(a1, a2);
-        cs[j] = (rr == 0) ? 1.0 : a1 / rr;
-        sn[j] = (rr == 0) ? 0.0 : a2 / rr;
-        H[(size_t)j * m + j] = rr;
-        H[(size_t)(j + 1) * m + j] = 0.0;
-        gv[j + 1] = -sn[j] * gv[j];
-        gv[j] = cs[j] * gv[j];
+        const double res = lsq.add_column(j, h.data(), hn);
         its++;
-        if (std::fabs(gv[j + 1]) <= rtol * beta0 || hn == 0.0) { j++; done = true; break; }
+        if (res <= rtol * beta0 || hn == 0.0) { j++; done = true; break; }
         if (its >= maxit) { j++; break; }
       }
-      std::vector<double> y(j, 0.0);
-      for (int l = j - 1; l >= 0; l--) {
-        double acc = gv[l];
-        for (int q = l + 1; q < j; q++) acc -= H[(size_t)l * m + q] * y[q];
-        y[l] = acc / H[(size_t)l * m + l];
-      }
+      const std::vector<double> y = lsq.solve(j);
       for (int l = 0; l < j; l++) axpby_block(y[l], Zb[l], 1.0, x);
       if (done) {
         // confirm with the true residual (the inner solves are inexact)
@@ -3198,8 +3076,8 @@ struct Engine {
     int it1, it2;
     {
       Timed tt_(*this, T_TENT);
-      it1 = cfg.tent_solver == 0 ? gmres(Qstar[0], dtt, 0, updU, Qtent[0])   // hdg_implicit.py:103-129
-                                 : cheb_gmres(Qstar[0], dtt, 0, updU, Qtent[0]);
+      const TentSystem S{Qstar[0], dtt, 0, updU};  // hdg_implicit.py:103-129
+      it1 = cfg.tent_solver == 0 ? tent_krylov(S, Qtent[0], cfg.tent_rtol, cfg.tent_maxit, true) : cheb_gmres(S, Qtent[0]);
     }
     {
       Timed tp_(*this, T_PRESS);
@@ -3273,7 +3151,7 @@ struct Engine {
   }
   void dg_precond(const V2& r, const double* qstar, double dtt, int psidx, V2& z) {
     zero(z.u, NQ);
-    gmres(qstar, dtt, 0, r.u, z.u, cfg.unsplit_inner_rtol, 200, false);
+    tent_krylov(TentSystem{qstar, dtt, 0, r.u}, z.u, cfg.unsplit_inner_rtol, 200, false);
     weak_div(z.u, 1.0, dg_rp, false);
     axpby(NPv, 1.0, r.p, -1.0, dg_rp);  // r_p - B u~
     use_pset(psidx);
@@ -4154,10 +4032,9 @@ struct Engine {
 
   // the host part of the state
   struct CkHost {
-    std::vector<double> ch_lmin, ch_lmax, ch_widen, bscale;
-    std::vector<long> ch_count;
-    std::vector<int> ch_last, ch_hand, bsep;
-    std::vector<char> ch_slow;
+    std::vector<ChebStage> ch;  // empty before the first Chebyshev solve
+    std::vector<double> bscale;
+    std::vector<int> bsep;
     double it_sum[4] = {0, 0, 0, 0};
     long it_cnt[4] = {0, 0, 0, 0}, ev[4] = {0, 0, 0, 0};
     double trace_scale = 0.0;
@@ -4169,8 +4046,8 @@ struct Engine {
   };
   CkHost ck_capture() const {
     CkHost h;
-    h.ch_lmin = ch_lmin; h.ch_lmax = ch_lmax; h.ch_widen = ch_widen; h.ch_count = ch_count; h.ch_last = ch_last;
-    h.ch_hand = ch_hand; h.ch_slow = ch_slow; h.bscale = bscale; h.bsep = bsep;
+    if (!cheb_history_empty(ch)) h.ch = ch;
+    h.bscale = bscale; h.bsep = bsep;
     for (int q = 0; q < 4; q++) { h.it_sum[q] = it_sum[q]; h.it_cnt[q] = it_cnt[q]; }
     h.ev[0] = ev_cg_replacements; h.ev[1] = ev_cg_floor_exits; h.ev[2] = n_sstep_cycles; h.ev[3] = n_sstep_fallbacks;
     h.trace_scale = trace_scale;
@@ -4186,8 +4063,7 @@ struct Engine {
     return h;
   }
   static void ck_write_host(const CkHost& h, ckpt::ByteWriter& solver, ckpt::ByteWriter& outputs) {
-    solver.vec(h.ch_lmin); solver.vec(h.ch_lmax); solver.vec(h.ch_widen); solver.vec(h.ch_count); solver.vec(h.ch_last);
-    solver.vec(h.ch_hand); solver.vec(h.ch_slow); solver.vec(h.bscale); solver.vec(h.bsep);
+    write_cheb_stages(solver, h.ch); solver.vec(h.bscale); solver.vec(h.bsep);
     solver.raw(h.it_sum, sizeof(h.it_sum)); solver.raw(h.it_cnt, sizeof(h.it_cnt)); solver.raw(h.ev, sizeof(h.ev));
     solver.put(h.trace_scale); solver.put(h.tracer_on); solver.put(h.tracer_vecs); solver.put(h.has_chd);
     outputs.raw(h.log, sizeof(h.log)); outputs.vec(h.probe_xy); outputs.put(h.pa_n); outputs.put(h.pa_every); outputs.put(h.pa_steps);
@@ -4195,17 +4071,14 @@ struct Engine {
   // empty return: read; otherwise what is wrong with the record
   std::string ck_read_host(CkHost& h, const void* solver, size_t ns, const void* outputs, size_t no) const {
     ckpt::ByteReader a(solver, ns), b(outputs, no);
-    a.vec(h.ch_lmin); a.vec(h.ch_lmax); a.vec(h.ch_widen); a.vec(h.ch_count); a.vec(h.ch_last);
-    a.vec(h.ch_hand); a.vec(h.ch_slow); a.vec(h.bscale); a.vec(h.bsep);
+    const std::string cheb_err = read_cheb_stages(a, (size_t)s + 1, h.ch);
+    a.vec(h.bscale); a.vec(h.bsep);
     a.raw(h.it_sum, sizeof(h.it_sum)); a.raw(h.it_cnt, sizeof(h.it_cnt)); a.raw(h.ev, sizeof(h.ev));
     h.trace_scale = a.get<double>(); h.tracer_on = a.get<int>(); h.tracer_vecs = a.get<int>(); h.has_chd = a.get<int>();
     if (!a.done()) return "section 'solver': the record does not have the length its fields need";
     b.raw(h.log, sizeof(h.log)); b.vec(h.probe_xy); h.pa_n = b.get<int>(); h.pa_every = b.get<int>(); h.pa_steps = b.get<long>();
     if (!b.done()) return "section 'outputs': the record does not have the length its fields need";
-    const size_t nh = h.ch_lmin.size();
-    if ((nh != 0 && nh != (size_t)s + 1) || h.ch_lmax.size() != nh) return "section 'solver': Chebyshev bounds of another stage count";
-    for (size_t n : {h.ch_widen.size(), h.ch_count.size(), h.ch_last.size(), h.ch_hand.size(), h.ch_slow.size()})
-      if (n != 0 && n != (size_t)s + 1) return "section 'solver': Chebyshev history of another stage count";
+    if (!cheb_err.empty()) return cheb_err;
     if (h.bscale.size() != (size_t)s + 1 || h.bsep.size() != (size_t)s + 1) return "section 'solver': forcing scales of another stage count";
     for (int q = 0; q < 3; q++)
       if (h.log[q][0] < 0 || h.log[q][1] < 0 || h.log[q][2] < 0 || h.log[q][2] > h.log[q][1] || h.log[q][3] < 0 ||
@@ -4410,8 +4283,8 @@ struct Engine {
     // ---- the engine becomes the saved one
     if (hs.tracer_vecs) { cg_setup(); tracer_alloc(); }
     if (hs.has_chd && !chd) chd = dalloc(NQ);
-    ch_lmin = hs.ch_lmin; ch_lmax = hs.ch_lmax; ch_widen = hs.ch_widen; ch_count = hs.ch_count; ch_last = hs.ch_last;
-    ch_hand = hs.ch_hand; ch_slow = hs.ch_slow; bscale = hs.bscale; bsep = hs.bsep;
+    ch = hs.ch.empty() ? std::vector<ChebStage>((size_t)s + 1) : hs.ch;
+    bscale = hs.bscale; bsep = hs.bsep;
     for (int q = 0; q < 4; q++) { it_sum[q] = hs.it_sum[q]; it_cnt[q] = hs.it_cnt[q]; }
     ev_cg_replacements = hs.ev[0]; ev_cg_floor_exits = hs.ev[1]; n_sstep_cycles = hs.ev[2]; n_sstep_fallbacks = hs.ev[3];
     trace_scale = hs.trace_scale;

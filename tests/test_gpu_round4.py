@@ -53,6 +53,36 @@ def test_sstep_tail_against_the_gmres_tail_and_the_oracle(hip_lib, tmp_path, k, 
         assert _rel(small["Q"], oQ) < 2e-8 and _rel(small["p"], op) < 2e-8 and _rel(small["lam"], o.lam) < 2e-8
 
 
+def test_solves_the_chebyshev_iteration_declines_run_by_sstep_cycles_or_arnoldi(hip_lib, tmp_path):
+    """The routes of Engine::tent_krylov that a default run seldom takes, k = 2, nx = 12, two steps.  (a) default.
+    (b) HDG_CHEB_MAX_EXPECTED=1: the Chebyshev iteration declines every solve after its Ritz cycle or its first norm
+    ("iterations predicted ... -> GMRES") and the whole rest runs as s-step minimal-residual cycles.  (c) the same with
+    HDG_GMRES_ARNOLDI=1: the declined solves run in the Arnoldi form, no s-step cycle anywhere.  One stopping rule (rtol 1e-10
+    on the preconditioned residual) in three schedules: the fields agree with (a) at 1e-9, the bound of the s-step / GMRES tail
+    test above.
+    Iterations per solve (tentative velocity, then the three condensed solves), measured on the commit before the routes were
+    rewired and unchanged by it: (a) 26.75, 12.125, 12, 12; (b) 25.875, 12.125, 12, 12; (c) 27.125, 12.125, 12, 12 -- (b)
+    needs fewer than the default, so there is no default <= mode chain to assert; the spread of the tentative solves is
+    27.125 - 25.875 = 1.25 per solve and none in the condensed solves: asserted with one iteration on top."""
+    res, its = {}, {}
+    for tag, env in (("a", {}), ("b", {"HDG_CHEB_MAX_EXPECTED": "1"}), ("c", {"HDG_CHEB_MAX_EXPECTED": "1", "HDG_GMRES_ARNOLDI": "1"})):
+        res[tag], log = _worker(tmp_path, tag, 2, 12, 2, env)
+        its[tag] = res[tag]["its"]
+        print(tag, "iterations per solve", its[tag])
+        if tag == "b":
+            assert "iterations predicted" in log and "[sstep] cycle" in log
+        if tag == "c":
+            assert "iterations predicted" in log and "[gmres]" in log and "[sstep]" not in log
+    for tag in ("b", "c"):
+        for name in ("Q", "p", "lam"):
+            print(tag, name, _rel(res[tag][name], res["a"][name]))
+            assert _rel(res[tag][name], res["a"][name]) < 1e-9, (tag, name)
+    tent = [its[t][0] for t in "abc"]
+    assert max(tent) - min(tent) <= 1.25 + 1.0, tent
+    for tag in ("b", "c"):
+        assert np.all(np.abs(its[tag][1:] - its["a"][1:]) <= 1.0), (tag, its)
+
+
 @pytest.mark.parametrize("k,level", [(1, 3), (2, 3), (3, 2)])
 def test_matrix_free_general_mesh_lift_equals_the_assembled_operators(hip_lib, k, level, monkeypatch):
     """k_g_lift (reference moment tables in LDS x per-cell geometry, one per-cell lifting matrix) against the CSR form of the BDM

@@ -541,6 +541,31 @@ def test_vertex_grid_level_plan_states_the_form_of_every_level(tmp_path):
     _host_check(tmp_path, "vertex_levels_check")
 
 
+def test_tentative_velocity_policy_and_givens_least_squares(tmp_path):
+    """csrc/hdg_krylov_host.hpp and csrc/hdg_tent_policy.hpp (plain C++, compiled here with g++): what the tentative-velocity
+    solver decides from the numbers it measures, stated as literal values derived by hand from the rules its loops followed
+    before the headers existed.
+    GivensLsq on a written-out 7 x 6 Hessenberg matrix, beta = 1.7: after each column the returned value is the residual
+    norm, and solve() the minimiser, of |beta e1 - H y| over the leading block to 1e-12 relative, against the normal
+    equations solved in long double; hn = 0 gives cs = 1, sn = 0 (with a zero diagonal too: rr = 0, nothing divided).
+    Check schedule: no history -> k = 4, 8, 12, ...; last = 22 after a head of 6 -> kfine = max(4, (22 - 6 - 4) & ~1) = 12:
+    8, 12, 14, 16, ... (fine step 3: 8, 12, 15, 18).
+    Verdicts at target 1e-10, beta0 = 1: growing when nz > 100 * best (bounds reset to -1, widen 1.25, 1.25^n cut at 4);
+    stalled after eight checks without halving (slow set, widen untouched), beyond 6 * expected + 64 iterations, or at the
+    iteration limit; deliberate hand-over at rate 0.3 from nz(4) = 1e-2, nz(8) = 1e-3 (rate 0.1^(1/4) = 0.562, 28 > 6
+    iterations left): slow tail, hand = 4, last = its, and the next solve hands over at its first check with k >= 4
+    (not with the GMRES tail); silent before min_k = 6 and within 6 iterations of the end; with rate 0 only k >= 16,
+    rate > 0.75, > 24 left fires; convergence sets slow exactly when its > 64 + 32.
+    Interval from Ritz real parts {1.1, 2.0, 3.2}: hybrid k = 2 [0.99, 4.16], merged with [0.9, 4.0] -> [0.9, 4.16], k = 1
+    upper factor 1.5, not hybrid 0.8 / 1.15, widen and the cheb_flo / cheb_fhi overrides multiply, lo <= 0 or hi <= lo rejected.
+    Ellipse [1, 4.8] at 0.3: theta 2.9, delta = sqrt(3.2851), rate = 2.47 / (2.9 + sqrt(5.1249)) to 1e-14, 39 iterations
+    for ten decades; [0.05, 6] predicts > 64.  s-step lengths: unknown residual min(6, smax); three decades at 1.7 per decade
+    ceil(5.1) + 1 = 7 cut to smax; never below 2; extension beyond the 0.7 * target margin by at least one.
+    Checkpoint: three records give the bytes of the seven literal columns (double, double, double, long, int, int, char)
+    and read back; no history is seven empty columns."""
+    _host_check(tmp_path, "tent_policy_check")
+
+
 def test_new_host_headers_compile_alone(tmp_path):
     """Each host-only header of csrc/ compiles on its own with g++ -Wall -Wextra -Werror: no HIP header behind it."""
     import shutil
@@ -551,7 +576,7 @@ def test_new_host_headers_compile_alone(tmp_path):
         pytest.skip("no g++")
     csrc = os.path.join(ROOT, "incompressibleeulerhdg_amd", "csrc")
     for h in ("hdg_dispatch.hpp", "hdg_mfma_pack.hpp", "hdg_row_log.hpp", "hdg_small_dense.hpp", "hdg_stage_coeffs.hpp",
-              "hdg_vertex_levels.hpp"):
+              "hdg_vertex_levels.hpp", "hdg_krylov_host.hpp", "hdg_tent_policy.hpp"):
         assert "hip" not in open(os.path.join(csrc, h)).read().split("#pragma once")[1].split("namespace hdg")[0], h
         tu = tmp_path / (h + ".cpp")
         tu.write_text(f'#include "{h}"\n')
