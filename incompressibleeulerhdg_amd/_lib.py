@@ -18,6 +18,7 @@ HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_mi355x.h"))
 CHECKPOINT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_checkpoint.h"))
 TRANSFER_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_transfer.h"))
 TRACER_DIFFUSION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_diffusion.h"))
+BUOYANCY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_buoyancy.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -90,7 +91,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -201,6 +202,13 @@ TRACER_DIFFUSION_SIGNATURES = {
     "hdg_apply_tracer_diffusion": [_h, _dp, _dp],
 }
 
+# Boussinesq buoyancy: the symbols include/hdg_buoyancy.h declares, in a table of their own like the three above
+BUOYANCY_SIGNATURES = {
+    "hdg_set_buoyancy": [_h, C.c_int, _dp, _dp],
+    "hdg_get_buoyancy": [_h, C.c_int, _dp, _dp],
+    "hdg_apply_buoyancy": [_h, _dp, _dp],
+}
+
 
 def load_library():
     """Load libhdg_mi355x.so; raise loudly when it has not been built."""
@@ -214,7 +222,7 @@ def load_library():
         )
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
-            list(TRACER_DIFFUSION_SIGNATURES.items()):
+            list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -514,6 +522,32 @@ class Engine:
         out = np.empty(self.shape_p)
         self._ck(self.lib.hdg_apply_tracer_diffusion(self.h, _ptr(q), _ptr(out)))
         return out
+
+    # --- Boussinesq buoyancy (include/hdg_buoyancy.h)
+    def set_buoyancy(self, beta, gravity=(0.0, -1.0)):
+        """The tracers force the flow: + sum_t beta_t q_t g in the momentum equation.  beta: one value for every tracer or a
+        sequence of n_tracers values (0: that tracer stays passive); None or zeros: off.  Needs a tracer (set_tracer)."""
+        if beta is not None:
+            beta = np.asarray(beta, dtype=np.float64)
+            beta = np.full(self.n_tracers, float(beta)) if beta.ndim == 0 else np.ascontiguousarray(beta.reshape(-1))
+        g = np.ascontiguousarray(np.asarray(gravity, dtype=np.float64).reshape(-1))
+        if g.shape != (2,):
+            raise ValueError(f"gravity must have two components (got {g.size})")
+        self._ck(self.lib.hdg_set_buoyancy(self.h, 0 if beta is None else len(beta), _ptr(beta), _ptr(g)))
+
+    def buoyancy(self):
+        """(beta (n_tracers,), gravity (2,)) as they are set; beta is all zero while the term is off."""
+        beta, g = np.zeros(self.n_tracers), np.zeros(2)
+        self._ck(self.lib.hdg_get_buoyancy(self.h, self.n_tracers, _ptr(beta), _ptr(g)))
+        return beta, g
+
+    def apply_buoyancy(self, q):
+        """B(q) = sum_t beta_t q_t g of nodal tracer fields (the layout of set_tracer) as a nodal velocity-space field
+        (the layout of get_field's Q), with the beta and gravity currently set (test hook)."""
+        q = _arr(q, self.shape_q)
+        f = np.empty(self.shape_Q)
+        self._ck(self.lib.hdg_apply_buoyancy(self.h, _ptr(q), _ptr(f)))
+        return f
 
     def cg_size(self):
         n = C.c_long()

@@ -31,6 +31,7 @@
 #include "../../include/hdg_checkpoint.h"
 #include "../../include/hdg_transfer.h"
 #include "../../include/hdg_tracer_diffusion.h"
+#include "../../include/hdg_buoyancy.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -49,6 +50,7 @@
 #include "hdg_stage_coeffs.hpp"
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
+#include "hdg_buoyancy.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
@@ -1574,6 +1576,14 @@ struct Engine {
     Terms terms;
     for (int j = 0; j < s; j++) terms.push_back({stQ[j], cq[j]});
     for (int j = 0; j < s; j++) terms.push_back({bvec(j), cb[j] * bscale[j]});
+    if (buoyancy_on())  // b_rhs[j] + B(q^(j)): the buoyancy vectors stand beside the user's forcing
+      for (int j = 0; j < s; j++) terms.push_back({buoy[(size_t)j], cb[j]});
+    return terms;
+  }
+  // the two implicit steppers: (Q, w) + dt (f(t_k) + B(q_n), w), slot 0
+  Terms start_terms(double dtt) const {
+    Terms terms{{curQ, 1.0}, {bvec(0), dtt * bscale[0]}};
+    if (buoyancy_on()) terms.push_back({buoy[0], dtt});
     return terms;
   }
   void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
@@ -2962,7 +2972,12 @@ struct Engine {
       backsub(wQ3, nullptr, curL, curQ, curP);
       it_sum[2] += its; it_cnt[2]++;
     } else if (key == HDG_KEY_PRESSURE_RECONSTRUCTION) {
-      precon_rhs(curQ, bvec(s), bscale[s], wP1, wL2);   // hdg_imex.py:201-207
+      if (buoyancy_on()) {  // the kernels take one forcing vector and read the neighbour's too: b_new + B(q^{n+1}) summed first
+        lincomb(NQ, {{bvec(s), bscale[s]}, {buoy[(size_t)s], 1.0}}, wQ3);
+        precon_rhs(curQ, wQ3, 1.0, wP1, wL2);
+      } else {
+        precon_rhs(curQ, bvec(s), bscale[s], wP1, wL2);   // hdg_imex.py:201-207
+      }
       condense(nullptr, wP1, wL2, wL1);
       its = trace_cg(wL1, recL);
       if (bwd_tol > 0.0) trace_scale = std::sqrt(dot(NLv, recL, recL, KL));
@@ -3047,6 +3062,7 @@ struct Engine {
     if (tracer_on) {  // hdg_implicit.py:93-96: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
       tracer_tendency(q_cur, uproj, q_t);
+      if (buoyancy_on()) buoyancy(q_cur, buoy[0]);  // slot 0: the tracer at the start of the step, next to f(t_k)
     }
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
@@ -3057,7 +3073,7 @@ struct Engine {
       // monolithic (u, phi, lambda) solve, hdg_implicit.py:153-186; fresh Function -> zero guess
       const int ps = get_pset(cfg.tau / dtt);
       if (!fg_b.u) fg_b = alloc3();
-      lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, fg_b.u);
+      lincomb(NQ, start_terms(dtt), fg_b.u);
       zero(fg_b.p, NPv); zero(fg_b.l, NLv);
       V3 x{updU, updP, updL};
       zero(updU, NQ); zero(updP, NPv); zero(updL, NLv);
@@ -3071,7 +3087,7 @@ struct Engine {
       return;
     }
     // rhs lives in updU: wQ1..wQ4 are scratch of GMRES and its preconditioner
-    lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, updU);  // (Q,w) + dt (f,w)
+    lincomb(NQ, start_terms(dtt), updU);  // (Q,w) + dt (f,w)
     zero(Qtent[0], NQ);
     int it1, it2;
     {
@@ -3181,9 +3197,10 @@ struct Engine {
     if (tracer_on) {  // dg_implicit.py:117-120: b_tracer is built from the fields at the START of the step
       cg_project(curQ, uproj);
       tracer_tendency(q_cur, uproj, q_t);
+      if (buoyancy_on()) buoyancy(q_cur, buoy[0]);  // slot 0: the tracer at the start of the step, next to f(t_k)
     }
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
-    lincomb(NQ, {{curQ, 1.0}, {bvec(0), dtt * bscale[0]}}, dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
+    lincomb(NQ, start_terms(dtt), dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
     zero(dg_b.p, NPv);
     zero(dg_x.u, NQ); zero(dg_x.p, NPv);                             // fresh Function: zero guess
     int it;
@@ -3615,6 +3632,62 @@ struct Engine {
     out2[0] = diff_lambda;
     out2[1] = kmax * cfg.dt * diff_lambda;
   }
+  // ---- Boussinesq buoyancy: the forcing slot j of a step becomes b_rhs[j] + B(q^(j)),
+  // B(q) = sum_t beta_t q_t g embedded in the velocity space (hdg_buoyancy.hpp).  The s + 1 vectors buoy[j] stand beside brhs and
+  // profile, whose meaning stays; they are allocated (zeroed: the kernels write the first NP modes only) on the first non-zero
+  // beta and rebuilt inside every step, so they are no state.  beta, g are configuration like kappa.  Without a tracer
+  // (hdg_set_tracer(NULL)) nothing forces the flow.
+  std::vector<double> by_beta;  // n_tr values while the term is on (some beta_t != 0), empty while it is off
+  double by_g[2] = {0.0, -1.0};
+  std::vector<double*> buoy;    // s + 1 slots, the last one for the pressure reconstruction
+  bool buoyancy_on() const { return tracer_on && !by_beta.empty(); }
+  BuoyCoef buoyancy_coef() const {
+    BuoyCoef B{};
+    for (size_t t = 0; t < by_beta.size(); t++) B.beta[t] = by_beta[t];
+    B.gx = by_g[0]; B.gy = by_g[1];
+    return B;
+  }
+  void set_buoyancy(int n, const double* beta, const double* grav) {
+    if (comm->size > 1) cg_setup();  // a strip: the tracer error of hdg_set_tracer
+    if (step_open) throw std::string("hdg_set_buoyancy: a step is open (between hdg_begin_step and the end of the step)");
+    if (!tracer_on) throw std::string("hdg_set_buoyancy: no tracer is set (hdg_set_tracer)");
+    bool any = false;
+    if (beta) {
+      if (n != n_tr) throw std::string("hdg_set_buoyancy: " + std::to_string(n) + " value(s) for " + std::to_string(n_tr) + " tracer(s)");
+      for (int t = 0; t < n; t++) {
+        if (!std::isfinite(beta[t])) throw std::string("hdg_set_buoyancy: beta[" + std::to_string(t) + "] = " + std::to_string(beta[t]) + " is not finite");
+        any = any || beta[t] != 0.0;
+      }
+    }
+    if (grav)
+      for (int d = 0; d < 2; d++)
+        if (!std::isfinite(grav[d])) throw std::string("hdg_set_buoyancy: g[" + std::to_string(d) + "] = " + std::to_string(grav[d]) + " is not finite");
+    by_g[0] = grav ? grav[0] : 0.0; by_g[1] = grav ? grav[1] : -1.0;
+    if (!any) { by_beta.clear(); return; }  // off: the vectors stay allocated, nothing reads them
+    if (buoy.empty())
+      for (int j = 0; j <= s; j++) {
+        buoy.push_back(dalloc(NQ));
+        HIPCHECK(hipMemsetAsync(buoy.back(), 0, sizeof(double) * NQ, stream));
+      }
+    by_beta.assign(beta, beta + n);
+  }
+  // f = B(q): q the n_tr tracers tracer-major, f a velocity vector whose modes NP .. NU-1 are zero (owned rows only)
+  void buoyancy(const double* q, double* f) {
+    int live = 0;
+    for (double b : by_beta) live += b != 0.0;
+    tally(LC_OTHER, live * bP() + 2.0 * bP());
+    const BuoyCoef B = buoyancy_coef();
+    if (general) by_degree([&](auto k) { k_g_buoyancy<k()><<<(gm->nc + 63) / 64, 64, 0, stream>>>(gm->nc, B, NPv, q, f); });
+    else by_degree([&](auto k) { k_buoyancy<k()><<<cell_grid(), bs(), 0, stream>>>(g, B, NPv, q, f); });
+    fl.set(f, 0);
+  }
+  // slot i of an IMEX step takes the stage tracer q_st[i], complete at the end of tracer_begin_step (i = 0) / tracer_stage(i);
+  // behind the last stage q_fin = q_{n+1} is complete too: slot s, the pressure reconstruction
+  void buoyancy_slot(int i) {
+    if (!buoyancy_on()) return;
+    buoyancy(q_st[(size_t)i], buoy[(size_t)i]);
+    if (i == s - 1) buoyancy(q_fin, buoy[(size_t)s]);
+  }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
     if (!tracer_on) return;
@@ -3625,6 +3698,7 @@ struct Engine {
       tracer_tendency(q_st[0], uproj, q_t);
       axpby(NTv(), cfg.dt * cfg.b_expl[0], q_t, 1.0, q_fin);
     }
+    buoyancy_slot(0);
   }
   // hdg_imex.py:622-623: q_i = q_0 + dt sum_{j<i} a_expl[i,j] T(q_j, P(Q_i)); plus the i-th term of the final residual
   void tracer_stage(int i) {
@@ -3641,6 +3715,7 @@ struct Engine {
       tracer_tendency(q_st[i], uproj, q_t);
       axpby(NTv(), cfg.dt * cfg.b_expl[i], q_t, 1.0, q_fin);
     }
+    buoyancy_slot(i);
   }
   void tracer_finish_step() {  // hdg_imex.py:638-639
     if (tracer_on) copy(q_cur, q_fin, NTv());
@@ -4162,6 +4237,8 @@ struct Engine {
     f.add("dg_rtol", cfg.dg_rtol); f.add("dg_restart", (long)cfg.dg_restart); f.add("dg_maxit", (long)cfg.dg_maxit);
     f.add("n_tracers", (long)cfg.n_tracers);
     for (size_t t = 0; t < tr_kappa.size(); t++) f.add("tracer_kappa[" + std::to_string(t) + "]", tr_kappa[t]);  // only with some kappa != 0
+    for (size_t t = 0; t < by_beta.size(); t++) f.add("buoyancy_beta[" + std::to_string(t) + "]", by_beta[t]);  // only with some beta != 0
+    if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (general) {
       f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
       f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
@@ -5219,6 +5296,34 @@ int hdg_apply_tracer_diffusion(hdg_handle* h, const double* q, double* out) {
   E.put_P(q, E.wP1);
   E.apply_tracer_diffusion(E.wP1, E.q_t);
   E.get_P(E.q_t, out);
+  HDG_API_END(h)
+}
+
+
+// ---- Boussinesq buoyancy (include/hdg_buoyancy.h)
+int hdg_set_buoyancy(hdg_handle* h, int n, const double* beta, const double g[2]) {
+  HDG_API_BEGIN(h)
+  E.set_buoyancy(n, beta, g);
+  HDG_API_END(h)
+}
+int hdg_get_buoyancy(hdg_handle* h, int n, double* beta, double g[2]) {
+  HDG_API_BEGIN(h)
+  if (!beta || !g) throw std::string("null argument");
+  if (n != E.n_tr) throw std::string("hdg_get_buoyancy: " + std::to_string(n) + " value(s) for " + std::to_string(E.n_tr) + " tracer(s)");
+  for (int t = 0; t < n; t++) beta[t] = E.by_beta.empty() ? 0.0 : E.by_beta[(size_t)t];
+  g[0] = E.by_g[0]; g[1] = E.by_g[1];
+  HDG_API_END(h)
+}
+int hdg_apply_buoyancy(hdg_handle* h, const double* q, double* f) {
+  HDG_API_BEGIN(h)
+  if (!q || !f) throw std::string("null argument");
+  if (E.comm->size > 1) E.cg_setup();  // a strip: the tracer error of hdg_set_tracer
+  if (E.step_open) throw std::string("hdg_apply_buoyancy: a step is open");
+  E.tracer_alloc();
+  for (int t = 0; t < E.n_tr; t++) E.put_P(q + t * E.NPb, E.q_t + t * E.NPv);
+  E.zero(E.wQ1, E.NQ);
+  E.buoyancy(E.q_t, E.wQ1);
+  E.get_Q(E.wQ1, f);
   HDG_API_END(h)
 }
 

@@ -85,6 +85,11 @@ def build_parser():
     parser.add_argument("--tracer_diffusivity", metavar="K", type=float, nargs="+", default=None,
                         help="molecular diffusivity of the tracers (with --tracer_advection): one value for all of them or "
                              "exactly --tracers values; explicit in time, see the printed diffusion number")
+    parser.add_argument("--buoyancy", metavar="B", type=float, nargs="+", default=None,
+                        help="Boussinesq buoyancy (with --tracer_advection): the momentum equation gains sum_t B_t q_t g; one "
+                             "value for all tracers or exactly --tracers values, 0 keeps a tracer passive; explicit in time")
+    parser.add_argument("--gravity", metavar=("GX", "GY"), type=float, nargs=2, default=None,
+                        help="the constant g of --buoyancy (default 0 -1)")
     parser.add_argument("--tracers", metavar="N", type=int, default=1,
                         help="number of passive tracers advected through the one flow (with --tracer_advection); tracer m "
                              "starts from sin(2 pi (m+1) x) sin(2 pi (m+1) y)")
@@ -172,6 +177,42 @@ def check_tracers(args):
         for m, x in enumerate(kappa):
             if not (np.isfinite(x) and x >= 0):
                 raise RuntimeError(f"--tracer_diffusivity: value {m} ({x}) is not a finite number >= 0")
+    beta = args.buoyancy
+    if args.gravity is not None and beta is None:
+        raise RuntimeError("--gravity needs --buoyancy")
+    if beta is not None:
+        if not args.tracer_advection:
+            raise RuntimeError("--buoyancy needs --tracer_advection")
+        if len(beta) not in (1, args.tracers):
+            raise RuntimeError(f"--buoyancy takes one value or --tracers = {args.tracers} values (got {len(beta)})")
+        for m, x in enumerate(beta):
+            if not np.isfinite(x):
+                raise RuntimeError(f"--buoyancy: value {m} ({x}) is not a finite number")
+        for m, x in enumerate(args.gravity or ()):
+            if not np.isfinite(x):
+                raise RuntimeError(f"--gravity: component {m} ({x}) is not a finite number")
+
+
+def nodal_mean(coordinates, degree, values):
+    """The mean over the domain of a broken nodal P_k field (k >= 1), on the host: `coordinates` (n_cells * n_p, 2) are the
+    node positions cell by cell, every cell an affine image of one node set.  The weights of the node set (the cell mean of a
+    polynomial as a combination of its node values) come from the moments of the barycentric monomials,
+    mean(l1^a l2^b) = 2 a! b! / (a + b + 2)!."""
+    from math import factorial
+
+    n_p = (degree + 1) * (degree + 2) // 2
+    X = np.asarray(coordinates, dtype=float).reshape(-1, n_p, 2)
+    area2 = lambda A, B, C: (B[..., 0] - A[..., 0]) * (C[..., 1] - A[..., 1]) - (C[..., 0] - A[..., 0]) * (B[..., 1] - A[..., 1])
+    x0 = X[0]
+    corners = max(((i, j, m) for i in range(n_p) for j in range(i + 1, n_p) for m in range(j + 1, n_p)),
+                  key=lambda t: abs(area2(x0[t[0]], x0[t[1]], x0[t[2]])))  # the vertices are among the nodes
+    A, B, C = (x0[i] for i in corners)
+    l1, l2 = area2(A, x0, C) / area2(A, B, C), area2(A, B, x0) / area2(A, B, C)
+    powers = [(a, b) for a in range(degree + 1) for b in range(degree + 1 - a)]
+    V = np.array([l1 ** a * l2 ** b for a, b in powers])
+    w = np.linalg.solve(V, np.array([2.0 * factorial(a) * factorial(b) / factorial(a + b + 2) for a, b in powers]))
+    area = np.abs(area2(X[:, corners[0]], X[:, corners[1]], X[:, corners[2]]))
+    return float(np.sum(area * (np.asarray(values, dtype=float).reshape(-1, n_p) @ w)) / np.sum(area))
 
 
 def check_checkpoint(args):
@@ -410,6 +451,9 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.tracer_diffusivity is not None:
         kappa = args.tracer_diffusivity
         several["tracer_diffusivity"] = kappa[0] if len(kappa) == 1 else kappa
+    if args.buoyancy is not None:
+        several["buoyancy"] = args.buoyancy[0] if len(args.buoyancy) == 1 else args.buoyancy
+        several["gravity"] = tuple(args.gravity) if args.gravity is not None else (0.0, -1.0)
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
@@ -527,6 +571,17 @@ def _run(args, ranks):
         Q_0, p_0, q_start = start_from(args, ranks, timestepper)
         if args.tracer_advection and q_start is not None:
             q_0 = q_start
+    if args.buoyancy is not None:
+        # the mean force of the initial state, sum_t beta_t mean(q_t) g: on the periodic square a uniform acceleration
+        beta = args.buoyancy * (args.tracers if len(args.buoyancy) == 1 else 1)
+        grav = args.gravity if args.gravity is not None else [0.0, -1.0]
+        V_q = timestepper._V_q
+        fields = q_0 if isinstance(q_0, (list, tuple)) else [q_0]
+        mean = sum(b * nodal_mean(V_q.coordinates, V_q.degree, timestepper._as_nodal_pressure(q)) for b, q in zip(beta, fields))
+        print(f"buoyancy = {' '.join(repr(x) for x in args.buoyancy)}")
+        print(f"gravity = {' '.join(repr(float(x)) for x in grav)}")
+        print(f"buoyancy mean force = {mean * grav[0]:.6g} {mean * grav[1]:.6g}")
+        print()
     kw = {"fused": True} if (args.fused and args.timestepper != "implicit") else {}
     if args.diagnostics:
         kw["diagnostics"] = True

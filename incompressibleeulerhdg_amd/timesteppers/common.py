@@ -67,6 +67,12 @@ class IncompressibleEuler(ABC):
         self._label = label
         # tracer_diffusivity=: kappa of every tracer (a scalar or n_tracers values); None: no call at all
         self._tracer_diffusivity = engine_options.pop("tracer_diffusivity", None)
+        # buoyancy=, gravity=: beta of every tracer (a scalar or n_tracers values) and g of the Boussinesq term + sum_t beta_t q_t g
+        # (DESIGN.md section 20); None: no call at all.  Set once the tracers are (Engine.set_buoyancy needs them).
+        self._buoyancy = engine_options.pop("buoyancy", None)
+        self._gravity = engine_options.pop("gravity", None)
+        if self._gravity is not None and self._buoyancy is None:
+            raise ValueError("gravity= needs buoyancy=")
         self._engine_options = engine_options
         self._engine = None
         # common.py:72-73
@@ -154,12 +160,20 @@ class IncompressibleEuler(ABC):
         """q_initial (expression / array / None, driver.py:340-344; a list of them for several tracers) -> the engine's
         tracer state; returns whether a tracer is advected."""
         if q_initial is None or q_initial is False:
+            if self._buoyancy is not None:
+                raise ValueError("buoyancy= needs a tracer (q_initial)")
             self._engine.set_tracer(None)
             self.q_tracer, self.q_tracers = None, []
             return False
         self._engine.set_tracer(self._stack_tracers(q_initial, self._engine.n_tracers))
+        self._set_buoyancy()
         self._tracer_function()
         return True
+
+    def _set_buoyancy(self):
+        """buoyancy= / gravity= of the constructor, once the engine holds its tracers"""
+        if self._buoyancy is not None:
+            self._engine.set_buoyancy(self._buoyancy, (0.0, -1.0) if self._gravity is None else self._gravity)
 
     def _tracer_function(self):
         """Fetches the tracers: self.q_tracers (all of them), self.q_tracer (tracer 0); returns what the callbacks are
@@ -271,6 +285,9 @@ class IncompressibleEuler(ABC):
                                  f"{len(np.asarray(requests[name], dtype=float).reshape(-1, 2))}")
         if saved["step"] > nt:
             raise ValueError(f"restart: the checkpoint was written after step {saved['step']}, this run ends after step {nt}")
+        if self._buoyancy is not None and saved["tracer"]:  # configuration, like the diffusivities: set before the load
+            eng.set_tracer(np.zeros(eng.shape_q))
+            self._set_buoyancy()
         k0, t0 = eng.load_checkpoint(blob)
         if saved["tracer"]:
             self._tracer_function()
