@@ -19,6 +19,7 @@ CHECKPOINT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_c
 TRANSFER_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_transfer.h"))
 TRACER_DIFFUSION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_diffusion.h"))
 BUOYANCY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_buoyancy.h"))
+VISCOSITY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_viscosity.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -91,7 +92,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -209,6 +210,21 @@ BUOYANCY_SIGNATURES = {
     "hdg_apply_buoyancy": [_h, _dp, _dp],
 }
 
+# viscous term: the symbols include/hdg_viscosity.h declares, in a table of their own like the four above
+VISCOSITY_SIGNATURES = {
+    "hdg_set_viscosity": [_h, C.c_double, C.c_int],
+    "hdg_get_viscosity": [_h, _dp, C.POINTER(C.c_int), _dp],
+    "hdg_apply_viscosity": [_h, C.c_int, _dp, _dp],
+}
+WALL_MODES = {"free_slip": 0, "no_slip": 1}
+
+
+def wall_code(wall):
+    """'free_slip' / 'no_slip' -> the integer of include/hdg_viscosity.h"""
+    if wall not in WALL_MODES:
+        raise ValueError(f"wall must be one of {sorted(WALL_MODES)} (got {wall!r})")
+    return WALL_MODES[wall]
+
 
 def load_library():
     """Load libhdg_mi355x.so; raise loudly when it has not been built."""
@@ -222,7 +238,7 @@ def load_library():
         )
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
-            list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()):
+            list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -548,6 +564,34 @@ class Engine:
         f = np.empty(self.shape_Q)
         self._ck(self.lib.hdg_apply_buoyancy(self.h, _ptr(q), _ptr(f)))
         return f
+
+    # --- viscous term (include/hdg_viscosity.h; DESIGN.md section 21)
+    def set_viscosity(self, nu, wall="free_slip"):
+        """+ nu Laplace u in the momentum equation, explicit in time: the symmetric interior-penalty form on the velocity
+        space with free-slip ('free_slip') or no-slip ('no_slip') walls.  nu = 0: off."""
+        self._ck(self.lib.hdg_set_viscosity(self.h, float(nu), wall_code(wall)))
+
+    def _get_viscosity(self):
+        nu, wall, out = C.c_double(), C.c_int(), np.zeros(2)
+        self._ck(self.lib.hdg_get_viscosity(self.h, C.byref(nu), C.byref(wall), _ptr(out)))
+        return nu.value, wall.value, out
+
+    def viscosity(self):
+        """(nu, wall) as they are set; nu is 0 while the term is off."""
+        nu, wall, _ = self._get_viscosity()
+        return nu, {v: k for k, v in WALL_MODES.items()}[wall]
+
+    def viscosity_number(self):
+        """(Lambda_u, nu dt Lambda_u): Lambda_u is an upper bound of the spectral radius of M^-1 V in the wall mode set."""
+        out = self._get_viscosity()[2]
+        return float(out[0]), float(out[1])
+
+    def apply_viscosity(self, Q, wall="free_slip"):
+        """M^-1 V Q of a nodal velocity-space field (the layout of get_field's Q), without nu (test hook)."""
+        Q = _arr(Q, self.shape_Q)
+        out = np.empty(self.shape_Q)
+        self._ck(self.lib.hdg_apply_viscosity(self.h, wall_code(wall), _ptr(Q), _ptr(out)))
+        return out
 
     def cg_size(self):
         n = C.c_long()

@@ -32,6 +32,7 @@
 #include "../../include/hdg_transfer.h"
 #include "../../include/hdg_tracer_diffusion.h"
 #include "../../include/hdg_buoyancy.h"
+#include "../../include/hdg_viscosity.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -51,6 +52,7 @@
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
 #include "hdg_buoyancy.hpp"
+#include "hdg_viscosity.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
@@ -1578,12 +1580,15 @@ struct Engine {
     for (int j = 0; j < s; j++) terms.push_back({bvec(j), cb[j] * bscale[j]});
     if (buoyancy_on())  // b_rhs[j] + B(q^(j)): the buoyancy vectors stand beside the user's forcing
       for (int j = 0; j < s; j++) terms.push_back({buoy[(size_t)j], cb[j]});
+    if (viscosity_on())  // ... + nu M^-1 V Q^(j): vectors of their own again; filled by viscosity_slots
+      for (int j = 0; j < s; j++) terms.push_back({visc[(size_t)j], cb[j]});
     return terms;
   }
   // the two implicit steppers: (Q, w) + dt (f(t_k) + B(q_n), w), slot 0
   Terms start_terms(double dtt) const {
     Terms terms{{curQ, 1.0}, {bvec(0), dtt * bscale[0]}};
     if (buoyancy_on()) terms.push_back({buoy[0], dtt});
+    if (viscosity_on()) terms.push_back({visc[0], dtt});
     return terms;
   }
   void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
@@ -2057,6 +2062,7 @@ struct Engine {
     residual_coeffs(cfg, i, cq, cb);
     // rhs = r_i - (I - gamma F) Q_i + gamma g(w, p_i, lambda_i)      (hdg_imex.py:239-247)
     double* rhs = updU;  // _update.u is overwritten by the following pressure solve anyway
+    viscosity_slots(cb);
     const Terms ri = residual_terms(cq, cb);               // r_i
     adv_apply(stQ[i], Qstar[i - 1], wQ4, gamma);           // (I - gamma F) Q_i
     // r_i is formed inside the pressure-gradient kernel where that has a form for it; otherwise as a vector of its own (the
@@ -2930,6 +2936,7 @@ struct Engine {
     if (!fg_b.u) fg_b = alloc3();
     std::vector<double> cq, cb;
     residual_coeffs(cfg, i, cq, cb);
+    viscosity_slots(cb);
     residual_vector(cq, cb, fg_b.u);
     zero(fg_b.p, NPv);
     zero(fg_b.l, NLv);
@@ -2965,6 +2972,7 @@ struct Engine {
     } else if (key == HDG_KEY_FINAL_STAGE) {
       std::vector<double> cq, cb;
       final_residual_coeffs(cfg, cq, cb);
+      viscosity_slots(cb);
       residual_vector(cq, cb, wQ3);                     // r^{n+1}  (hdg_imex.py:190-192)
       condense(wQ3, nullptr, nullptr, wL1);
       if (bwd_tol > 0.0) zero(curL, NLv);
@@ -2972,8 +2980,12 @@ struct Engine {
       backsub(wQ3, nullptr, curL, curQ, curP);
       it_sum[2] += its; it_cnt[2]++;
     } else if (key == HDG_KEY_PRESSURE_RECONSTRUCTION) {
-      if (buoyancy_on()) {  // the kernels take one forcing vector and read the neighbour's too: b_new + B(q^{n+1}) summed first
-        lincomb(NQ, {{bvec(s), bscale[s]}, {buoy[(size_t)s], 1.0}}, wQ3);
+      if (viscosity_on()) viscosity_slot(s, curQ);  // slot s: Q_{n+1}, complete since the final-stage back-substitution
+      if (buoyancy_on() || viscosity_on()) {  // the kernels take one forcing vector and read the neighbour's too: b_new + B(q^{n+1}) + nu M^-1 V Q_{n+1} summed first
+        Terms bnew{{bvec(s), bscale[s]}};
+        if (buoyancy_on()) bnew.push_back({buoy[(size_t)s], 1.0});
+        if (viscosity_on()) bnew.push_back({visc[(size_t)s], 1.0});
+        lincomb(NQ, bnew, wQ3);
         precon_rhs(curQ, wQ3, 1.0, wP1, wL2);
       } else {
         precon_rhs(curQ, bvec(s), bscale[s], wP1, wL2);   // hdg_imex.py:201-207
@@ -3009,6 +3021,7 @@ struct Engine {
   // curL and recL keep their copies too (finish_step): the final-stage and reconstruction solves warm-start from the values
   // at those addresses, and HDG_STATE_RECON is readable.
   void begin_step(bool whole_step = false) {
+    visc_valid = 0; visc_step = true;  // the viscous slots of the last step are stale
     if (whole_step && opt.glue_fusion) { std::swap(stQ[0], curQ); return; }
     copy(stQ[0], curQ, NQ); copy(stP[0], curP, NPv); copy(stL[0], curL, NLv);
   }
@@ -3019,6 +3032,7 @@ struct Engine {
     axpby(NLv, 1.0, updL, 1.0, stL[i]);
   }
   void finish_step() {
+    visc_step = false;
     copy(curP, recP, NPv);
     copy(curL, recL, NLv);
     shift(curP, curL);
@@ -3067,6 +3081,7 @@ struct Engine {
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
     auto tracer_end = [&]() { if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur); };
+    if (viscosity_on()) viscosity_apply(curQ, visc_nu, visc_wall, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
     ensure_dinv(0, dtt);
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }             // hdg_implicit.py:98
     if (!cfg.use_projection) {
@@ -3199,6 +3214,7 @@ struct Engine {
       tracer_tendency(q_cur, uproj, q_t);
       if (buoyancy_on()) buoyancy(q_cur, buoy[0]);  // slot 0: the tracer at the start of the step, next to f(t_k)
     }
+    if (viscosity_on()) viscosity_apply(curQ, visc_nu, visc_wall, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
     lincomb(NQ, start_terms(dtt), dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
     zero(dg_b.p, NPv);
@@ -3687,6 +3703,80 @@ struct Engine {
     if (!buoyancy_on()) return;
     buoyancy(q_st[(size_t)i], buoy[(size_t)i]);
     if (i == s - 1) buoyancy(q_fin, buoy[(size_t)s]);
+  }
+  // ---- viscous term: the forcing slot j of a step becomes b_rhs[j] + B(q^(j)) + nu M^-1 V Q^(j), V the
+  // symmetric interior-penalty form on [DG_{k+1}]^2 with free-slip or no-slip Nitsche walls.  Structured meshes: nine scalar
+  // NU x NU blocks per element shape (hdg_tables.hpp: ViscosityTables) applied by k_viscosity; general meshes: M^-1 V assembled
+  // once per wall mode (hdg_general.hpp: assemble_viscosity) and applied by the CSR kernel.  The s + 1 vectors visc[j] stand
+  // beside brhs, profile and buoy; they are allocated (zeroed: the kernel writes owned rows only) on the first nu != 0 and
+  // rebuilt inside every step, so they are no state.  Slot j < s is filled from stQ[j] the first time a residual of the open
+  // step reads it (visc_valid, cleared by begin_step; stQ[j] is final once stage j + 1 begins, so the Richardson passes of a
+  // stage reuse it); outside a step a read recomputes.  nu and the wall mode are configuration like kappa.
+  double visc_nu = 0.0;
+  int visc_wall = 0;  // 0 free slip, 1 no slip
+  std::vector<double*> visc;
+  unsigned visc_valid = 0;   // bit j: slot j holds nu M^-1 V Q^(j) of the open step
+  bool visc_step = false;    // between begin_step and finish_step
+  const double* d_visctab = nullptr;
+  DevCsr gvisc[2];
+  double visc_lambda[2] = {-1.0, -1.0};  // upper bound of rho(M^-1 V) per wall mode; < 0: not built
+  bool viscosity_on() const { return visc_nu != 0.0; }
+  void visc_setup(int wall) {
+    if (visc_lambda[wall] >= 0.0) return;
+    if (general) {
+      if (comm->size > 1) throw std::string("viscosity on a general mesh: single rank only");
+      double lam = 0.0;
+      gvisc[wall] = upload_csr(assemble_viscosity(*gtab, *gm, wall == 1, lam));
+      visc_lambda[wall] = lam;
+    } else {
+      const ViscosityTables V(K, g.h);
+      if (!d_visctab) d_visctab = upload(V.packed());
+      visc_lambda[0] = visc_lambda[1] = V.lambda;
+    }
+  }
+  static void visc_check_wall(const char* who, int wall) {
+    if (wall != 0 && wall != 1) throw std::string(who) + ": wall = " + std::to_string(wall) + " (0: free slip, 1: no slip)";
+  }
+  void set_viscosity(double nu, int wall) {
+    if (step_open) throw std::string("hdg_set_viscosity: a step is open (between hdg_begin_step and the end of the step)");
+    if (!(nu >= 0.0) || !std::isfinite(nu)) throw std::string("hdg_set_viscosity: nu = " + std::to_string(nu) + " is not a finite value >= 0");
+    visc_check_wall("hdg_set_viscosity", wall);
+    if (nu != 0.0) {
+      visc_setup(wall);
+      if (visc.empty())
+        for (int j = 0; j <= s; j++) {
+          visc.push_back(dalloc(NQ));
+          HIPCHECK(hipMemsetAsync(visc.back(), 0, sizeof(double) * NQ, stream));
+        }
+    }
+    visc_nu = nu; visc_wall = wall;  // off: the vectors stay allocated, nothing reads them
+    visc_valid = 0;
+  }
+  // out = sc M^-1 V Q (owned rows); Q's ghost rows are filled here: wrapped on the periodic square, one exchange on a strip
+  void viscosity_apply(const double* Q, double sc, int wall, double* out) {
+    if (general) { csr(gvisc[wall], Q, sc, 0.0, out); return; }  // tallied in 'other' by csr()
+    tally(LC_OTHER, 2.0 * bQ());
+    stencil_in(Q, FQ);
+    by_degree([&](auto k) { k_viscosity<k()><<<cell_grid(), bs(), 0, stream>>>(g, d_visctab, sc, wall, Q, out); });
+    fl.set(out, 0);
+  }
+  void viscosity_slot(int j, const double* Q) {
+    if (visc_step && (visc_valid >> j & 1u)) return;
+    viscosity_apply(Q, visc_nu, visc_wall, visc[(size_t)j]);
+    visc_valid |= 1u << j;
+  }
+  // the slots a residual with the forcing coefficients cb reads
+  void viscosity_slots(const std::vector<double>& cb) {
+    if (!viscosity_on()) return;
+    for (int j = 0; j < s; j++)
+      if (cb[(size_t)j] != 0.0) viscosity_slot(j, stQ[j]);
+  }
+  void viscosity_number(double nu, int wall, double* out2) {
+    if (!(nu >= 0.0) || !std::isfinite(nu)) throw std::string("hdg_get_viscosity: nu = " + std::to_string(nu) + " is not a finite value >= 0");
+    visc_check_wall("hdg_get_viscosity", wall);
+    visc_setup(wall);
+    out2[0] = visc_lambda[wall];
+    out2[1] = nu * cfg.dt * visc_lambda[wall];
   }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
@@ -4239,6 +4329,7 @@ struct Engine {
     for (size_t t = 0; t < tr_kappa.size(); t++) f.add("tracer_kappa[" + std::to_string(t) + "]", tr_kappa[t]);  // only with some kappa != 0
     for (size_t t = 0; t < by_beta.size(); t++) f.add("buoyancy_beta[" + std::to_string(t) + "]", by_beta[t]);  // only with some beta != 0
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
+    if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
     if (general) {
       f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
       f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
@@ -5324,6 +5415,33 @@ int hdg_apply_buoyancy(hdg_handle* h, const double* q, double* f) {
   E.zero(E.wQ1, E.NQ);
   E.buoyancy(E.q_t, E.wQ1);
   E.get_Q(E.wQ1, f);
+  HDG_API_END(h)
+}
+
+
+// ---- viscous term (include/hdg_viscosity.h)
+int hdg_set_viscosity(hdg_handle* h, double nu, int wall) {
+  HDG_API_BEGIN(h)
+  E.set_viscosity(nu, wall);
+  HDG_API_END(h)
+}
+int hdg_get_viscosity(hdg_handle* h, double* nu, int* wall, double out2[2]) {
+  HDG_API_BEGIN(h)
+  if (!nu || !wall) throw std::string("null argument");
+  *nu = E.visc_nu; *wall = E.visc_wall;
+  if (out2) E.viscosity_number(E.visc_nu, E.visc_wall, out2);
+  HDG_API_END(h)
+}
+int hdg_apply_viscosity(hdg_handle* h, int wall, const double* Q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!Q || !out) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_apply_viscosity: a step is open");
+  hdg::Engine::visc_check_wall("hdg_apply_viscosity", wall);
+  E.visc_setup(wall);
+  E.put_Q(Q, E.wQ1);
+  E.zero(E.wQ2, E.NQ);
+  E.viscosity_apply(E.wQ1, 1.0, wall, E.wQ2);
+  E.get_Q(E.wQ2, out);
   HDG_API_END(h)
 }
 

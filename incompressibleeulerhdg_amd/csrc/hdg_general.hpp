@@ -905,6 +905,115 @@ inline Csr assemble_tracer_diffusion(const GeneralTables& T, const GMesh& M, dou
   return out;
 }
 
+// ------------------------------------------------------------------------------------------
+// Viscous term on a general triangulation (the form and its blocks: hdg_tables.hpp, ViscosityTables):
+// M^-1 V assembled once in the orthonormal modal basis psi = Dub / sqrt(detJ) of [DG_{k+1}]^2, rows and columns
+// c * 2 nu + d * nu + m (the modal velocity layout), with eta_e = (p+1)(p+2)/4 max(P_K / |K|), p = k + 1, on interior edges and
+// eta_b = (p+1)(p+2)/2 P_K / |K| on walls, from the actual perimeters and areas.  Interior edges and the volume act on each
+// component alone; a wall edge with normal n adds n n^T (x) W_e, W_e = int_e (psi_r dn psi_m + psi_m dn psi_r - eta_b psi_r psi_m),
+// which couples the components, and with no slip t t^T (x) W_e as well (together I (x) W_e).  lambda: the infinity norm.
+// ------------------------------------------------------------------------------------------
+inline Csr assemble_viscosity(const GeneralTables& T, const GMesh& M, bool no_slip, double& lambda) {
+  const int p = T.k + 1, nu = T.nu, n2 = 2 * nu, nc = M.nc;
+  Dubiner U(p);
+  CsrBuilder A(nc * n2, nc * n2);
+  auto add2 = [&](int ca, int cb, int r, int m, real v, real wxx, real wxy, real wyy) {  // (w_{d1 d2}) (x) v
+    A.add(ca * n2 + r, cb * n2 + m, (double)(wxx * v));
+    A.add(ca * n2 + nu + r, cb * n2 + nu + m, (double)(wyy * v));
+    if (wxy != 0) {
+      A.add(ca * n2 + r, cb * n2 + nu + m, (double)(wxy * v));
+      A.add(ca * n2 + nu + r, cb * n2 + m, (double)(wxy * v));
+    }
+  };
+  // reference integrals of the gradient products: Gg[rho][sig][r][m] = int_ref d_rho Dub_r d_sig Dub_m   (exact to degree 2p)
+  std::vector<real> Gg((size_t)4 * nu * nu, 0), val(nu), gx(nu), gy(nu);
+  {
+    const int mc = p + 1;
+    std::vector<real> xa, wa, xb, wb;
+    gaussJacobi(mc, 0, 0, xa, wa);
+    gaussJacobi(mc, 1, 0, xb, wb);
+    for (int i = 0; i < mc; i++)
+      for (int j = 0; j < mc; j++) {
+        const real eta = (xb[j] + 1) / 2, xi = (xa[i] + 1) / 2 * (1 - eta), w = wa[i] * wb[j] / 8;
+        U.eval(xi, eta, val.data(), gx.data(), gy.data());
+        for (int r = 0; r < nu; r++)
+          for (int m = 0; m < nu; m++) {
+            Gg[((size_t)0 * nu + r) * nu + m] += w * gx[r] * gx[m];
+            Gg[((size_t)1 * nu + r) * nu + m] += w * gx[r] * gy[m];
+            Gg[((size_t)2 * nu + r) * nu + m] += w * gy[r] * gx[m];
+            Gg[((size_t)3 * nu + r) * nu + m] += w * gy[r] * gy[m];
+          }
+      }
+  }
+  std::vector<real> ratio((size_t)nc);  // P_K / |K|
+  for (int c = 0; c < nc; c++) {
+    real per = 0;
+    for (int l = 0; l < 3; l++) per += (real)M.elen[(size_t)M.cedge[3 * (size_t)c + l]];
+    ratio[(size_t)c] = per / ((real)M.detJ[c] / 2);
+    const double* Ji = &M.Jinv[4 * (size_t)c];
+    for (int r = 0; r < nu; r++)
+      for (int m = 0; m < nu; m++) {
+        real acc = 0;
+        for (int rho = 0; rho < 2; rho++)
+          for (int sig = 0; sig < 2; sig++)
+            acc += ((real)Ji[rho * 2] * Ji[sig * 2] + (real)Ji[rho * 2 + 1] * Ji[sig * 2 + 1]) * Gg[((size_t)(rho * 2 + sig) * nu + r) * nu + m];
+        add2(c, c, r, m, -acc, 1, 0, 1);
+      }
+  }
+  std::vector<real> tq, wq;
+  gaussLegendre01(T.nqe, tq, wq);
+  std::vector<real> v[2], dn[2];
+  for (int sd = 0; sd < 2; sd++) { v[sd].resize(nu); dn[sd].resize(nu); }
+  std::vector<real> blk[2][2];
+  for (int e = 0; e < M.ne; e++) {
+    const bool wall = M.ecell[2 * (size_t)e + 1] < 0;
+    const int nside = wall ? 1 : 2;
+    const int cell[2] = {M.ecell[2 * (size_t)e], M.ecell[2 * (size_t)e + 1]};
+    const int loc[2] = {M.elocal[2 * (size_t)e], M.elocal[2 * (size_t)e + 1]};
+    const real sg = (real)M.csig[3 * (size_t)cell[0] + loc[0]], nx = sg * (real)M.enx[e], ny = sg * (real)M.eny[e];  // out of cell[0], the '+' cell
+    const real c0 = (real)(p + 1) * (p + 2) / 4;
+    const real eta_e = wall ? 2 * c0 * ratio[(size_t)cell[0]] : c0 * std::max(ratio[(size_t)cell[0]], ratio[(size_t)cell[1]]);
+    const real sign[2] = {1, -1};
+    for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) blk[a][b].assign((size_t)nu * nu, 0);
+    for (int q = 0; q < T.nqe; q++) {
+      for (int sd = 0; sd < nside; sd++) {
+        const int c = cell[sd];
+        real xi, eta;
+        GMesh::edge_ref(loc[sd], M.cflip[3 * (size_t)c + loc[sd]], tq[q], xi, eta);
+        U.eval(xi, eta, val.data(), gx.data(), gy.data());
+        const real is = 1 / std::sqrt((real)M.detJ[c]);
+        const double* Ji = &M.Jinv[4 * (size_t)c];
+        for (int m = 0; m < nu; m++) {
+          v[sd][m] = is * val[m];
+          dn[sd][m] = is * (nx * ((real)Ji[0] * gx[m] + (real)Ji[2] * gy[m]) + ny * ((real)Ji[1] * gx[m] + (real)Ji[3] * gy[m]));
+        }
+      }
+      const real w = wq[q] * (real)M.elen[e];
+      const real half = wall ? 1 : (real)1 / 2;  // a wall: the one-sided value, not the average
+      for (int a = 0; a < nside; a++)    // test function on side a
+        for (int b = 0; b < nside; b++)  // trial function on side b
+          for (int r = 0; r < nu; r++)
+            for (int m = 0; m < nu; m++)
+              blk[a][b][(size_t)r * nu + m] += w * (sign[a] * v[a][r] * dn[b][m] * half + sign[b] * v[b][m] * dn[a][r] * half -
+                                                    sign[a] * sign[b] * eta_e * v[a][r] * v[b][m]);
+    }
+    // a wall: n n^T (free slip), n n^T + t t^T = I (no slip)
+    const real wxx = wall && !no_slip ? nx * nx : 1, wxy = wall && !no_slip ? nx * ny : 0, wyy = wall && !no_slip ? ny * ny : 1;
+    for (int a = 0; a < nside; a++)
+      for (int b = 0; b < nside; b++)
+        for (int r = 0; r < nu; r++)
+          for (int m = 0; m < nu; m++) add2(cell[a], cell[b], r, m, blk[a][b][(size_t)r * nu + m], wxx, wxy, wyy);
+  }
+  Csr out = A.build();
+  lambda = 0.0;
+  for (int r = 0; r < out.nrows; r++) {
+    double sum = 0.0;
+    for (int q = out.rowptr[(size_t)r]; q < out.rowptr[(size_t)r + 1]; q++) sum += std::fabs(out.val[(size_t)q]);
+    lambda = std::max(lambda, sum);
+  }
+  return out;
+}
+
 // element block-Jacobi of the tentative-velocity operator,  (I + gamma sum_e alpha / len_e N_e^T N_e)^-1  per cell
 inline Csr assemble_block_jacobi(const GeneralTables& T, const GMesh& M, const std::vector<CellLocal>& loc, double gamma) {
   const int n2 = T.n2, ne = T.ne;

@@ -724,4 +724,128 @@ struct TracerDiffusionTables {
   }
 };
 
+// ------------------------------------------------------------------------------------------
+// Viscous term: the symmetric interior-penalty form of section 19 on one component of [DG_{k+1}]^2,
+// degree p = k + 1, plus Nitsche terms on the walls,
+//   V(w, u) = - sum_K int_K grad w : grad u + sum_{interior e} int_e ( [w].{dn u} + [u].{dn w} - eta_e [w].[u] )
+//             + sum_{wall e} int_e ( (w.n)(n.dn u) + (u.n)(n.dn w) - eta_b (w.n)(u.n) )      and the same with t for no-slip,
+//   eta_e = (p+1)(p+2)/4 max(P_K / |K|),  eta_b = 2 eta_e  (one cell: (p+1)(p+2)/2 P_K / |K|).
+// Every wall of the structured meshes is axis-aligned, so the components decouple and the blocks are scalar, nu x nu row-major
+// in the orthonormal modal basis (mass = identity: the blocks of M^-1 V), nu = the modes of one component:
+//   Vol[s], Own[s][e], Nbr[s][e]   as in TracerDiffusionTables, at degree p
+//   Wall[s][e]  int_e ( psi_r dn psi_m + psi_m dn psi_r - eta_b psi_r psi_m )  for the leg edges e = 0 (horizontal) and 2 (vertical);
+//               the hypotenuse e = 1 is never a wall.  wall_normal_component(e): the component the wall's normal points along.
+// A cell's row: Vol u_K + sum_{e with a neighbour} (Own[e] u_K + Nbr[e] u_K') + sum_{wall e} Wall[e] u_K, the last one on the
+// normal component only (free slip) or on both (no slip).  Volume rule exact to degree 2p (k + 2 collapsed Gauss-Jacobi points
+// a side), edge rule as in section 19 (exact to 3k + 3 >= 2p).  lambda: the largest absolute row sum over both shapes and every
+// assignment of neighbour / wall term / nothing to the edges, so lambda >= rho(M^-1 V) in either wall mode.
+// ------------------------------------------------------------------------------------------
+struct ViscosityTables {
+  int k, nu;
+  double h, eta, eta_b, lambda;
+  dvec Vol[2], Own[2][3], Nbr[2][3], Wall[2][3];  // Wall[s][1] stays empty
+  static int wall_normal_component(int e) { return e == 0 ? 1 : 0; }
+
+  ViscosityTables(int k_, double h_) : k(k_), nu(n_scalar(k_ + 1)), h(h_) {
+    const int p = k + 1;
+    const real rh = h, s2 = std::sqrt((real)2);
+    const real eta_ = (real)(p + 1) * (p + 2) / 4 * 2 * (2 + s2) / rh, etab_ = 2 * eta_;
+    eta = (double)eta_; eta_b = (double)etab_;
+    const real nfix[3][2] = {{0, 1}, {1 / s2, 1 / s2}, {1, 0}};
+    const real sg[2][3] = {{-1, 1, -1}, {1, -1, 1}}, elen_[3] = {rh, s2 * rh, rh};
+    Dubiner U(p);
+    std::vector<real> val(nu), gx(nu), gy(nu), vn(nu), nx_(nu), ny_(nu), dno(nu), dnn(nu);
+    auto edge_ref = [](int s, int e, real t, real& xi, real& et) {  // as in Tables: the point with GLOBAL edge parameter t
+      if (s == 0) {
+        if (e == 0) { xi = t; et = 0; }
+        else if (e == 1) { xi = 1 - t; et = t; }
+        else { xi = 0; et = t; }
+      } else {
+        if (e == 0) { xi = 1 - t; et = 0; }
+        else if (e == 1) { xi = t; et = 1 - t; }
+        else { xi = 0; et = 1 - t; }
+      }
+    };
+    {
+      const int mc = p + 1;
+      std::vector<real> xa, wa, xb, wb, V((size_t)nu * nu, 0);
+      gaussJacobi(mc, 0, 0, xa, wa);
+      gaussJacobi(mc, 1, 0, xb, wb);
+      for (int i = 0; i < mc; i++)
+        for (int j = 0; j < mc; j++) {
+          const real et = (xb[j] + 1) / 2, xi = (xa[i] + 1) / 2 * (1 - et), w = wa[i] * wb[j] / 8;
+          U.eval(xi, et, val.data(), gx.data(), gy.data());
+          for (int r = 0; r < nu; r++)
+            for (int m = 0; m < nu; m++) V[(size_t)r * nu + m] -= w * (gx[r] * gx[m] + gy[r] * gy[m]) / (rh * rh);
+        }
+      for (int s = 0; s < 2; s++) Vol[s].assign(V.begin(), V.end());
+    }
+    const int nqe = (3 * k + 4 + 1) / 2;
+    std::vector<real> tq, wq;
+    gaussLegendre01(nqe, tq, wq);
+    for (int s = 0; s < 2; s++) {
+      const real sgn = s == 0 ? 1 : -1;
+      for (int e = 0; e < 3; e++) {
+        const real nx = sg[s][e] * nfix[e][0], ny = sg[s][e] * nfix[e][1];  // this cell's outward normal
+        std::vector<real> O((size_t)nu * nu, 0), N((size_t)nu * nu, 0), W((size_t)nu * nu, 0);
+        for (int q = 0; q < nqe; q++) {
+          real xi, et;
+          edge_ref(s, e, tq[q], xi, et);
+          U.eval(xi, et, val.data(), gx.data(), gy.data());
+          for (int m = 0; m < nu; m++) { val[m] /= rh; dno[m] = sgn * (nx * gx[m] + ny * gy[m]) / (rh * rh); }
+          edge_ref(1 - s, e, tq[q], xi, et);
+          U.eval(xi, et, vn.data(), nx_.data(), ny_.data());
+          for (int m = 0; m < nu; m++) { vn[m] /= rh; dnn[m] = -sgn * (nx * nx_[m] + ny * ny_[m]) / (rh * rh); }
+          const real w = wq[q] * elen_[e];
+          for (int r = 0; r < nu; r++)
+            for (int m = 0; m < nu; m++) {
+              O[(size_t)r * nu + m] += w * (val[r] * dno[m] / 2 + val[m] * dno[r] / 2 - eta_ * val[r] * val[m]);
+              N[(size_t)r * nu + m] += w * (val[r] * dnn[m] / 2 - vn[m] * dno[r] / 2 + eta_ * val[r] * vn[m]);
+              W[(size_t)r * nu + m] += w * (val[r] * dno[m] + val[m] * dno[r] - etab_ * val[r] * val[m]);
+            }
+        }
+        Own[s][e].assign(O.begin(), O.end());
+        Nbr[s][e].assign(N.begin(), N.end());
+        if (e != 1) Wall[s][e].assign(W.begin(), W.end());
+      }
+    }
+    lambda = 0.0;
+    for (int s = 0; s < 2; s++)
+      for (int st = 0; st < 27; st++) {  // per edge: 0 nothing, 1 a neighbour, 2 the wall term
+        const int se[3] = {st % 3, st / 3 % 3, st / 9};
+        if (se[1] == 2) continue;
+        for (int r = 0; r < nu; r++) {
+          double sum = 0.0;
+          for (int m = 0; m < nu; m++) {
+            double d = Vol[s][(size_t)r * nu + m];
+            for (int e = 0; e < 3; e++) {
+              if (se[e] == 1) { d += Own[s][e][(size_t)r * nu + m]; sum += std::fabs(Nbr[s][e][(size_t)r * nu + m]); }
+              if (se[e] == 2) d += Wall[s][e][(size_t)r * nu + m];
+            }
+            sum += std::fabs(d);
+          }
+          lambda = std::max(lambda, sum);
+        }
+      }
+  }
+  // device layout: per shape s the nine blocks Vol, Own[0..2], Nbr[0..2], Wall[0], Wall[2], each nu x nu and TRANSPOSED
+  // (entry (r, m) at m * nu + r): k_viscosity streams the operand mode by mode and reads one column per mode
+  static constexpr int NBLK = 9;
+  dvec packed() const {
+    dvec out;
+    auto put = [&](const dvec& B) {
+      for (int m = 0; m < nu; m++)
+        for (int r = 0; r < nu; r++) out.push_back(B[(size_t)r * nu + m]);
+    };
+    for (int s = 0; s < 2; s++) {
+      put(Vol[s]);
+      for (int e = 0; e < 3; e++) put(Own[s][e]);
+      for (int e = 0; e < 3; e++) put(Nbr[s][e]);
+      put(Wall[s][0]);
+      put(Wall[s][2]);
+    }
+    return out;
+  }
+};
+
 }  // namespace hdg

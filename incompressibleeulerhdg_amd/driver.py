@@ -85,6 +85,11 @@ def build_parser():
     parser.add_argument("--tracer_diffusivity", metavar="K", type=float, nargs="+", default=None,
                         help="molecular diffusivity of the tracers (with --tracer_advection): one value for all of them or "
                              "exactly --tracers values; explicit in time, see the printed diffusion number")
+    parser.add_argument("--viscosity", metavar="NU", type=float, default=None,
+                        help="kinematic viscosity: the momentum equation gains NU Laplace u, explicit in time (see the printed "
+                             "viscous diffusion number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
+    parser.add_argument("--wall", choices=["free_slip", "no_slip"], default=None,
+                        help="walls of the viscous term (with --viscosity; default free_slip)")
     parser.add_argument("--buoyancy", metavar="B", type=float, nargs="+", default=None,
                         help="Boussinesq buoyancy (with --tracer_advection): the momentum equation gains sum_t B_t q_t g; one "
                              "value for all tracers or exactly --tracers values, 0 keeps a tracer passive; explicit in time")
@@ -213,6 +218,14 @@ def nodal_mean(coordinates, degree, values):
     w = np.linalg.solve(V, np.array([2.0 * factorial(a) * factorial(b) / factorial(a + b + 2) for a, b in powers]))
     area = np.abs(area2(X[:, corners[0]], X[:, corners[1]], X[:, corners[2]]))
     return float(np.sum(area * (np.asarray(values, dtype=float).reshape(-1, n_p) @ w)) / np.sum(area))
+
+
+def check_viscosity(args):
+    """--viscosity / --wall, before any engine exists"""
+    if args.wall is not None and args.viscosity is None:
+        raise RuntimeError("--wall needs --viscosity")
+    if args.viscosity is not None and not (np.isfinite(args.viscosity) and args.viscosity >= 0):
+        raise RuntimeError(f"--viscosity {args.viscosity} is not a finite number >= 0")
 
 
 def check_checkpoint(args):
@@ -432,6 +445,7 @@ def main(argv=None):
     check_multi_gpu(args)
     check_particles(args)
     check_tracers(args)
+    check_viscosity(args)
     check_checkpoint(args)
     check_start_from(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -454,6 +468,9 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.buoyancy is not None:
         several["buoyancy"] = args.buoyancy[0] if len(args.buoyancy) == 1 else args.buoyancy
         several["gravity"] = tuple(args.gravity) if args.gravity is not None else (0.0, -1.0)
+    if args.viscosity is not None:
+        several["viscosity"] = args.viscosity
+        several["wall"] = args.wall or "free_slip"
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
@@ -525,6 +542,10 @@ def _run(args, ranks):
     if args.tracer_diffusivity is not None:
         print(f"tracer diffusivity = {' '.join(repr(x) for x in args.tracer_diffusivity)}")
         print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g} (limit {timestepper.diffusion_limit:.6g})")
+    if args.viscosity is not None:
+        print(f"viscosity = {args.viscosity!r}")
+        print(f"wall = {args.wall or 'free_slip'}")
+        print(f"viscous diffusion number = {timestepper._engine.viscosity_number()[1]:.6g} (limit {timestepper.viscosity_limit:.6g})")
     print(f"timestepping method = {timestepper.label}")
     print()
 
@@ -561,7 +582,7 @@ def _run(args, ranks):
     elif args.problem == "kelvinhelmholtz":
         model_problem = KelvinHelmholtz(timestepper._V_Q, timestepper._V_p)  # driver.py:336-337
     else:
-        model_problem = TaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa)
+        model_problem = TaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa, viscosity=args.viscosity or 0.0)
     Q_0, p_0 = model_problem.initial_condition()
     # driver.py:340-344
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None

@@ -27,12 +27,17 @@ class SeparableForcing:
 
 
 class TaylorGreen:
-    """Taylor-Green vortex with manufactured time dependence (model_problems.py:38-105)."""
+    """Taylor-Green vortex with manufactured time dependence (model_problems.py:38-105).
 
-    def __init__(self, V_Q, V_p, forcing="exponential", kappa=0.5):
+    viscosity: nu of the viscous term.  Laplace Q_s = -2 pi^2 Q_s and Q_s is free-slip on the unit square,
+    so a(t) Q_s stays an exact Navier-Stokes solution with the separable forcing a'(t) + 2 pi^2 nu a(t); nu = 0 is exactly the
+    Euler problem, the kappa == 0 rule included."""
+
+    def __init__(self, V_Q, V_p, forcing="exponential", kappa=0.5, viscosity=0.0):
         assert forcing in ("exponential", "constant"), "Forcing must be 'constant' or 'exponential'"
         self.V_Q, self.V_p = V_Q, V_p
         self.kappa = kappa
+        self.viscosity = viscosity
         self.forcing = forcing
         S = lambda z: np.sin((z - 0.5) * np.pi)
         C = lambda z: np.cos((z - 0.5) * np.pi)
@@ -48,6 +53,11 @@ class TaylorGreen:
     def f_rhs(self):
         """Forcing as a function of time; kappa == 0 is treated as zero forcing."""
         k = self.kappa
+        if self.viscosity != 0:
+            c = 2.0 * np.pi ** 2 * self.viscosity
+            if self.forcing == "exponential":
+                return SeparableForcing(self._Qs, lambda t: (-k + c) * np.exp(-k * t))
+            return SeparableForcing(self._Qs, lambda t: -k + c * (1.0 - k * t))
         if k == 0:
             return SeparableForcing(self._Qs, lambda t: 0.0)
         if self.forcing == "exponential":

@@ -73,6 +73,12 @@ class IncompressibleEuler(ABC):
         self._gravity = engine_options.pop("gravity", None)
         if self._gravity is not None and self._buoyancy is None:
             raise ValueError("gravity= needs buoyancy=")
+        # viscosity=, wall=: nu and the wall mode ('free_slip', 'no_slip') of the explicit viscous term + nu Laplace u (DESIGN.md
+        # section 21); None: no call at all
+        self._viscosity = engine_options.pop("viscosity", None)
+        self._wall = engine_options.pop("wall", None)
+        if self._wall is not None and self._viscosity is None:
+            raise ValueError("wall= needs viscosity=")
         self._engine_options = engine_options
         self._engine = None
         # common.py:72-73
@@ -105,6 +111,10 @@ class IncompressibleEuler(ABC):
             self._engine.set_tracer_diffusivity(self._tracer_diffusivity)
             self.diffusion_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
             warn_if_diffusion_unstable(self._engine.tracer_diffusion_number()[1], self.diffusion_limit)
+        if self._viscosity is not None:  # independent of the tracer check above
+            self._engine.set_viscosity(self._viscosity, "free_slip" if self._wall is None else self._wall)
+            self.viscosity_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
+            warn_if_diffusion_unstable(self._engine.viscosity_number()[1], self.viscosity_limit, what="viscosity")
         return self._engine
 
     def _as_nodal_velocity(self, Q):
