@@ -20,6 +20,7 @@ TRANSFER_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tra
 TRACER_DIFFUSION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_diffusion.h"))
 BUOYANCY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_buoyancy.h"))
 VISCOSITY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_viscosity.h"))
+CORIOLIS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_coriolis.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -92,7 +93,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -218,6 +219,13 @@ VISCOSITY_SIGNATURES = {
 }
 WALL_MODES = {"free_slip": 0, "no_slip": 1}
 
+# Coriolis term: the symbols include/hdg_coriolis.h declares, in a table of their own like the five above
+CORIOLIS_SIGNATURES = {
+    "hdg_set_coriolis": [_h, C.c_double, C.c_double],
+    "hdg_get_coriolis": [_h, _dp, _dp, _dp],
+    "hdg_apply_coriolis": [_h, C.c_double, C.c_double, _dp, _dp],
+}
+
 
 def wall_code(wall):
     """'free_slip' / 'no_slip' -> the integer of include/hdg_viscosity.h"""
@@ -238,7 +246,8 @@ def load_library():
         )
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
-            list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()):
+            list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
+            list(CORIOLIS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -591,6 +600,34 @@ class Engine:
         Q = _arr(Q, self.shape_Q)
         out = np.empty(self.shape_Q)
         self._ck(self.lib.hdg_apply_viscosity(self.h, wall_code(wall), _ptr(Q), _ptr(out)))
+        return out
+
+    # --- Coriolis term (include/hdg_coriolis.h)
+    def set_coriolis(self, f0, beta=0.0):
+        """- f_c k x u in the momentum equation, f_c = f0 + beta y (y the mesh's own ordinate), explicit in time.
+        f0 = beta = 0: off.  beta != 0 is refused on the doubly periodic square."""
+        self._ck(self.lib.hdg_set_coriolis(self.h, float(f0), float(beta)))
+
+    def _get_coriolis(self):
+        f0, beta, out = C.c_double(), C.c_double(), np.zeros(2)
+        self._ck(self.lib.hdg_get_coriolis(self.h, C.byref(f0), C.byref(beta), _ptr(out)))
+        return f0.value, beta.value, out
+
+    def coriolis(self):
+        """(f0, beta) as they are set; both 0 while the term is off."""
+        return self._get_coriolis()[:2]
+
+    def coriolis_number(self):
+        """(F, F dt): F = max over the mesh vertices of |f0 + beta y|, an upper bound of the spectral radius of M^-1 C."""
+        out = self._get_coriolis()[2]
+        return float(out[0]), float(out[1])
+
+    def apply_coriolis(self, Q, f0, beta=0.0):
+        """M^-1 C Q of a nodal velocity-space field (the layout of get_field's Q) for the given f0 and beta (test hook;
+        it sets nothing)."""
+        Q = _arr(Q, self.shape_Q)
+        out = np.empty(self.shape_Q)
+        self._ck(self.lib.hdg_apply_coriolis(self.h, float(f0), float(beta), _ptr(Q), _ptr(out)))
         return out
 
     def cg_size(self):

@@ -33,6 +33,7 @@
 #include "../../include/hdg_tracer_diffusion.h"
 #include "../../include/hdg_buoyancy.h"
 #include "../../include/hdg_viscosity.h"
+#include "../../include/hdg_coriolis.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -53,6 +54,7 @@
 #include "hdg_general_kernels.hpp"
 #include "hdg_buoyancy.hpp"
 #include "hdg_viscosity.hpp"
+#include "hdg_coriolis.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
@@ -1580,7 +1582,7 @@ struct Engine {
     for (int j = 0; j < s; j++) terms.push_back({bvec(j), cb[j] * bscale[j]});
     if (buoyancy_on())  // b_rhs[j] + B(q^(j)): the buoyancy vectors stand beside the user's forcing
       for (int j = 0; j < s; j++) terms.push_back({buoy[(size_t)j], cb[j]});
-    if (viscosity_on())  // ... + nu M^-1 V Q^(j): vectors of their own again; filled by viscosity_slots
+    if (vel_linear_on())  // ... + nu M^-1 V Q^(j) + M^-1 C Q^(j): vectors of their own again (DESIGN.md sections 21, 22); filled by viscosity_slots
       for (int j = 0; j < s; j++) terms.push_back({visc[(size_t)j], cb[j]});
     return terms;
   }
@@ -1588,7 +1590,7 @@ struct Engine {
   Terms start_terms(double dtt) const {
     Terms terms{{curQ, 1.0}, {bvec(0), dtt * bscale[0]}};
     if (buoyancy_on()) terms.push_back({buoy[0], dtt});
-    if (viscosity_on()) terms.push_back({visc[0], dtt});
+    if (vel_linear_on()) terms.push_back({visc[0], dtt});
     return terms;
   }
   void residual_vector(const std::vector<double>& cq, const std::vector<double>& cb, double* out) {
@@ -2980,11 +2982,11 @@ struct Engine {
       backsub(wQ3, nullptr, curL, curQ, curP);
       it_sum[2] += its; it_cnt[2]++;
     } else if (key == HDG_KEY_PRESSURE_RECONSTRUCTION) {
-      if (viscosity_on()) viscosity_slot(s, curQ);  // slot s: Q_{n+1}, complete since the final-stage back-substitution
-      if (buoyancy_on() || viscosity_on()) {  // the kernels take one forcing vector and read the neighbour's too: b_new + B(q^{n+1}) + nu M^-1 V Q_{n+1} summed first
+      if (vel_linear_on()) viscosity_slot(s, curQ);  // slot s: Q_{n+1}, complete since the final-stage back-substitution
+      if (buoyancy_on() || vel_linear_on()) {  // the kernels take one forcing vector and read the neighbour's too: b_new + B(q^{n+1}) + nu M^-1 V Q_{n+1} summed first
         Terms bnew{{bvec(s), bscale[s]}};
         if (buoyancy_on()) bnew.push_back({buoy[(size_t)s], 1.0});
-        if (viscosity_on()) bnew.push_back({visc[(size_t)s], 1.0});
+        if (vel_linear_on()) bnew.push_back({visc[(size_t)s], 1.0});
         lincomb(NQ, bnew, wQ3);
         precon_rhs(curQ, wQ3, 1.0, wP1, wL2);
       } else {
@@ -3081,7 +3083,7 @@ struct Engine {
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
     auto tracer_end = [&]() { if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur); };
-    if (viscosity_on()) viscosity_apply(curQ, visc_nu, visc_wall, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
+    if (vel_linear_on()) vel_linear_apply(curQ, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
     ensure_dinv(0, dtt);
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }             // hdg_implicit.py:98
     if (!cfg.use_projection) {
@@ -3214,7 +3216,7 @@ struct Engine {
       tracer_tendency(q_cur, uproj, q_t);
       if (buoyancy_on()) buoyancy(q_cur, buoy[0]);  // slot 0: the tracer at the start of the step, next to f(t_k)
     }
-    if (viscosity_on()) viscosity_apply(curQ, visc_nu, visc_wall, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
+    if (vel_linear_on()) vel_linear_apply(curQ, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }              // dg_implicit.py:122
     lincomb(NQ, start_terms(dtt), dg_b.u);  // (Q, w) + dt (f, w)   dg_implicit.py:73
     zero(dg_b.p, NPv);
@@ -3737,17 +3739,20 @@ struct Engine {
   static void visc_check_wall(const char* who, int wall) {
     if (wall != 0 && wall != 1) throw std::string(who) + ": wall = " + std::to_string(wall) + " (0: free slip, 1: no slip)";
   }
+  void visc_alloc() {
+    if (!visc.empty()) return;
+    for (int j = 0; j <= s; j++) {
+      visc.push_back(dalloc(NQ));
+      HIPCHECK(hipMemsetAsync(visc.back(), 0, sizeof(double) * NQ, stream));
+    }
+  }
   void set_viscosity(double nu, int wall) {
     if (step_open) throw std::string("hdg_set_viscosity: a step is open (between hdg_begin_step and the end of the step)");
     if (!(nu >= 0.0) || !std::isfinite(nu)) throw std::string("hdg_set_viscosity: nu = " + std::to_string(nu) + " is not a finite value >= 0");
     visc_check_wall("hdg_set_viscosity", wall);
     if (nu != 0.0) {
       visc_setup(wall);
-      if (visc.empty())
-        for (int j = 0; j <= s; j++) {
-          visc.push_back(dalloc(NQ));
-          HIPCHECK(hipMemsetAsync(visc.back(), 0, sizeof(double) * NQ, stream));
-        }
+      visc_alloc();
     }
     visc_nu = nu; visc_wall = wall;  // off: the vectors stay allocated, nothing reads them
     visc_valid = 0;
@@ -3762,12 +3767,12 @@ struct Engine {
   }
   void viscosity_slot(int j, const double* Q) {
     if (visc_step && (visc_valid >> j & 1u)) return;
-    viscosity_apply(Q, visc_nu, visc_wall, visc[(size_t)j]);
+    vel_linear_apply(Q, visc[(size_t)j]);
     visc_valid |= 1u << j;
   }
   // the slots a residual with the forcing coefficients cb reads
   void viscosity_slots(const std::vector<double>& cb) {
-    if (!viscosity_on()) return;
+    if (!vel_linear_on()) return;
     for (int j = 0; j < s; j++)
       if (cb[(size_t)j] != 0.0) viscosity_slot(j, stQ[j]);
   }
@@ -3777,6 +3782,74 @@ struct Engine {
     visc_setup(wall);
     out2[0] = visc_lambda[wall];
     out2[1] = nu * cfg.dt * visc_lambda[wall];
+  }
+  // ---- Coriolis term: - f_c k x u, f_c = f0 + beta y.  M^-1 C is block diagonal per cell, so the term
+  // rides in the vectors of the viscous term: visc[j] is the velocity-linear part of slot j, nu M^-1 V Q^(j) + M^-1 C Q^(j).
+  // With both terms on k_viscosity writes the slot and k_coriolis adds to it in place; with rotation alone k_coriolis writes
+  // it.  No ghost rows, no exchange; general meshes run matrix-free on one rank.  f0 and beta are configuration like nu.
+  double cor_f0 = 0.0, cor_beta = 0.0;
+  const double* d_cortab = nullptr;  // structured: Y_0, Y_1 transposed; general: L_1, L_2
+  const double* d_coryv = nullptr;   // general: the ordinates of a cell's three vertices, nc x 3
+  bool coriolis_on() const { return cor_f0 != 0.0 || cor_beta != 0.0; }
+  bool vel_linear_on() const { return viscosity_on() || coriolis_on(); }
+  void coriolis_check(const char* who, double f0, double beta) const {
+    if (step_open) throw std::string(who) + ": a step is open (between hdg_begin_step and the end of the step)";
+    if (!std::isfinite(f0) || !std::isfinite(beta))
+      throw std::string(who) + ": f0 = " + std::to_string(f0) + ", beta = " + std::to_string(beta) + " are not both finite";
+    if (beta != 0.0 && cfg.periodic)
+      throw std::string(who) + ": beta != 0 on the doubly periodic square (f0 + beta y jumps at the wrap)";
+  }
+  void coriolis_setup() {
+    if (d_cortab) return;
+    const CoriolisTables T(K);
+    if (general) {
+      if (comm->size > 1) throw std::string("rotation on a general mesh: single rank only");
+      dvec yv((size_t)3 * gm->nc);
+      for (size_t n = 0; n < yv.size(); n++) yv[n] = gm->X[2 * (size_t)gm->C[n] + 1];
+      d_coryv = upload(yv);
+      d_cortab = upload(T.general());
+    } else
+      d_cortab = upload(T.packed());
+  }
+  void set_coriolis(double f0, double beta) {
+    coriolis_check("hdg_set_coriolis", f0, beta);
+    if (f0 != 0.0 || beta != 0.0) {
+      coriolis_setup();
+      visc_alloc();
+    }
+    cor_f0 = f0; cor_beta = beta;  // off: the vectors stay allocated, nothing reads them
+    visc_valid = 0;
+  }
+  // out = M^-1 C Q, or out += M^-1 C Q (acc), on the owned rows
+  void coriolis_apply(const double* Q, double f0, double beta, bool acc, double* out) {
+    tally(LC_OTHER, (acc ? 3.0 : 2.0) * bQ());
+    by_degree([&](auto k) {
+      if (general) {
+        const dim3 gr((gm->nc + 63) / 64);
+        if (acc) k_g_coriolis<k(), true><<<gr, 64, 0, stream>>>(gm->nc, d_cortab, d_coryv, f0, beta, Q, out);
+        else k_g_coriolis<k(), false><<<gr, 64, 0, stream>>>(gm->nc, d_cortab, d_coryv, f0, beta, Q, out);
+      } else {
+        if (acc) k_coriolis<k(), true><<<cell_grid(), bs(), 0, stream>>>(g, d_cortab, f0, beta, g.h, Q, out);
+        else k_coriolis<k(), false><<<cell_grid(), bs(), 0, stream>>>(g, d_cortab, f0, beta, g.h, Q, out);
+      }
+    });
+    fl.set(out, 0);
+  }
+  // the velocity-linear part of a slot: out = nu M^-1 V Q + M^-1 C Q, whichever of the two is on
+  void vel_linear_apply(const double* Q, double* out) {
+    if (viscosity_on()) viscosity_apply(Q, visc_nu, visc_wall, out);
+    if (coriolis_on()) coriolis_apply(Q, cor_f0, cor_beta, viscosity_on(), out);
+  }
+  // F = max over the mesh vertices of |f0 + beta y|, an upper bound of rho(M^-1 C); f_c is linear, so on the structured meshes
+  // the two ends of the ordinate decide
+  double coriolis_bound(double f0, double beta) const {
+    if (general) {
+      double F = 0.0;
+      for (int v = 0; v < gm->nv; v++) F = std::max(F, std::fabs(f0 + beta * gm->X[2 * (size_t)v + 1]));
+      return F;
+    }
+    if (cfg.periodic) return std::fabs(f0);
+    return std::max(std::fabs(f0), std::fabs(f0 + beta * g.h * g.nyg));
   }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
@@ -4330,6 +4403,7 @@ struct Engine {
     for (size_t t = 0; t < by_beta.size(); t++) f.add("buoyancy_beta[" + std::to_string(t) + "]", by_beta[t]);  // only with some beta != 0
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
+    if (coriolis_on()) { f.add("coriolis_f0", cor_f0); f.add("coriolis_beta", cor_beta); }  // only with one of them != 0
     if (general) {
       f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
       f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
@@ -5441,6 +5515,34 @@ int hdg_apply_viscosity(hdg_handle* h, int wall, const double* Q, double* out) {
   E.put_Q(Q, E.wQ1);
   E.zero(E.wQ2, E.NQ);
   E.viscosity_apply(E.wQ1, 1.0, wall, E.wQ2);
+  E.get_Q(E.wQ2, out);
+  HDG_API_END(h)
+}
+
+// ---- Coriolis term (include/hdg_coriolis.h)
+int hdg_set_coriolis(hdg_handle* h, double f0, double beta) {
+  HDG_API_BEGIN(h)
+  E.set_coriolis(f0, beta);
+  HDG_API_END(h)
+}
+int hdg_get_coriolis(hdg_handle* h, double* f0, double* beta, double out2[2]) {
+  HDG_API_BEGIN(h)
+  if (!f0 || !beta) throw std::string("null argument");
+  *f0 = E.cor_f0; *beta = E.cor_beta;
+  if (out2) {
+    out2[0] = E.coriolis_bound(E.cor_f0, E.cor_beta);
+    out2[1] = out2[0] * E.cfg.dt;
+  }
+  HDG_API_END(h)
+}
+int hdg_apply_coriolis(hdg_handle* h, double f0, double beta, const double* Q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!Q || !out) throw std::string("null argument");
+  E.coriolis_check("hdg_apply_coriolis", f0, beta);
+  E.coriolis_setup();
+  E.put_Q(Q, E.wQ1);
+  E.zero(E.wQ2, E.NQ);
+  E.coriolis_apply(E.wQ1, f0, beta, false, E.wQ2);
   E.get_Q(E.wQ2, out);
   HDG_API_END(h)
 }

@@ -848,4 +848,59 @@ struct ViscosityTables {
   }
 };
 
+// ------------------------------------------------------------------------------------------
+// Coriolis term: C(w, u) = sum_K int_K f_c (w_x u_y - w_y u_x), f_c = f0 + beta y, on [DG_{k+1}]^2.
+// f_c is linear, so on a cell with vertices v_0, v_1, v_2 (barycentric coordinates lambda_1 = xi, lambda_2 = eta)
+//   f_c = f_c(v_0) + (f_c(v_1) - f_c(v_0)) lambda_1 + (f_c(v_2) - f_c(v_0)) lambda_2
+// and in an orthonormal modal basis (mass = identity) the cell's block of M^-1 C is
+//   (f_c(v_0) I + (f_1 - f_0) L_1 + (f_2 - f_0) L_2) (x) J,   L_v[r][m] = int_ref lambda_v phi_r phi_m,   J = [[0, 1], [-1, 0]],
+// phi the orthonormal Dubiner modes of the reference triangle: L_v carries no geometry and serves every affine cell.  The
+// integrand has degree 2k + 3: k + 2 collapsed Gauss-Jacobi points a side are exact.  L_v is symmetric with its spectrum in
+// [0, 1] (0 <= lambda_v <= 1), so the spectral radius of the block is at most the largest |f_c| over the cell's vertices.
+// Structured meshes: y = y_j + h eta on shape L and y = y_{j+1} - h eta on shape U, so with the cell's reference ordinate
+// y_{j+s} the block is (f_c(y_{j+s}) I + beta h Y_s) (x) J with Y_0 = L_2 and Y_1 = -L_2.
+// ------------------------------------------------------------------------------------------
+struct CoriolisTables {
+  int k, nu;
+  dvec L[2];  // L_1, L_2, nu x nu row-major
+  dvec Y[2];  // per element shape
+
+  explicit CoriolisTables(int k_) : k(k_), nu(n_scalar(k_ + 1)) {
+    const int mc = k + 2;
+    Dubiner U(k + 1);
+    std::vector<real> xa, wa, xb, wb, val(nu), A[2];
+    gaussJacobi(mc, 0, 0, xa, wa);
+    gaussJacobi(mc, 1, 0, xb, wb);
+    for (auto& a : A) a.assign((size_t)nu * nu, 0);
+    for (int i = 0; i < mc; i++)
+      for (int j = 0; j < mc; j++) {
+        const real et = (xb[j] + 1) / 2, xi = (xa[i] + 1) / 2 * (1 - et), w = wa[i] * wb[j] / 8;
+        U.eval(xi, et, val.data(), nullptr, nullptr);
+        for (int r = 0; r < nu; r++)
+          for (int m = 0; m < nu; m++) {
+            A[0][(size_t)r * nu + m] += w * xi * val[r] * val[m];
+            A[1][(size_t)r * nu + m] += w * et * val[r] * val[m];
+          }
+      }
+    for (int v = 0; v < 2; v++) L[v].assign(A[v].begin(), A[v].end());
+    Y[0] = L[1];
+    Y[1].resize(L[1].size());
+    for (size_t n = 0; n < L[1].size(); n++) Y[1][n] = -L[1][n];
+  }
+  // device layout of the structured kernel: Y_0, Y_1, each TRANSPOSED (entry (r, m) at m * nu + r), as ViscosityTables::packed
+  dvec packed() const {
+    dvec out;
+    for (int s = 0; s < 2; s++)
+      for (int m = 0; m < nu; m++)
+        for (int r = 0; r < nu; r++) out.push_back(Y[s][(size_t)r * nu + m]);
+    return out;
+  }
+  // device layout of the general-mesh kernel: L_1, L_2 row-major
+  dvec general() const {
+    dvec out(L[0]);
+    out.insert(out.end(), L[1].begin(), L[1].end());
+    return out;
+  }
+};
+
 }  // namespace hdg

@@ -40,7 +40,7 @@ from ._lib import DIAGNOSTICS, HDG_MAX_TRACERS, POINT_COLUMNS
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
-from .model_problems import DoubleLayerShearFlow, KelvinHelmholtz, TaylorGreen
+from .model_problems import DoubleLayerShearFlow, KelvinHelmholtz, RotatingTaylorGreen, TaylorGreen
 from .output import VTKFile
 from .timesteppers import (
     IncompressibleEulerHDGIMEXARS2_232,
@@ -90,6 +90,9 @@ def build_parser():
                              "viscous diffusion number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
     parser.add_argument("--wall", choices=["free_slip", "no_slip"], default=None,
                         help="walls of the viscous term (with --viscosity; default free_slip)")
+    parser.add_argument("--coriolis", metavar="F", type=float, nargs="+", default=None,
+                        help="rotation F0 [BETA]: the momentum equation gains - (F0 + BETA y) k x u, explicit in time (see the "
+                             "printed rotation number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
     parser.add_argument("--buoyancy", metavar="B", type=float, nargs="+", default=None,
                         help="Boussinesq buoyancy (with --tracer_advection): the momentum equation gains sum_t B_t q_t g; one "
                              "value for all tracers or exactly --tracers values, 0 keeps a tracer passive; explicit in time")
@@ -226,6 +229,28 @@ def check_viscosity(args):
         raise RuntimeError("--wall needs --viscosity")
     if args.viscosity is not None and not (np.isfinite(args.viscosity) and args.viscosity >= 0):
         raise RuntimeError(f"--viscosity {args.viscosity} is not a finite number >= 0")
+
+
+def coriolis_pair(args):
+    """(f0, beta) of --coriolis F0 [BETA]"""
+    return args.coriolis[0], args.coriolis[1] if len(args.coriolis) == 2 else 0.0
+
+
+def check_coriolis(args):
+    """--coriolis F0 [BETA], before any engine exists"""
+    if args.coriolis is None:
+        return
+    if len(args.coriolis) > 2:
+        raise RuntimeError(f"--coriolis takes F0 or F0 BETA ({len(args.coriolis)} values given)")
+    for x in args.coriolis:
+        if not np.isfinite(x):
+            raise RuntimeError(f"--coriolis: {x} is not a finite number")
+    if len(args.coriolis) == 2 and args.coriolis[1] != 0 and args.problem == "shear":
+        raise RuntimeError("--coriolis: BETA != 0 is not available on the doubly periodic square of --problem shear "
+                           "(f0 + beta y jumps at the wrap)")
+    if args.problem == "taylorgreen" and args.forcing == "constant":
+        raise RuntimeError("--coriolis with --problem taylorgreen needs --forcing exponential (with constant forcing the "
+                           "manufactured forcing is not separable)")
 
 
 def check_checkpoint(args):
@@ -446,6 +471,7 @@ def main(argv=None):
     check_particles(args)
     check_tracers(args)
     check_viscosity(args)
+    check_coriolis(args)
     check_checkpoint(args)
     check_start_from(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -471,6 +497,8 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.viscosity is not None:
         several["viscosity"] = args.viscosity
         several["wall"] = args.wall or "free_slip"
+    if args.coriolis is not None:
+        several["coriolis"] = coriolis_pair(args)
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
@@ -546,6 +574,11 @@ def _run(args, ranks):
         print(f"viscosity = {args.viscosity!r}")
         print(f"wall = {args.wall or 'free_slip'}")
         print(f"viscous diffusion number = {timestepper._engine.viscosity_number()[1]:.6g} (limit {timestepper.viscosity_limit:.6g})")
+    if args.coriolis is not None:
+        number = timestepper._engine.coriolis_number()[1]
+        print(f"coriolis = {' '.join(repr(x) for x in args.coriolis)}")
+        print(f"rotation number F dt = {number:.6g} (growth per inertial period "
+              f"{(timestepper.rotation_growth * 2 * np.pi / number if number > 0 else 0.0):.6g})")
     print(f"timestepping method = {timestepper.label}")
     print()
 
@@ -582,7 +615,11 @@ def _run(args, ranks):
     elif args.problem == "kelvinhelmholtz":
         model_problem = KelvinHelmholtz(timestepper._V_Q, timestepper._V_p)  # driver.py:336-337
     else:
-        model_problem = TaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa, viscosity=args.viscosity or 0.0)
+        if args.coriolis is not None:
+            model_problem = RotatingTaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa,
+                                                viscosity=args.viscosity or 0.0, coriolis=coriolis_pair(args))
+        else:
+            model_problem = TaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa, viscosity=args.viscosity or 0.0)
     Q_0, p_0 = model_problem.initial_condition()
     # driver.py:340-344
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None

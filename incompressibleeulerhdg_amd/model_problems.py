@@ -8,7 +8,7 @@ import numpy as np
 
 from .mesh import Function
 
-__all__ = ["TaylorGreen", "KelvinHelmholtz", "DoubleLayerShearFlow", "SeparableForcing"]
+__all__ = ["TaylorGreen", "RotatingTaylorGreen", "KelvinHelmholtz", "DoubleLayerShearFlow", "SeparableForcing"]
 
 
 class SeparableForcing:
@@ -76,6 +76,35 @@ class TaylorGreen:
         if integrate_pressure is not None:
             p = p - integrate_pressure(p)  # model_problems.py:104: no division by the volume
         return Function(self.V_Q, Q, "velocity_exact"), Function(self.V_p, p, "pressure_exact")
+
+
+class RotatingTaylorGreen(TaylorGreen):
+    """The Taylor-Green vortex in a rotating frame: coriolis = (f0, beta) of - f_c k x u, f_c = f0 + beta y.
+
+    The solution is TaylorGreen's: the forcing gains + f_c k x Q, which cancels the term.  With the exponential time factor the
+    forcing stays separable, profile (-kappa + 2 pi^2 nu) Q_s + f_c k x Q_s times exp(-kappa t); with forcing="constant" the
+    two parts carry different time factors (-kappa + ... and 1 - kappa t), so that combination is refused.  coriolis = (0, 0)
+    is TaylorGreen itself."""
+
+    def __init__(self, V_Q, V_p, forcing="exponential", kappa=0.5, viscosity=0.0, coriolis=(0.0, 0.0)):
+        f0, beta = (float(coriolis), 0.0) if np.ndim(coriolis) == 0 else (float(coriolis[0]), float(coriolis[1]))
+        if (f0 != 0 or beta != 0) and forcing != "exponential":
+            raise ValueError("RotatingTaylorGreen: forcing='constant' is not separable with rotation (the two time factors differ)")
+        super().__init__(V_Q, V_p, forcing, kappa, viscosity)
+        self.coriolis = (f0, beta)
+
+    def f_rhs(self):
+        f0, beta = self.coriolis
+        if f0 == 0 and beta == 0:
+            return super().f_rhs()
+        k, c = self.kappa, -self.kappa + 2.0 * np.pi ** 2 * self.viscosity
+
+        def profile(x, y):
+            qx, qy = self.Q_stationary(x, y)
+            fc = f0 + beta * y
+            return c * qx - fc * qy, c * qy + fc * qx  # k x Q = (-Q_y, Q_x)
+
+        return SeparableForcing(self.V_Q.interpolate(profile), lambda t: np.exp(-k * t))
 
 
 class KelvinHelmholtz:

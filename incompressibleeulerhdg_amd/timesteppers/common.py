@@ -52,6 +52,73 @@ def warn_if_diffusion_unstable(number, limit, what="tracer diffusion"):
                       "or the diffusivity", RuntimeWarning, stacklevel=3)
 
 
+def _stability_polynomial(a_expl, b_expl):
+    """Ascending coefficients of R(z) = 1 + z b^T (I - z A)^-1 1 of an explicit tableau"""
+    b = np.asarray(b_expl, dtype=float).reshape(-1)
+    A = np.asarray(a_expl, dtype=float).reshape(len(b), len(b))
+    coef, v = [1.0], np.ones(len(b))
+    for _ in range(len(b)):
+        coef.append(float(b @ v))
+        v = A @ v
+    return np.array(coef)
+
+
+def _imaginary_excess(a_expl, b_expl):
+    """Ascending coefficients in Y = y^2 of (|R(iy)|^2 - 1) / Y, a real polynomial; coefficients at rounding level (the order
+    conditions cancel the low ones exactly only in exact arithmetic) are set to zero"""
+    c = _stability_polynomial(a_expl, b_expl)
+    re = np.array([(-1.0) ** (m // 2) * c[m] for m in range(0, len(c), 2)])  # Re R(iy) = sum c_2j (-1)^j Y^j
+    im = np.array([(-1.0) ** (m // 2) * c[m] for m in range(1, len(c), 2)])  # Im R(iy) = y sum c_2j+1 (-1)^j Y^j
+    g = np.polynomial.polynomial.polymul(re, re)
+    g2 = np.concatenate([[0.0], np.polynomial.polynomial.polymul(im, im)]) if len(im) else np.zeros(1)
+    n = max(len(g), len(g2))
+    g = np.pad(g, (0, n - len(g))) + np.pad(g2, (0, n - len(g2)))
+    g[0] -= 1.0
+    g[np.abs(g) <= 1e-13] = 0.0
+    return g[1:]  # g[0] = R(0)^2 - 1 = 0
+
+
+def explicit_imaginary_limit(a_expl, b_expl):
+    """The imaginary-axis stability limit of an explicit tableau: the largest y up to which |R(iy')| <= 1 for all
+    0 <= y' <= y.  0 when |R| exceeds 1 right away (forward Euler, every second-order tableau with |R|^2 = 1 + c y^4 + ...)."""
+    e = _imaginary_excess(a_expl, b_expl)
+    nz = np.nonzero(e)[0]
+    if len(nz) == 0:
+        return float("inf")
+    if e[nz[0]] > 0:  # the leading term of |R|^2 - 1 is positive
+        return 0.0
+    roots = [z.real for z in np.atleast_1d(np.roots(e[::-1])) if abs(z.imag) <= 1e-12 * max(1.0, abs(z)) and z.real > 0]
+    for Y in sorted(roots):  # the first one behind which |R|^2 - 1 is positive
+        if np.polyval(e[::-1], Y * (1 + 1e-6)) > 0:
+            return float(np.sqrt(Y))
+    return float("inf")
+
+
+def explicit_imaginary_growth(a_expl, b_expl, y):
+    """max over 0 <= y' <= y of |R(iy')| - 1, the growth per step of an undamped oscillation with frequency * dt <= y; 0 up to
+    explicit_imaginary_limit."""
+    e = _imaginary_excess(a_expl, b_expl)
+    Y = float(y) ** 2
+    if Y == 0.0 or not np.any(e):
+        return 0.0
+    g = np.concatenate([[0.0], e])[::-1]  # |R|^2 - 1 as a polynomial in Y = y'^2, highest power first
+    inner = [z.real for z in np.atleast_1d(np.roots(np.polyder(g))) if abs(z.imag) <= 1e-12 * max(1.0, abs(z)) and 0 < z.real < Y]
+    worst = max(np.polyval(g, Yc) for Yc in [Y] + inner)  # the end of the interval or a local maximum inside it
+    return float(np.sqrt(1.0 + max(worst, 0.0)) - 1.0)
+
+
+def warn_if_rotation_unstable(number, growth, limit, growth_limit):
+    """The explicit Coriolis term: `number` = F dt, `growth` = the growth per step at that number, `limit` the imaginary-axis
+    limit of the tableau.  Warns when the growth per inertial period exceeds growth_limit, or when a non-zero limit is exceeded."""
+    per_period = growth * 2.0 * np.pi / number if number > 0 else 0.0
+    if per_period > growth_limit or (limit > 0 and number > limit):
+        warnings.warn(f"rotation: at the rotation number F dt = {number:.4g} the explicit tableau (imaginary-axis limit {limit:.4g}) "
+                      f"amplifies an inertial oscillation by {per_period:.3g} per inertial period (more than {growth_limit:.3g}); F is an "
+                      "upper bound of the spectral radius (the largest |f0 + beta y| on the mesh), and in 2-D the part of the "
+                      "force that is a gradient is taken by the pressure, so the flow may grow more slowly; reduce dt",
+                      RuntimeWarning, stacklevel=3)
+
+
 class IncompressibleEuler(ABC):
     """Abstract base class for timesteppers of the incompressible Euler equations.
 
@@ -59,6 +126,8 @@ class IncompressibleEuler(ABC):
     (common.py:36-70); here those live inside the engine's operator tables (edge lengths are closed
     form on the structured mesh; the BDM averaging is built into the projection kernel).
     """
+
+    rotation_growth_limit = 0.01  # growth per inertial period above which coriolis= warns: a policy default, not a measurement
 
     def __init__(self, mesh, degree, dt, label=None, **engine_options):
         self._mesh = mesh
@@ -79,6 +148,8 @@ class IncompressibleEuler(ABC):
         self._wall = engine_options.pop("wall", None)
         if self._wall is not None and self._viscosity is None:
             raise ValueError("wall= needs viscosity=")
+        # coriolis=: f0 or (f0, beta) of the explicit Coriolis term - (f0 + beta y) k x u; None: no call at all
+        self._coriolis = engine_options.pop("coriolis", None)
         self._engine_options = engine_options
         self._engine = None
         # common.py:72-73
@@ -115,6 +186,13 @@ class IncompressibleEuler(ABC):
             self._engine.set_viscosity(self._viscosity, "free_slip" if self._wall is None else self._wall)
             self.viscosity_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
             warn_if_diffusion_unstable(self._engine.viscosity_number()[1], self.viscosity_limit, what="viscosity")
+        if self._coriolis is not None:  # independent of the tracers and of the viscosity
+            f0, beta = (self._coriolis, 0.0) if np.ndim(self._coriolis) == 0 else self._coriolis
+            self._engine.set_coriolis(f0, beta)
+            number = self._engine.coriolis_number()[1]
+            self.rotation_limit = explicit_imaginary_limit(opts["a_expl"], opts["b_expl"])
+            self.rotation_growth = explicit_imaginary_growth(opts["a_expl"], opts["b_expl"], number)
+            warn_if_rotation_unstable(number, self.rotation_growth, self.rotation_limit, self.rotation_growth_limit)
         return self._engine
 
     def _as_nodal_velocity(self, Q):
