@@ -21,6 +21,7 @@ TRACER_DIFFUSION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", 
 BUOYANCY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_buoyancy.h"))
 VISCOSITY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_viscosity.h"))
 CORIOLIS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_coriolis.h"))
+TRACER_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_walls.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -93,7 +94,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -226,6 +227,14 @@ CORIOLIS_SIGNATURES = {
     "hdg_apply_coriolis": [_h, C.c_double, C.c_double, _dp, _dp],
 }
 
+# tracer wall conditions: the symbols include/hdg_tracer_walls.h declares, in a table of their own like the six above
+TRACER_WALL_SIGNATURES = {
+    "hdg_set_tracer_walls": [_h, C.c_int, _ip, _dp],
+    "hdg_get_tracer_wall_flux": [_h, C.c_int, _dp],
+    "hdg_apply_tracer_wall_diffusion": [_h, _ip, _dp, _dp, _dp],
+}
+WALL_SIDES = ("bottom", "right", "top", "left")  # the sides of the structured unit square, in the order of the C-ABI
+
 
 def wall_code(wall):
     """'free_slip' / 'no_slip' -> the integer of include/hdg_viscosity.h"""
@@ -247,7 +256,7 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
-            list(CORIOLIS_SIGNATURES.items()):
+            list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -546,6 +555,61 @@ class Engine:
         q = _arr(q, self.shape_p)
         out = np.empty(self.shape_p)
         self._ck(self.lib.hdg_apply_tracer_diffusion(self.h, _ptr(q), _ptr(out)))
+        return out
+
+    # --- tracer wall conditions (include/hdg_tracer_walls.h)
+    def _wall_arrays(self, walls, rows):
+        """walls: a dict {side: value} for every tracer, or a sequence of `rows` such dicts -> (kind, value), each (rows, 4).
+        Sides: 'bottom', 'right', 'top', 'left' on the structured unit square, 'boundary' on a general mesh; a missing side
+        is no flux."""
+        sides = ("boundary",) if self.general else WALL_SIDES
+        if isinstance(walls, dict):
+            walls = [walls] * rows
+        walls = list(walls)
+        if len(walls) != rows or not all(isinstance(w, dict) for w in walls):
+            raise ValueError(f"walls must be a dict or a sequence of {rows} dicts, one per tracer")
+        kind, value = np.zeros((rows, 4), dtype=np.int32), np.zeros((rows, 4))
+        for t, w in enumerate(walls):
+            for side, v in w.items():
+                if side not in sides:
+                    raise ValueError(f"tracer {t}: unknown wall side {side!r}; this mesh has {', '.join(sides)}")
+                kind[t, sides.index(side)] = 1
+                value[t, sides.index(side)] = float(v)
+        return kind, value
+
+    def set_tracer_walls(self, walls):
+        """Hold tracers at fixed values on wall sides: walls is a dict {side: value} applied to every tracer, or a sequence
+        of n_tracers such dicts; a missing side is no flux; None or no fixed side at all: off.  The values act through the
+        diffusivity: with kappa = 0 they do nothing."""
+        if walls is None:
+            self._ck(self.lib.hdg_set_tracer_walls(self.h, 0, None, None))
+            self._tracer_walls = None
+            return
+        kind, value = self._wall_arrays(walls, self.n_tracers)
+        self._ck(self.lib.hdg_set_tracer_walls(self.h, self.n_tracers, kind.ctypes.data_as(_ip), _ptr(value)))
+        sides = ("boundary",) if self.general else WALL_SIDES
+        self._tracer_walls = [{sides[w]: float(value[t, w]) for w in range(len(sides)) if kind[t, w]} for t in range(self.n_tracers)]
+        if not kind.any():
+            self._tracer_walls = None
+
+    def tracer_walls(self):
+        """The walls as they are set: a list of n_tracers dicts {side: value}, or None while the feature is off."""
+        return getattr(self, "_tracer_walls", None)
+
+    def tracer_wall_flux(self):
+        """(n_tracers, 4): the flux kappa_t int_w (dn q_t - eta_b (q_t - g)) of the current tracers through every side, positive
+        into the domain, 0 on a no-flux side; with zero velocity d/dt int q_t is the sum over the sides."""
+        flux = np.zeros((self.n_tracers, 4))
+        self._ck(self.lib.hdg_get_tracer_wall_flux(self.h, self.n_tracers, _ptr(flux)))
+        return flux
+
+    def apply_tracer_wall_diffusion(self, q, walls):
+        """M^-1 (D + sum_w D_w) q + M^-1 sum_w l_w of one nodal DG_k field for one dict of walls, without kappa (test hook;
+        it sets nothing)."""
+        q = _arr(q, self.shape_p)
+        kind, value = self._wall_arrays(walls, 1)
+        out = np.empty(self.shape_p)
+        self._ck(self.lib.hdg_apply_tracer_wall_diffusion(self.h, kind.ctypes.data_as(_ip), _ptr(value), _ptr(q), _ptr(out)))
         return out
 
     # --- Boussinesq buoyancy (include/hdg_buoyancy.h; DESIGN.md section 20)

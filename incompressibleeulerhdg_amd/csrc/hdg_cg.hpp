@@ -283,9 +283,19 @@ __global__ __launch_bounds__(128) void k_tracer_adv(Geo g, DevTables T, int nt, 
 // has just run on the same q (so the ghost rows of the periodic square are filled) and has written out.  Per tracer the
 // floating-point operations and their order are those of one tracer alone, whatever TB and whatever the other tracers'
 // kappa; a tracer with kappa_t = 0 is neither read back nor written.
-template <int K, int TB>
+//
+// WALLS: some tracer is held at a fixed value on a side of the unit square.  wkind / wval hold, per tracer,
+// the kind (0 no flux, 1 fixed value) and the value of the four sides bottom, right, top, left; a wall leg e (0 or 2) of a cell
+// lies on side wall_side(s, e), and a fixed side adds  Wall[s][e] q_K + g wvec[s][e]  to the row (wtab: per shape Wall[0], Wall[2],
+// wvec[0], wvec[2]; TracerDiffusionTables::packed_walls).  The idiom is k_viscosity's: the branch around a wall block is taken by
+// the whole wave (a ballot), a lane that has a neighbour there and a tracer whose side is no-flux contribute an operand of zero,
+// so the accumulator is never indexed dynamically and per tracer the operations do not depend on TB or on the other tracers.
+// WALLS = false is the kernel as it was: everything new sits behind if constexpr.
+template <int K, int TB, bool WALLS>
 __global__ __launch_bounds__(128) void k_tracer_diff(Geo g, const double* __restrict__ tab, const double* __restrict__ kappa, int nt,
-                                                      long tstride, const double* __restrict__ q, double* __restrict__ out) {
+                                                      long tstride, const double* __restrict__ q, double* __restrict__ out,
+                                                      const double* __restrict__ wtab, const int* __restrict__ wkind,
+                                                      const double* __restrict__ wval) {
   constexpr int NP = Dim<K>::NP, BL = NP * NP;
   HDG_CELL_PROLOGUE
   const int t0 = blockIdx.y * TB;
@@ -312,6 +322,41 @@ __global__ __launch_bounds__(128) void k_tracer_diff(Geo g, const double* __rest
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     long cn;
+    if constexpr (WALLS) {
+      const bool wall = !nbr(s, e, i, j, g, cn);
+      if (e != 1 && __builtin_amdgcn_ballot_w64(wall) != 0) {  // uniform over the wave
+        const int side = s == 0 ? (e == 0 ? 0 : 3) : (e == 0 ? 2 : 1);
+        const double* __restrict__ W = wtab + (long)s * (2 * BL + 2 * NP) + (e == 0 ? 0 : BL);
+        const double* __restrict__ wv = wtab + (long)s * (2 * BL + 2 * NP) + 2 * BL + (e == 0 ? 0 : NP);
+        bool on[TB];
+        double gv[TB];
+#pragma unroll
+        for (int b = 0; b < TB; b++) {
+          const bool fixed = b < nb && wkind[(t0 + b) * 4 + side] != 0;  // uniform over the workgroup
+          const double gb = fixed ? wval[(t0 + b) * 4 + side] : 0.0;  // a no-flux side's value is never read
+          on[b] = wall && fixed;
+          gv[b] = wall ? gb : 0.0;
+        }
+#pragma unroll
+        for (int m = 0; m < NP; m++) {
+          double x[TB];
+#pragma unroll
+          for (int b = 0; b < TB; b++) x[b] = on[b] ? qc[b][m] : 0.0;
+#pragma unroll
+          for (int r = 0; r < NP; r++) {
+            const double a = W[r * NP + m];
+#pragma unroll
+            for (int b = 0; b < TB; b++) F[b][r] = fma(a, x[b], F[b][r]);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < NP; r++) {
+          const double a = wv[r];
+#pragma unroll
+          for (int b = 0; b < TB; b++) F[b][r] = fma(a, gv[b], F[b][r]);
+        }
+      }
+    }
     if (!nbr(s, e, i, j, g, cn)) continue;
     double qn[TB][NP];
 #pragma unroll

@@ -31,6 +31,7 @@
 #include "../../include/hdg_checkpoint.h"
 #include "../../include/hdg_transfer.h"
 #include "../../include/hdg_tracer_diffusion.h"
+#include "../../include/hdg_tracer_walls.h"
 #include "../../include/hdg_buoyancy.h"
 #include "../../include/hdg_viscosity.h"
 #include "../../include/hdg_coriolis.h"
@@ -55,6 +56,7 @@
 #include "hdg_buoyancy.hpp"
 #include "hdg_viscosity.hpp"
 #include "hdg_coriolis.hpp"
+#include "hdg_tracer_walls.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
@@ -3613,10 +3615,15 @@ struct Engine {
   }
   // out_t += kap_t M^-1 D q_t for n tracers, tracer-major (kap: device values for the kernel, host values for the CSR path);
   // structured meshes read the ghost rows of q, which the caller has filled (tracer_adv on the same q, or halo_rows)
-  void tracer_diff(const double* q, const double* kap_dev, const double* kap_host, double* out, int n) {
+  // slot: the first tracer's row of the wall arrays (0: the engine's setting, HDG_MAX_TRACERS: the hook's); < 0: no walls
+  void tracer_diff(const double* q, const double* kap_dev, const double* kap_host, double* out, int n, int slot = -1) {
     if (general) {
-      for (int t = 0; t < n; t++)
-        if (kap_host[t] != 0.0) csr(gdiff, q + t * NPv, kap_host[t], 1.0, out + t * NPv);
+      for (int t = 0; t < n; t++) {
+        if (kap_host[t] == 0.0) continue;
+        const bool fixed = slot >= 0 && tw_kind_all[(size_t)(slot + t) * 4] != 0;  // the whole boundary: index 0
+        csr(fixed ? gdiffw : gdiff, q + t * NPv, kap_host[t], 1.0, out + t * NPv);
+        if (fixed) axpby(NPv, kap_host[t] * tw_val_all[(size_t)(slot + t) * 4], d_gwload, 1.0, out + t * NPv);
+      }
       return;
     }
     tally(LC_OTHER, 3.0 * n * bP());
@@ -3626,14 +3633,134 @@ struct Engine {
         constexpr int TB = decltype(tb)::value;
         dim3 grid = cell_grid();
         grid.y = (unsigned)((n + TB - 1) / TB);
-        k_tracer_diff<KK, TB><<<grid, bs(), 0, stream>>>(g, d_difftab, kap_dev, n, NPv, q, out);
+        if (slot >= 0)  // instead of the plain form, not after it: no launch more and no second pass over out
+          k_tracer_diff<KK, TB, true><<<grid, bs(), 0, stream>>>(g, d_difftab, kap_dev, n, NPv, q, out, d_walltab, d_wkind + 4 * slot, d_wval + 4 * slot);
+        else
+          k_tracer_diff<KK, TB, false><<<grid, bs(), 0, stream>>>(g, d_difftab, kap_dev, n, NPv, q, out, nullptr, nullptr, nullptr);
       });
     });
   }
-  // the tendency of every tracer: transport, plus diffusion when some kappa_t != 0
+  // the tendency of every tracer: transport, plus diffusion when some kappa_t != 0 (with the wall terms when some side is fixed)
   void tracer_tendency(const double* q, const double* u, double* out) {
     tracer_adv(q, u, out, n_tr);
-    if (!tr_kappa.empty()) tracer_diff(q, d_kappa, tr_kappa.data(), out, n_tr);
+    if (!tr_kappa.empty()) tracer_diff(q, d_kappa, tr_kappa.data(), out, n_tr, tw_kind.empty() ? -1 : 0);
+  }
+  // ---- fixed-value walls and the wall flux (include/hdg_tracer_walls.h).  Per tracer and side (structured:
+  // bottom, right, top, left; general: the whole boundary at index 0) a kind (0 no flux, 1 fixed value) and a value; a fixed side
+  // adds the Nitsche terms D_w q + l_w(g) to the diffusion form.  Structured meshes: k_tracer_diff<K, TB, true> runs instead of
+  // the plain form; general meshes: a second assembled operator M^-1 (D + D_w) and one axpy with the load vector per tracer.
+  // Configuration like kappa, and independent of it: with every kappa_t = 0 the walls do nothing.
+  std::vector<int> tw_kind;     // n_tr x 4 while some side is fixed, empty while the feature is off
+  std::vector<double> tw_val;   // n_tr x 4 (0 on a no-flux side)
+  std::vector<int> tw_kind_all = std::vector<int>((HDG_MAX_TRACERS + 1) * 4, 0);       // host mirror of d_wkind, the hook's row last
+  std::vector<double> tw_val_all = std::vector<double>((HDG_MAX_TRACERS + 1) * 4, 0.0);  // host mirror of d_wval
+  int* d_wkind = nullptr;
+  double *d_wval = nullptr, *d_wflux = nullptr, *d_wpart = nullptr, *d_gwload = nullptr;
+  const double* d_walltab = nullptr;
+  DevCsr gdiffw;
+  double wall_wone = 0.0;         // structured: eta_b h; general: the sum of eta_b |e| over the boundary
+  double diff_lambda_gw = -1.0;   // general: the infinity norm of M^-1 (D + D_w)
+  static const char* wall_side_name(bool gen, int w) {
+    static const char* names[4] = {"bottom", "right", "top", "left"};
+    return gen ? "boundary" : names[w];
+  }
+  int wall_flux_blocks() const { return (std::max(g.nx, g.ny) + HDG_WALL_FLUX_BLOCK - 1) / HDG_WALL_FLUX_BLOCK; }
+  // the wall tables, on the first fixed side
+  void walls_setup() {
+    diff_setup();
+    if (d_wkind) return;
+    void* p = nullptr;
+    HIPCHECK(hipMalloc(&p, sizeof(int) * tw_kind_all.size()));
+    allocs.push_back(p);
+    HIPCHECK(hipMemset(p, 0, sizeof(int) * tw_kind_all.size()));
+    d_wval = dalloc((long)tw_val_all.size());
+    d_wflux = dalloc(HDG_MAX_TRACERS * 4);
+    if (general) {
+      double lam = 0.0;
+      std::vector<double> load;
+      gdiffw = upload_csr(assemble_tracer_diffusion(*gtab, *gm, lam, &load, &wall_wone));
+      d_gwload = const_cast<double*>(upload(load));
+      diff_lambda_gw = lam;
+    } else {
+      const TracerDiffusionTables D(K, g.h);
+      d_walltab = upload(D.packed_walls());
+      wall_wone = D.wone;
+      d_wpart = dalloc((long)HDG_MAX_TRACERS * 4 * wall_flux_blocks());
+    }
+    d_wkind = (int*)p;
+  }
+  // throws unless kind / value (rows x 4) are an admissible setting of this mesh; what: the entry point's name
+  void check_walls(const char* what, int rows, const int* kind, const double* value) const {
+    for (int t = 0; t < rows; t++)
+      for (int w = 0; w < 4; w++) {
+        const int kd = kind[t * 4 + w];
+        const std::string where = std::string(what) + ": tracer " + std::to_string(t) + ", side " + std::to_string(w) +
+            " (" + wall_side_name(general && w == 0, w) + ")";
+        if (kd != 0 && kd != 1) throw where + ": kind " + std::to_string(kd) + " is neither 0 (no flux) nor 1 (fixed value)";
+        if (kd == 0) continue;
+        if (!value || !std::isfinite(value[t * 4 + w])) throw where + ": the fixed value " + (value ? std::to_string(value[t * 4 + w]) : std::string("(null)")) + " is not finite";
+        if (!general && periodic) throw where + ": the doubly periodic square has no walls";
+        if (general && w != 0) throw where + ": a general mesh has one side, the whole boundary, at index 0";
+      }
+  }
+  void upload_walls(int row0, int rows) {
+    HIPCHECK(hipMemcpyAsync(d_wkind + 4 * row0, tw_kind_all.data() + 4 * row0, sizeof(int) * 4 * rows, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipMemcpyAsync(d_wval + 4 * row0, tw_val_all.data() + 4 * row0, sizeof(double) * 4 * rows, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  void set_tracer_walls(int n, const int* kind, const double* value) {
+    if (comm->size > 1) cg_setup();  // a strip: the tracer error of hdg_set_tracer
+    if (step_open) throw std::string("hdg_set_tracer_walls: a step is open (between hdg_begin_step and the end of the step)");
+    bool any = false;
+    if (kind) {
+      if (n != n_tr) throw std::string("hdg_set_tracer_walls: " + std::to_string(n) + " row(s) for " + std::to_string(n_tr) + " tracer(s)");
+      check_walls("hdg_set_tracer_walls", n, kind, value);
+      for (int m = 0; m < 4 * n; m++) any = any || kind[m] != 0;
+    }
+    if (!any) { tw_kind.clear(); tw_val.clear(); return; }
+    walls_setup();
+    tw_kind.assign(kind, kind + 4 * n);
+    tw_val.assign((size_t)4 * n, 0.0);
+    for (int m = 0; m < 4 * n; m++) if (kind[m]) tw_val[(size_t)m] = value[m];
+    std::copy(tw_kind.begin(), tw_kind.end(), tw_kind_all.begin());
+    std::copy(tw_val.begin(), tw_val.end(), tw_val_all.begin());
+    upload_walls(0, n);
+  }
+  // test hook: out = M^-1 (D + sum_w D_w) q + M^-1 sum_w l_w for one field (device layout), without kappa; sets nothing
+  void apply_tracer_wall_diffusion(const int* kind, const double* value, double* q, double* out) {
+    bool any = false;
+    check_walls("hdg_apply_tracer_wall_diffusion", 1, kind, value);
+    for (int w = 0; w < 4; w++) any = any || kind[w] != 0;
+    if (!any) { apply_tracer_diffusion(q, out); return; }  // the plain form: bit for bit
+    walls_setup();
+    for (int w = 0; w < 4; w++) {
+      tw_kind_all[(size_t)HDG_MAX_TRACERS * 4 + w] = kind[w];
+      tw_val_all[(size_t)HDG_MAX_TRACERS * 4 + w] = kind[w] ? value[w] : 0.0;
+    }
+    upload_walls(HDG_MAX_TRACERS, 1);
+    if (!general) halo_rows(q, (long)g.R * g.nx, g.nx, NP * 2, 1);
+    zero(out, NPv);
+    const double one = 1.0;
+    tracer_diff(q, d_kappa + HDG_MAX_TRACERS, &one, out, 1, HDG_MAX_TRACERS);
+  }
+  // flux[n_tr x 4] of the current tracers q_cur
+  void tracer_wall_flux(double* flux) {
+    std::fill(flux, flux + 4 * n_tr, 0.0);
+    if (tw_kind.empty() || tr_kappa.empty()) return;  // no fixed side, or no diffusivity: no flux through any wall
+    if (general) {
+      for (int t = 0; t < n_tr; t++) {
+        if (!tw_kind[(size_t)t * 4] || tr_kappa[(size_t)t] == 0.0) continue;
+        flux[t * 4] = tr_kappa[(size_t)t] * (tw_val[(size_t)t * 4] * wall_wone - dot(NPv, d_gwload, q_cur + t * NPv, KC));
+      }
+      return;
+    }
+    const int nblk = wall_flux_blocks();
+    tally(LC_OTHER, 0.0);
+    tally(LC_OTHER, 0.0);
+    by_degree([&](auto k) { k_tracer_wall_flux<k()><<<dim3(nblk, 4), HDG_WALL_FLUX_BLOCK, 0, stream>>>(g, d_walltab, n_tr, NPv, q_cur, d_wpart); });
+    k_tracer_wall_flux_finish<<<1, 64, 0, stream>>>(n_tr, nblk, g.nx, g.ny, wall_wone, d_kappa, d_wkind, d_wval, d_wpart, d_wflux);
+    HIPCHECK(hipMemcpyAsync(flux, d_wflux, sizeof(double) * 4 * n_tr, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
   }
   // test hook: out = M^-1 D q for one field (q, out in the device layout), without kappa
   void apply_tracer_diffusion(double* q, double* out) {
@@ -3647,8 +3774,17 @@ struct Engine {
     diff_setup();
     double kmax = 0.0;
     for (double x : tr_kappa) kmax = std::max(kmax, x);
-    out2[0] = diff_lambda;
-    out2[1] = kmax * cfg.dt * diff_lambda;
+    double lam = diff_lambda;
+    if (!tw_kind.empty()) {  // with the wall blocks of every side that is fixed for some tracer
+      if (general) lam = std::max(lam, diff_lambda_gw);
+      else {
+        bool fixed[4] = {false, false, false, false};
+        for (size_t m = 0; m < tw_kind.size(); m++) fixed[m & 3] = fixed[m & 3] || tw_kind[m] != 0;
+        lam = TracerDiffusionTables(K, g.h).lambda_walls(fixed);
+      }
+    }
+    out2[0] = lam;
+    out2[1] = kmax * cfg.dt * lam;
   }
   // ---- Boussinesq buoyancy: the forcing slot j of a step becomes b_rhs[j] + B(q^(j)),
   // B(q) = sum_t beta_t q_t g embedded in the velocity space (hdg_buoyancy.hpp).  The s + 1 vectors buoy[j] stand beside brhs and
@@ -4400,6 +4536,8 @@ struct Engine {
     f.add("dg_rtol", cfg.dg_rtol); f.add("dg_restart", (long)cfg.dg_restart); f.add("dg_maxit", (long)cfg.dg_maxit);
     f.add("n_tracers", (long)cfg.n_tracers);
     for (size_t t = 0; t < tr_kappa.size(); t++) f.add("tracer_kappa[" + std::to_string(t) + "]", tr_kappa[t]);  // only with some kappa != 0
+    for (size_t m = 0; m < tw_kind.size(); m++)  // one line per (tracer, side) with a fixed value, and only then
+      if (tw_kind[m]) f.add("tracer_wall[" + std::to_string(m / 4) + "][" + std::to_string(m % 4) + "]", tw_val[m]);
     for (size_t t = 0; t < by_beta.size(); t++) f.add("buoyancy_beta[" + std::to_string(t) + "]", by_beta[t]);  // only with some beta != 0
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
@@ -5460,6 +5598,34 @@ int hdg_apply_tracer_diffusion(hdg_handle* h, const double* q, double* out) {
   E.tracer_alloc();
   E.put_P(q, E.wP1);
   E.apply_tracer_diffusion(E.wP1, E.q_t);
+  E.get_P(E.q_t, out);
+  HDG_API_END(h)
+}
+
+
+// ---- tracer wall conditions (include/hdg_tracer_walls.h)
+int hdg_set_tracer_walls(hdg_handle* h, int n, const int* kind, const double* value) {
+  HDG_API_BEGIN(h)
+  E.set_tracer_walls(n, kind, value);
+  HDG_API_END(h)
+}
+int hdg_get_tracer_wall_flux(hdg_handle* h, int n, double* flux) {
+  HDG_API_BEGIN(h)
+  if (!flux) throw std::string("null argument");
+  if (!E.tracer_on) throw std::string("hdg_get_tracer_wall_flux: no tracer is set (hdg_set_tracer)");
+  if (E.step_open) throw std::string("hdg_get_tracer_wall_flux: a step is open");
+  if (n != E.n_tr) throw std::string("hdg_get_tracer_wall_flux: " + std::to_string(n) + " row(s) for " + std::to_string(E.n_tr) + " tracer(s)");
+  E.tracer_wall_flux(flux);
+  HDG_API_END(h)
+}
+int hdg_apply_tracer_wall_diffusion(hdg_handle* h, const int kind[4], const double value[4], const double* q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!kind || !q || !out) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_apply_tracer_wall_diffusion: a step is open");
+  E.diff_setup();
+  E.tracer_alloc();
+  E.put_P(q, E.wP1);
+  E.apply_tracer_wall_diffusion(kind, value, E.wP1, E.q_t);
   E.get_P(E.q_t, out);
   HDG_API_END(h)
 }

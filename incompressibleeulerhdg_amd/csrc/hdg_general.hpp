@@ -815,8 +815,13 @@ inline void assemble_cg(const GeneralTables& T, const GMesh& M, const GeneralOps
 // TracerDiffusionTables): M^-1 D assembled once in the orthonormal modal basis psi = Dub / sqrt(detJ) of DG_k, rows and columns
 // c * np + m, with eta_e = (k+1)(k+2)/4 max(P_K / |K|) from the actual perimeters and areas of the two cells of an edge.
 // Boundary edges carry no term.  lambda: the infinity norm of the assembled operator (symmetric in this basis, so >= rho).
+// Fixed-value walls: with load != nullptr every boundary edge e of cell K adds the Nitsche block
+// int_e ( psi_r dn psi_m + psi_m dn psi_r - eta_b psi_r psi_m ), eta_b = (k+1)(k+2)/2 P_K / |K|, so that the result is
+// M^-1 (D + D_w); load receives the load vector of g = 1, int_e ( eta_b psi_r - dn psi_r ), which is minus the flux functional,
+// and wtotal the sum of eta_b |e|: the wall flux is kappa (g wtotal - load . q).
 // ------------------------------------------------------------------------------------------
-inline Csr assemble_tracer_diffusion(const GeneralTables& T, const GMesh& M, double& lambda) {
+inline Csr assemble_tracer_diffusion(const GeneralTables& T, const GMesh& M, double& lambda, std::vector<double>* load = nullptr,
+                                     double* wtotal = nullptr) {
   const int k = T.k, np = T.np, nc = M.nc;
   Dubiner U(k);
   CsrBuilder A(nc * np, nc * np);
@@ -861,8 +866,38 @@ inline Csr assemble_tracer_diffusion(const GeneralTables& T, const GMesh& M, dou
   std::vector<real> v[2], dn[2];
   for (int sd = 0; sd < 2; sd++) { v[sd].resize(np); dn[sd].resize(np); }
   std::vector<real> blk[2][2];
+  if (load) load->assign((size_t)nc * np, 0.0);
+  if (wtotal) *wtotal = 0.0;
   for (int e = 0; e < M.ne; e++) {
-    if (M.ecell[2 * (size_t)e + 1] < 0) continue;  // a wall: no flux, no term
+    if (M.ecell[2 * (size_t)e + 1] < 0) {  // a wall: no flux, no term; a fixed value, the Nitsche block and the load
+      if (!load) continue;
+      const int c = M.ecell[2 * (size_t)e], l = M.elocal[2 * (size_t)e];
+      const real sgw = (real)M.csig[3 * (size_t)c + l], nxw = sgw * (real)M.enx[e], nyw = sgw * (real)M.eny[e];  // out of the domain
+      const real eta_b = (real)(k + 1) * (k + 2) / 2 * ratio[(size_t)c];
+      const real is = 1 / std::sqrt((real)M.detJ[c]);
+      const double* Ji = &M.Jinv[4 * (size_t)c];
+      std::vector<real> W((size_t)np * np, 0), wv(np, 0);
+      for (int q = 0; q < T.nqe; q++) {
+        real xi, eta;
+        GMesh::edge_ref(l, M.cflip[3 * (size_t)c + l], tq[q], xi, eta);
+        U.eval(xi, eta, val.data(), gx.data(), gy.data());
+        for (int m = 0; m < np; m++) {
+          v[0][m] = is * val[m];
+          dn[0][m] = is * (nxw * ((real)Ji[0] * gx[m] + (real)Ji[2] * gy[m]) + nyw * ((real)Ji[1] * gx[m] + (real)Ji[3] * gy[m]));
+        }
+        const real w = wq[q] * (real)M.elen[e];
+        for (int r = 0; r < np; r++) {
+          for (int m = 0; m < np; m++) W[(size_t)r * np + m] += w * (v[0][r] * dn[0][m] + v[0][m] * dn[0][r] - eta_b * v[0][r] * v[0][m]);
+          wv[r] += w * (eta_b * v[0][r] - dn[0][r]);
+        }
+      }
+      for (int r = 0; r < np; r++) {
+        for (int m = 0; m < np; m++) A.add(c * np + r, c * np + m, (double)W[(size_t)r * np + m]);
+        (*load)[(size_t)c * np + r] += (double)wv[r];
+      }
+      if (wtotal) *wtotal += (double)(eta_b * (real)M.elen[e]);
+      continue;
+    }
     const int cell[2] = {M.ecell[2 * (size_t)e], M.ecell[2 * (size_t)e + 1]};
     const int loc[2] = {M.elocal[2 * (size_t)e], M.elocal[2 * (size_t)e + 1]};
     const real sg = (real)M.csig[3 * (size_t)cell[0] + loc[0]], nx = sg * (real)M.enx[e], ny = sg * (real)M.eny[e];  // out of cell[0], the '+' cell

@@ -631,16 +631,25 @@ struct Tables {
 // 2k (k + 1 collapsed Gauss-Jacobi points a side), the edge rule is the advection form's (ceil((3k+4)/2) points, exact to 3k+3).
 // lambda: the largest absolute row sum over both shapes and every set of edges with a neighbour; the operator is symmetric in
 // this basis, so lambda >= rho(M^-1 D) on every mesh these cells tile.
+// Fixed-value walls: a tracer held at g on a wall leg e of cell K adds the Nitsche terms
+//   Wall[s][e]  int_e ( psi_r dn psi_m + psi_m dn psi_r - eta_b psi_r psi_m ),   eta_b = (k+1)(k+2)/2 P_K / |K| = 2 eta
+//   wvec[s][e]  int_e ( eta_b psi_r - dn psi_r )                                 (the load of g = 1)
+// to the cell's row: + Wall[e] q_K + g wvec[e].  Same edge rule, same long double.
 // ------------------------------------------------------------------------------------------
 struct TracerDiffusionTables {
   int k, np;
   double h, eta, lambda;
   dvec Vol[2], Own[2][3], Nbr[2][3];
+  // fixed-value walls, leg edges e = 0 and 2 only ([s][1] stays empty)
+  double eta_b, wone;         // eta_b = 2 eta; wone = eta_b h = int_e eta_b over one leg
+  dvec Wall[2][3], wvec[2][3];
 
   TracerDiffusionTables(int k_, double h_) : k(k_), np(n_scalar(k_)), h(h_) {
     const real rh = h, s2 = std::sqrt((real)2);
     const real eta_ = (real)(k + 1) * (k + 2) / 4 * 2 * (2 + s2) / rh;
     eta = (double)eta_;
+    const real etab_ = 2 * eta_;
+    eta_b = (double)etab_; wone = (double)(etab_ * rh);
     const real nfix[3][2] = {{0, 1}, {1 / s2, 1 / s2}, {1, 0}};
     const real sg[2][3] = {{-1, 1, -1}, {1, -1, 1}}, elen_[3] = {rh, s2 * rh, rh};
     Dubiner U(k);
@@ -678,7 +687,7 @@ struct TracerDiffusionTables {
       const real sgn = s == 0 ? 1 : -1;
       for (int e = 0; e < 3; e++) {
         const real nx = sg[s][e] * nfix[e][0], ny = sg[s][e] * nfix[e][1];  // this cell's outward normal
-        std::vector<real> O((size_t)np * np, 0), N((size_t)np * np, 0);
+        std::vector<real> O((size_t)np * np, 0), N((size_t)np * np, 0), W((size_t)np * np, 0), wv(np, 0);
         for (int q = 0; q < nqe; q++) {
           real xi, et;
           edge_ref(s, e, tq[q], xi, et);
@@ -688,14 +697,18 @@ struct TracerDiffusionTables {
           U.eval(xi, et, vn.data(), nx_.data(), ny_.data());
           for (int m = 0; m < np; m++) { vn[m] /= rh; dnn[m] = -sgn * (nx * nx_[m] + ny * ny_[m]) / (rh * rh); }
           const real w = wq[q] * elen_[e];
-          for (int r = 0; r < np; r++)
+          for (int r = 0; r < np; r++) {
             for (int m = 0; m < np; m++) {
               O[(size_t)r * np + m] += w * (val[r] * dno[m] / 2 + val[m] * dno[r] / 2 - eta_ * val[r] * val[m]);
               N[(size_t)r * np + m] += w * (val[r] * dnn[m] / 2 - vn[m] * dno[r] / 2 + eta_ * val[r] * vn[m]);
+              W[(size_t)r * np + m] += w * (val[r] * dno[m] + val[m] * dno[r] - etab_ * val[r] * val[m]);
             }
+            wv[r] += w * (etab_ * val[r] - dno[r]);
+          }
         }
         Own[s][e].assign(O.begin(), O.end());
         Nbr[s][e].assign(N.begin(), N.end());
+        if (e != 1) { Wall[s][e].assign(W.begin(), W.end()); wvec[s][e].assign(wv.begin(), wv.end()); }
       }
     }
     lambda = 0.0;
@@ -721,6 +734,44 @@ struct TracerDiffusionTables {
       for (int e = 0; e < 3; e++) out.insert(out.end(), Nbr[s][e].begin(), Nbr[s][e].end());
     }
     return out;
+  }
+  // ---- fixed-value walls.  The sides of the unit square in the order bottom, right, top, left;
+  // wall_side(s, e): the side a leg edge (s, e) can lie on (e = 0 horizontal, e = 2 vertical; the hypotenuse is never a wall).
+  static int wall_side(int s, int e) { return s == 0 ? (e == 0 ? 0 : 3) : (e == 0 ? 2 : 1); }
+  // The flux functional: the wall flux of a cell through its leg (s, e), kappa int_e (dn q - eta_b (q - g)), is
+  // kappa (g wone - wvec[s][e] . q_K): Wall[s][e]^T coef(1) = - wvec[s][e], so nothing more is stored.
+  // device layout: per shape s  Wall[s][0], Wall[s][2] (np x np row-major, as the seven blocks), wvec[s][0], wvec[s][2]
+  static constexpr int wall_stride(int np) { return 2 * np * np + 2 * np; }
+  dvec packed_walls() const {
+    dvec out;
+    for (int s = 0; s < 2; s++) {
+      for (int e = 0; e < 3; e += 2) out.insert(out.end(), Wall[s][e].begin(), Wall[s][e].end());
+      for (int e = 0; e < 3; e += 2) out.insert(out.end(), wvec[s][e].begin(), wvec[s][e].end());
+    }
+    return out;
+  }
+  // lambda with the wall blocks: the largest absolute row sum over both shapes and every assignment of nothing / a neighbour /
+  // (on a leg whose side is fixed for some tracer) the wall block to the edges; fixed: the four sides.  Never below lambda.
+  double lambda_walls(const bool (&fixed)[4]) const {
+    double lam = lambda;
+    for (int s = 0; s < 2; s++)
+      for (int st = 0; st < 27; st++) {  // per edge: 0 nothing, 1 a neighbour, 2 the wall block
+        const int se[3] = {st % 3, st / 3 % 3, st / 9};
+        if (se[1] == 2 || (se[0] == 2 && !fixed[wall_side(s, 0)]) || (se[2] == 2 && !fixed[wall_side(s, 2)])) continue;
+        for (int r = 0; r < np; r++) {
+          double sum = 0.0;
+          for (int m = 0; m < np; m++) {
+            double d = Vol[s][(size_t)r * np + m];
+            for (int e = 0; e < 3; e++) {
+              if (se[e] == 1) { d += Own[s][e][(size_t)r * np + m]; sum += std::fabs(Nbr[s][e][(size_t)r * np + m]); }
+              if (se[e] == 2) d += Wall[s][e][(size_t)r * np + m];
+            }
+            sum += std::fabs(d);
+          }
+          lam = std::max(lam, sum);
+        }
+      }
+    return lam;
   }
 };
 

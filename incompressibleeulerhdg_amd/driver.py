@@ -9,6 +9,11 @@ driver.py:203-213); the ``conforming`` discretisation raises (SURVEY.md section 
 the CG vorticity, callbacks.py:30-85) and ``--tracer_advection`` (driver.py:340-344) work on every mesh.  The final fields are written to ``solution.pvd``
 (``--output``) like the reference does (driver.py:356-385).
 
+``--problem cavity`` is the unit square at rest with every tracer starting from 0; ``--tracer_wall SIDE VALUE [T]`` holds
+tracers at fixed values on wall sides, e.g. a heated cavity:
+``--problem cavity --tracer_advection --tracer_diffusivity K --viscosity NU --wall no_slip --buoyancy 1 --tracer_wall left 0.5
+--tracer_wall right -0.5``.  The wall flux of every tracer and side is printed at the end.
+
 ``--particles FILE`` advects Lagrangian particles through the two structured problems on the device
 and writes their positions to ``--particle_output`` (``particles.npz``).
 
@@ -36,11 +41,11 @@ import time
 
 import numpy as np
 
-from ._lib import DIAGNOSTICS, HDG_MAX_TRACERS, POINT_COLUMNS
+from ._lib import DIAGNOSTICS, HDG_MAX_TRACERS, POINT_COLUMNS, WALL_SIDES
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
-from .model_problems import DoubleLayerShearFlow, KelvinHelmholtz, RotatingTaylorGreen, TaylorGreen
+from .model_problems import Cavity, DoubleLayerShearFlow, KelvinHelmholtz, RotatingTaylorGreen, TaylorGreen
 from .output import VTKFile
 from .timesteppers import (
     IncompressibleEulerHDGIMEXARS2_232,
@@ -64,7 +69,7 @@ TIMESTEPPERS = {
 def build_parser():
     """Same flags and defaults as driver.py:26-176."""
     parser = argparse.ArgumentParser("Mesh specifications and polynomial degree")
-    parser.add_argument("--problem", choices=["taylorgreen", "kelvinhelmholtz", "shear"], type=str, default="taylorgreen", help="model problem to solve")
+    parser.add_argument("--problem", choices=["taylorgreen", "kelvinhelmholtz", "shear", "cavity"], type=str, default="taylorgreen", help="model problem to solve")
     parser.add_argument("--nx", metavar="nx", type=int, default=8, help="number of grid cells in x-direction")
     parser.add_argument("--refinement", metavar="refinement", type=int, default=2, help="refinement level for unit disk mesh")
     parser.add_argument("--degree", metavar="degree", type=int, default=1, help="polynomial degree")
@@ -85,6 +90,10 @@ def build_parser():
     parser.add_argument("--tracer_diffusivity", metavar="K", type=float, nargs="+", default=None,
                         help="molecular diffusivity of the tracers (with --tracer_advection): one value for all of them or "
                              "exactly --tracers values; explicit in time, see the printed diffusion number")
+    parser.add_argument("--tracer_wall", metavar=("SIDE", "VALUE"), nargs="+", action="append", default=None,
+                        help="SIDE VALUE [T]: hold tracer T (without T: every tracer) at VALUE on the wall SIDE (bottom, right, top, "
+                             "left on the unit square; boundary with --problem kelvinhelmholtz); repeatable; acts through "
+                             "--tracer_diffusivity; the wall flux of every tracer and side is printed at the end")
     parser.add_argument("--viscosity", metavar="NU", type=float, default=None,
                         help="kinematic viscosity: the momentum equation gains NU Laplace u, explicit in time (see the printed "
                              "viscous diffusion number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
@@ -185,6 +194,7 @@ def check_tracers(args):
         for m, x in enumerate(kappa):
             if not (np.isfinite(x) and x >= 0):
                 raise RuntimeError(f"--tracer_diffusivity: value {m} ({x}) is not a finite number >= 0")
+    tracer_walls(args)
     beta = args.buoyancy
     if args.gravity is not None and beta is None:
         raise RuntimeError("--gravity needs --buoyancy")
@@ -199,6 +209,39 @@ def check_tracers(args):
         for m, x in enumerate(args.gravity or ()):
             if not np.isfinite(x):
                 raise RuntimeError(f"--gravity: component {m} ({x}) is not a finite number")
+
+
+def tracer_walls(args):
+    """--tracer_wall SIDE VALUE [T] (repeatable) -> one dict {side: value} per tracer, or None without the flag; refuses what
+    the engine would, before any engine exists."""
+    if not args.tracer_wall:
+        return None
+    if not args.tracer_advection:
+        raise RuntimeError("--tracer_wall needs --tracer_advection")
+    if args.problem == "shear":
+        raise RuntimeError("--tracer_wall: the doubly periodic square of --problem shear has no walls")
+    sides = ("boundary",) if args.problem == "kelvinhelmholtz" else WALL_SIDES
+    walls = [dict() for _ in range(args.tracers)]
+    for item in args.tracer_wall:
+        if len(item) not in (2, 3):
+            raise RuntimeError(f"--tracer_wall takes SIDE VALUE [T] (got {len(item)} words: {' '.join(item)})")
+        side = item[0]
+        if side not in sides:
+            raise RuntimeError(f"--tracer_wall: unknown side {side!r} for --problem {args.problem} (one of {', '.join(sides)})")
+        try:
+            value = float(item[1])
+        except ValueError:
+            value = float("nan")
+        if not np.isfinite(value):
+            raise RuntimeError(f"--tracer_wall {side}: value {item[1]} is not a finite number")
+        if len(item) == 3:
+            if not item[2].isdigit() or int(item[2]) >= args.tracers:
+                raise RuntimeError(f"--tracer_wall {side}: tracer {item[2]} is not in 0 .. {args.tracers - 1}")
+            walls[int(item[2])][side] = value
+        else:
+            for w in walls:
+                w[side] = value
+    return walls
 
 
 def nodal_mean(coordinates, degree, values):
@@ -285,6 +328,7 @@ def check_start_from(args):
     refused = [
         (args.problem == "taylorgreen", "--problem taylorgreen (forcing and exact solution are tied to the absolute time)"),
         (args.problem == "kelvinhelmholtz", "--problem kelvinhelmholtz (general meshes are not transferred)"),
+        (args.problem == "cavity", "--problem cavity (the source run is the periodic square's)"),
         (args.gpus > 1, f"--gpus {args.gpus} (the transfer is single-rank)"),
         (bool(args.restart), "--restart (a restart continues its own checkpoint)"),
         (args.warmup, "--warmup (one step from the initial condition)"),
@@ -491,6 +535,8 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.tracer_diffusivity is not None:
         kappa = args.tracer_diffusivity
         several["tracer_diffusivity"] = kappa[0] if len(kappa) == 1 else kappa
+    if args.tracer_wall:
+        several["tracer_walls"] = tracer_walls(args)
     if args.buoyancy is not None:
         several["buoyancy"] = args.buoyancy[0] if len(args.buoyancy) == 1 else args.buoyancy
         several["gravity"] = tuple(args.gravity) if args.gravity is not None else (0.0, -1.0)
@@ -570,6 +616,9 @@ def _run(args, ranks):
     if args.tracer_diffusivity is not None:
         print(f"tracer diffusivity = {' '.join(repr(x) for x in args.tracer_diffusivity)}")
         print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g} (limit {timestepper.diffusion_limit:.6g})")
+    if args.tracer_wall:
+        for t, w in enumerate(timestepper._engine.tracer_walls() or []):
+            print(f"tracer wall = tracer {t}: " + (", ".join(f"{side} {value!r}" for side, value in w.items()) or "no flux"))
     if args.viscosity is not None:
         print(f"viscosity = {args.viscosity!r}")
         print(f"wall = {args.wall or 'free_slip'}")
@@ -614,6 +663,8 @@ def _run(args, ranks):
         model_problem = DoubleLayerShearFlow(timestepper._V_Q, timestepper._V_p)  # driver.py:334-335
     elif args.problem == "kelvinhelmholtz":
         model_problem = KelvinHelmholtz(timestepper._V_Q, timestepper._V_p)  # driver.py:336-337
+    elif args.problem == "cavity":
+        model_problem = Cavity(timestepper._V_Q, timestepper._V_p)
     else:
         if args.coriolis is not None:
             model_problem = RotatingTaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa,
@@ -625,6 +676,9 @@ def _run(args, ranks):
     q_0 = (lambda x, y: np.sin(2 * np.pi * x) * np.sin(2 * np.pi * y)) if args.tracer_advection else None
     if args.tracers > 1:
         q_0 = [tracer_initial(m) for m in range(args.tracers)]
+    if args.problem == "cavity" and args.tracer_advection:  # every tracer starts from 0: the walls set it going
+        zero = lambda x, y: 0.0 * x
+        q_0 = [zero] * args.tracers if args.tracers > 1 else zero
     if args.start_from:
         Q_0, p_0, q_start = start_from(args, ranks, timestepper)
         if args.tracer_advection and q_start is not None:
@@ -668,10 +722,15 @@ def _run(args, ranks):
             half_sq = timestepper.compute_diagnostics(Q, p, q)["tracer_half_sq"]
             print(f"{q.name()}: integral = {integral!r}, half square integral = {half_sq!r}")
         print()
+    if args.tracer_wall:
+        sides = ("boundary",) if args.problem == "kelvinhelmholtz" else WALL_SIDES
+        for t, row in enumerate(eng.tracer_wall_flux()):
+            print(f"tracer wall flux = tracer {t}: " + ", ".join(f"{side} {float(row[w])!r}" for w, side in enumerate(sides)))
+        print()
     log_summary()
     print(f"state digest = {state_digest[0]:016x}{state_digest[1]:016x}")
     print()
-    if args.problem in ("shear", "kelvinhelmholtz"):
+    if args.problem in ("shear", "kelvinhelmholtz", "cavity"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here
         # with an AttributeError); write the final fields
         if args.output:

@@ -129,6 +129,27 @@ class KelvinHelmholtz:
         return None
 
 
+class Cavity:
+    """A closed box of fluid at rest: zero velocity, zero pressure, zero forcing; what moves it is the
+    buoyancy of tracers held at fixed values on the walls (the differentially heated cavity, Rayleigh-Benard convection in a
+    box).  No exact solution."""
+
+    def __init__(self, V_Q, V_p):
+        self.V_Q, self.V_p = V_Q, V_p
+        self.Q_initial = lambda x, y: (0.0 * x, 0.0 * y)
+        self.p_initial = lambda x, y: 0.0 * x
+
+    def initial_condition(self):
+        return self.Q_initial, self.p_initial
+
+    def f_rhs(self):
+        """Zero forcing."""
+        return None
+
+    def solution(self, t, integrate_pressure=None):
+        return None
+
+
 class DoubleLayerShearFlow:
     """Double layer shear flow (model_problems.py:134-196; Guzman, Shu, Sequeira, IMA J. Numer. Anal. 37 (2017)) on the
     periodic square [0, 2 pi]^2: two tanh shear layers of width rho perturbed by a vertical velocity of magnitude delta;

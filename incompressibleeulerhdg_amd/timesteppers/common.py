@@ -136,6 +136,9 @@ class IncompressibleEuler(ABC):
         self._label = label
         # tracer_diffusivity=: kappa of every tracer (a scalar or n_tracers values); None: no call at all
         self._tracer_diffusivity = engine_options.pop("tracer_diffusivity", None)
+        # tracer_walls=: fixed-value walls of the tracers, a dict {side: value} or n_tracers of them;
+        # None: no call at all
+        self._tracer_walls = engine_options.pop("tracer_walls", None)
         # buoyancy=, gravity=: beta of every tracer (a scalar or n_tracers values) and g of the Boussinesq term + sum_t beta_t q_t g
         # (DESIGN.md section 20); None: no call at all.  Set once the tracers are (Engine.set_buoyancy needs them).
         self._buoyancy = engine_options.pop("buoyancy", None)
@@ -178,6 +181,11 @@ class IncompressibleEuler(ABC):
             V._engine = self._engine  # device operations on a Function (vorticity callback)
         self._V_trace = ("DGT", k, self._engine.n_edges * self._engine.n_l)
         self._V = (self._V_Q, self._V_p, self._V_trace)
+        if self._tracer_walls is not None:  # before the diffusion number is read: Lambda then counts the wall blocks
+            self._engine.set_tracer_walls(self._tracer_walls)
+            if self._tracer_diffusivity is None or not np.any(np.asarray(self._tracer_diffusivity, dtype=float) != 0.0):
+                warnings.warn("tracer_walls= without a non-zero tracer_diffusivity=: a fixed wall value acts through the "
+                              "diffusion term only, so the walls do nothing", RuntimeWarning, stacklevel=3)
         if self._tracer_diffusivity is not None:
             self._engine.set_tracer_diffusivity(self._tracer_diffusivity)
             self.diffusion_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
