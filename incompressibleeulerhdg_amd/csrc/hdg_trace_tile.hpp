@@ -13,9 +13,12 @@
 // work into them bought 1-2 %.  Here a workgroup owns a tile of TW x TH grid corners, keeps the
 // stencil inputs of every stage in LDS with a halo that shrinks by one corner per operator application (2 for the pre
 // kernel, 3 for the post kernel: recomputed, not exchanged) and walks through the stages between barriers -- the scheme
-// of the vertex-grid kernels k_p1_down / k_p1_up.  Values a stage only needs pointwise (r, r0, z1) stay in registers: one
-// thread keeps the same corners through all stages (the index map of the halo-2 region; stages that act on a smaller region
-// mask the rest).
+// of the vertex-grid kernels k_p1_down / k_p1_up.  One thread keeps the same corners through all stages (the index map of
+// the halo-2 region; stages that act on a smaller region mask the rest).  The post kernel holds every value ONCE: only r / r0,
+// which no LDS array has, crosses a barrier in registers.  d0 lives in Ds and z0 in Zs; the stage that needs them pointwise
+// reads them back at the thread's own slot (d0 is own[] of the stencil read it does anyway), and z1 = z0 + d0 is formed
+// where it is consumed.  Held in registers as well (36 VGPRs at k = 2) they kept it at 157 VGPRs, three workgroups per CU;
+// without them it fits four.  The pre kernel keeps r and d0 in registers (four workgroups per CU either way).
 //
 // Same arithmetic per corner as trace_stencil / k_trace_smooth.  Round 4: strips as well, and the doubly periodic square
 // (corner_info: wrapped columns; in y a strip whose ghost rows are its own opposite rows).  A launch
@@ -38,7 +41,9 @@ struct TraceTile {
   // to 4 waves per SIMD 90 / 188 (spills).  The five row-stencil launches they replace: 60 + 37 and 97 + 78 + 37.
   static constexpr int TW = 16, TH = 8, NTHREADS = 256;
   static constexpr int W2 = TW + 4, H2 = TH + 4, N2 = W2 * H2;  // halo-2 region: the index map of every stage
-  static constexpr int WPE_POST = K == 1 ? 4 : (K == 2 ? 3 : (K == 3 ? 2 : 1));  // waves per SIMD the post kernel is held to (with the inner products too)
+  // waves per SIMD the post kernel is held to (with the inner products too): the step its registers reach without scratch and
+  // its LDS fits (k = 1, 2, 3: 87 / 123 / 159 VGPRs; 5 x 26464, 4 x 39616, 3 x 52768 B of the CU's 160 KiB)
+  static constexpr int WPE_POST = K == 1 ? 5 : (K == 2 ? 4 : (K == 3 ? 3 : 1));
   static constexpr int W3 = TW + 6, H3 = TH + 6, N3 = W3 * H3;  // halo-3 region (post kernel, stage 0)
   static constexpr int W1 = TW + 2, H1 = TH + 2, N1 = W1 * H1;  // halo-1 region
   static constexpr int KMAX = (N2 + NTHREADS - 1) / NTHREADS;   // corners per thread
@@ -186,7 +191,8 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) void k_trace_pre_tile(int n
   HDG_TILE_OF_BLOCK
   const int i0 = tile_x * TW, j0 = tr.jlo + tile_y * TH;
   double rr[KMAX][NT], dd[KMAX][NT];
-  // stage 1: d0 = c0 Dinv r on the halo-2 region (pointwise); r and d0 of this thread's corners stay in registers
+  // stage 1: d0 = c0 Dinv r on the halo-2 region (pointwise); r and d0 of this thread's corners stay in registers (d0 taken
+  // from the stencil's own[] as in the post kernel stops short of the five-wave step and is no faster: DESIGN.md section 9)
 #pragma unroll
   for (int k = 0; k < KMAX; k++) {
     const int idx = threadIdx.x + k * TT::NTHREADS;
@@ -299,7 +305,7 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
   }
   // r of this thread's stage-1 corners: requested BEFORE the barrier, so that the loads travel together with those of stage 0
   // (the compiler does not move a load across s_barrier; behind it the round trip was exposed once more per workgroup)
-  double r0[KMAX][NT], z1[KMAX][NT], d0[KMAX][NT];
+  double r0[KMAX][NT];
 #pragma unroll
   for (int k = 0; k < KMAX; k++) {
     const int idx = threadIdx.x + k * TT::NTHREADS;
@@ -310,7 +316,7 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
   }
   __syncthreads();
   double dots[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // (z,n), (z,r), (z,z), (z,w), (n,r) of this thread's tile corners
-  // stage 1 on the halo-2 region: r0 = r - T z0, d0 = c0 Dinv r0, z1 = z0 + d0
+  // stage 1 on the halo-2 region: r0 = r - T z0, d0 = c0 Dinv r0 (to Ds only; z1 = z0 + d0 is formed in stage 2)
 #pragma unroll
   for (int k = 0; k < KMAX; k++) {
     const int idx = threadIdx.x + k * TT::NTHREADS;
@@ -318,8 +324,9 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
       const int lj = idx / W2, li = idx - lj * W2;
       const int jc = j0 - 2 + lj;
       const CornerInfo c = corner_info(g, tr, i0 - 2 + li, jc);
+      double d0[NT];
 #pragma unroll
-      for (int q = 0; q < NT; q++) z1[k][q] = d0[k][q] = 0.0;  // (r0 holds r: zeros where the corner or an edge does not exist)
+      for (int q = 0; q < NT; q++) d0[q] = 0.0;  // (r0 holds r: zeros where the corner or an edge does not exist)
       if (c.exists) {
         double own[NT], y[3][NL];
         lds_trace_stencil<K, W3, H3>(Zs, li + 1, lj + 1, c.in_x, c.in_y, c.below, c.left, T, own, y[0], y[1], y[2]);
@@ -329,16 +336,18 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
           r0[k][NL + m] -= y[2][m];
           r0[k][2 * NL + m] -= y[1][m];
         }
-        corner_dinv<NL>(T, c, c0, r0[k], d0[k]);
-#pragma unroll
-        for (int q = 0; q < NT; q++) z1[k][q] = own[q] + d0[k][q];
+        corner_dinv<NL>(T, c, c0, r0[k], d0);
       }
 #pragma unroll
-      for (int q = 0; q < NT; q++) Ds[(plane_of<NL>(q) * H2 + lj) * W2 + li] = d0[k][q];
+      for (int q = 0; q < NT; q++) Ds[(plane_of<NL>(q) * H2 + lj) * W2 + li] = d0[q];
     }
   }
   __syncthreads();
-  // stage 2 on the halo-1 region: r1 = r0 - T d0, d1 = c1 d0 + c2 Dinv r1, z2 = z1 + d1 (stored over z0, which is dead)
+  // stage 2 on the halo-1 region: z1 = z0 + d0, r1 = r0 - T d0, d1 = c1 d0 + c2 Dinv r1, z2 = z1 + d1 (stored over z0, which is
+  // dead).  d0 of the corner is own[] of the Ds stencil and z0 the corner's own slot of Zs, which only this thread writes
+  // in this stage and no thread reads before the next barrier.  An entry of an edge that does not exist is +0.0 in both
+  // arrays: stage 0 stores the zero load_corner gives and prolongs onto existing edges only, and corner_dinv maps the zero
+  // of r0 there to +0.0 (Dinv is block diagonal over the edges) -- the same values the masks of the stencil give.
 #pragma unroll
   for (int k = 0; k < KMAX; k++) {
     const int idx = threadIdx.x + k * TT::NTHREADS;
@@ -361,7 +370,10 @@ __global__ __launch_bounds__(TraceTile<K>::NTHREADS) __attribute__((amdgpu_waves
           }
           corner_dinv<NL>(T, c, c2, r1, zz);
 #pragma unroll
-          for (int q = 0; q < NT; q++) z2[q] = z1[k][q] + fma(c1, d0[k][q], zz[q]);
+          for (int q = 0; q < NT; q++) {
+            const double z1 = Zs[(plane_of<NL>(q) * H3 + (lj + 1)) * W3 + (li + 1)] + own[q];
+            z2[q] = z1 + fma(c1, own[q], zz[q]);
+          }
         }
 #pragma unroll
         for (int q = 0; q < NT; q++) Zs[(plane_of<NL>(q) * H3 + (lj + 1)) * W3 + (li + 1)] = z2[q];
