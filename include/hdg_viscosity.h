@@ -14,7 +14,7 @@
  *             + sum_{wall e}     int_e ( (w.t)(t.dn u) + (u.t)(t.dn w) - eta_b (w.t)(u.t) )     tangential: no slip only
  *   [v] = v+ - v-, {g} = (g+ + g-)/2, dn u = (grad u) n, n out of the '+' cell (out of the domain on a wall), t normal to n
  *   eta_e = (p+1)(p+2)/4 max(P_K+/|K+|, P_K-/|K-|),  eta_b = (p+1)(p+2)/2 P_K/|K|            (P = perimeter)
- * Wall data is homogeneous.  The term is explicit, like the forcing: wherever the scheme uses the forcing slot b_rhs[j] it uses
+ * Wall data is homogeneous unless include/hdg_moving_walls.h gives the no-slip walls a speed.  The term is explicit, like the forcing: wherever the scheme uses the forcing slot b_rhs[j] it uses
  * b_rhs[j] + B(q^(j)) + nu M^-1 V Q^(j), Q^(j) the stage velocity of slot j (slot 0: Q_n; slot s, the pressure reconstruction:
  * Q_{n+1}); the two implicit steppers take Q_n (forward Euler).  So nu dt rho(M^-1 V) has to lie inside the real-axis stability
  * interval of the explicit tableau.  The slots are filled inside the solves that read them: no new call in a time loop.

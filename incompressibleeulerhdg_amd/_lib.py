@@ -22,6 +22,7 @@ BUOYANCY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_buo
 VISCOSITY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_viscosity.h"))
 CORIOLIS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_coriolis.h"))
 TRACER_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_walls.h"))
+MOVING_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_moving_walls.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -94,7 +95,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -235,6 +236,30 @@ TRACER_WALL_SIGNATURES = {
 }
 WALL_SIDES = ("bottom", "right", "top", "left")  # the sides of the structured unit square, in the order of the C-ABI
 
+# moving no-slip walls and the wall force: the symbols include/hdg_moving_walls.h declares, in a table of their own like the seven above
+MOVING_WALL_SIGNATURES = {
+    "hdg_set_wall_velocity": [_h, _dp],
+    "hdg_get_wall_velocity": [_h, _dp],
+    "hdg_get_wall_force": [_h, _dp],
+    "hdg_apply_moving_walls": [_h, C.c_int, _dp, _dp, _dp],
+    "hdg_apply_wall_force": [_h, C.c_int, _dp, _dp, _dp],
+}
+
+
+def wall_velocity_array(v):
+    """{side: speed} (a missing side stands still) or four values in the order bottom, right, top, left -> (4,) float64"""
+    if isinstance(v, dict):
+        out = np.zeros(4)
+        for side, u in v.items():
+            if side not in WALL_SIDES:
+                raise ValueError(f"unknown wall side {side!r}; one of {', '.join(WALL_SIDES)}")
+            out[WALL_SIDES.index(side)] = float(u)
+        return out
+    out = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    if out.shape != (4,):
+        raise ValueError(f"wall_velocity must be a dict {{side: speed}} or four values (got {out.size})")
+    return out
+
 
 def wall_code(wall):
     """'free_slip' / 'no_slip' -> the integer of include/hdg_viscosity.h"""
@@ -256,7 +281,7 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
-            list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()):
+            list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -665,6 +690,43 @@ class Engine:
         out = np.empty(self.shape_Q)
         self._ck(self.lib.hdg_apply_viscosity(self.h, wall_code(wall), _ptr(Q), _ptr(out)))
         return out
+
+    # --- moving no-slip walls and the wall force (include/hdg_moving_walls.h)
+    def set_wall_velocity(self, v):
+        """Constant tangential speeds of the no-slip walls of the structured unit square: a dict such as {"top": 1.0} (a
+        missing side stands still) or four values in the order bottom, right, top, left; the wall's u_x on bottom and top, its
+        u_y on left and right.  None or zeros: off.  Needs set_viscosity(nu, "no_slip") before.  On a strip partition every
+        rank has to pass the same speeds."""
+        self._ck(self.lib.hdg_set_wall_velocity(self.h, None if v is None else _ptr(wall_velocity_array(v))))
+
+    def wall_velocity(self):
+        """The four speeds as they are set, in the order bottom, right, top, left."""
+        U = np.zeros(4)
+        self._ck(self.lib.hdg_get_wall_velocity(self.h, _ptr(U)))
+        return U
+
+    def wall_force(self):
+        """(4, 2): the viscous force on the fluid through every side (bottom, right, top, left) of the current velocity, with
+        the nu, wall mode and speeds that are set; free slip gives the normal part only.  The pressure force is not in it."""
+        F = np.zeros((4, 2))
+        self._ck(self.lib.hdg_get_wall_force(self.h, _ptr(F)))
+        return F
+
+    def apply_moving_walls(self, Q, wall_velocity, wall="no_slip"):
+        """M^-1 (V Q + l(U)) of a nodal velocity-space field, without nu (test hook; it sets nothing)."""
+        Q = _arr(Q, self.shape_Q)
+        out = np.empty(self.shape_Q)
+        U = None if wall_velocity is None else wall_velocity_array(wall_velocity)
+        self._ck(self.lib.hdg_apply_moving_walls(self.h, wall_code(wall), _ptr(U), _ptr(Q), _ptr(out)))
+        return out
+
+    def wall_force_of(self, Q, wall_velocity, wall="no_slip"):
+        """(4, 2): the force functionals of a nodal velocity-space field, without nu (test hook; it sets nothing)."""
+        Q = _arr(Q, self.shape_Q)
+        F = np.zeros((4, 2))
+        U = None if wall_velocity is None else wall_velocity_array(wall_velocity)
+        self._ck(self.lib.hdg_apply_wall_force(self.h, wall_code(wall), _ptr(U), _ptr(Q), _ptr(F)))
+        return F
 
     # --- Coriolis term (include/hdg_coriolis.h; DESIGN.md section 22)
     def set_coriolis(self, f0, beta=0.0):

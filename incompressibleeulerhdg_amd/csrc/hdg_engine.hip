@@ -35,6 +35,7 @@
 #include "../../include/hdg_buoyancy.h"
 #include "../../include/hdg_viscosity.h"
 #include "../../include/hdg_coriolis.h"
+#include "../../include/hdg_moving_walls.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -55,6 +56,7 @@
 #include "hdg_general_kernels.hpp"
 #include "hdg_buoyancy.hpp"
 #include "hdg_viscosity.hpp"
+#include "hdg_wall_force.hpp"
 #include "hdg_coriolis.hpp"
 #include "hdg_tracer_walls.hpp"
 #include "hdg_amg.hpp"
@@ -3868,7 +3870,8 @@ struct Engine {
       visc_lambda[wall] = lam;
     } else {
       const ViscosityTables V(K, g.h);
-      if (!d_visctab) d_visctab = upload(V.packed());
+      if (!d_visctab) d_visctab = upload(V.packed_moving());  // packed(), then the load vectors of moving walls (section 24)
+      visc_wone = V.wone;
       visc_lambda[0] = visc_lambda[1] = V.lambda;
     }
   }
@@ -3886,6 +3889,7 @@ struct Engine {
     if (step_open) throw std::string("hdg_set_viscosity: a step is open (between hdg_begin_step and the end of the step)");
     if (!(nu >= 0.0) || !std::isfinite(nu)) throw std::string("hdg_set_viscosity: nu = " + std::to_string(nu) + " is not a finite value >= 0");
     visc_check_wall("hdg_set_viscosity", wall);
+    if (wall != 1 && moving_on()) throw std::string("hdg_set_viscosity: a wall velocity is set (hdg_set_wall_velocity), which needs no-slip walls");
     if (nu != 0.0) {
       visc_setup(wall);
       visc_alloc();
@@ -3894,12 +3898,59 @@ struct Engine {
     visc_valid = 0;
   }
   // out = sc M^-1 V Q (owned rows); Q's ghost rows are filled here: wrapped on the periodic square, one exchange on a strip
-  void viscosity_apply(const double* Q, double sc, int wall, double* out) {
+  // U (may be NULL): the four wall speeds of section 24; with one of them != 0 the kernel that adds sc M^-1 l(U) runs instead
+  void viscosity_apply(const double* Q, double sc, int wall, double* out, const double* U = nullptr) {
     if (general) { csr(gvisc[wall], Q, sc, 0.0, out); return; }  // tallied in 'other' by csr()
     tally(LC_OTHER, 2.0 * bQ());
     stencil_in(Q, FQ);
-    by_degree([&](auto k) { k_viscosity<k()><<<cell_grid(), bs(), 0, stream>>>(g, d_visctab, sc, wall, Q, out); });
+    const WallSpeed W = wall_speed(U);
+    if (U && wall_moving(U)) by_degree([&](auto k) { k_viscosity<k(), true><<<cell_grid(), bs(), 0, stream>>>(g, d_visctab, sc, wall, Q, out, W); });
+    else by_degree([&](auto k) { k_viscosity<k(), false><<<cell_grid(), bs(), 0, stream>>>(g, d_visctab, sc, wall, Q, out, W); });
     fl.set(out, 0);
+  }
+  // ---- moving no-slip walls and the wall force: the tangential Nitsche term of the viscous form acts on
+  // u.t - U_w, U_w the constant Cartesian tangential speed of side w (bottom, right, top, left) of the structured unit square,
+  // which adds nu M^-1 l(U) to every viscous slot: k_viscosity<K, true> runs instead of the plain kernel, no launch more.
+  // Configuration like nu; on a strip every rank has to be given the same speeds (not checked).
+  double wall_u[4] = {0.0, 0.0, 0.0, 0.0};
+  double visc_wone = 0.0;  // eta_b h of the viscous form
+  double *d_wforce = nullptr, *d_wfpart = nullptr;
+  static bool wall_moving(const double* U) { return U[0] != 0.0 || U[1] != 0.0 || U[2] != 0.0 || U[3] != 0.0; }
+  static WallSpeed wall_speed(const double* U) { return U ? WallSpeed{U[0], U[1], U[2], U[3]} : WallSpeed{0.0, 0.0, 0.0, 0.0}; }
+  bool moving_on() const { return wall_moving(wall_u); }
+  // throws unless the speeds U (NULL: none) are admissible on this mesh in the wall mode `wall`; general meshes are refused by
+  // the entry points before (HDG_ERR_UNSUPPORTED)
+  void check_wall_velocity(const char* who, const double* U, int wall) const {
+    if (step_open) throw std::string(who) + ": a step is open (between hdg_begin_step and the end of the step)";
+    if (!U) return;
+    for (int w = 0; w < 4; w++)
+      if (!std::isfinite(U[w])) throw std::string(who) + ": side " + std::to_string(w) + " (" + wall_side_name(false, w) + "): the speed " + std::to_string(U[w]) + " is not finite";
+    if (!wall_moving(U)) return;
+    if (periodic) throw std::string(who) + ": the doubly periodic square has no walls";
+    if (wall != 1) throw std::string(who) + ": a wall velocity needs no-slip walls (HDG_WALL_NO_SLIP)";
+  }
+  void set_wall_velocity(const double* U) {
+    check_wall_velocity("hdg_set_wall_velocity", U, visc_wall);
+    for (int w = 0; w < 4; w++) wall_u[w] = U ? U[w] : 0.0;
+    visc_valid = 0;
+  }
+  int wall_force_blocks() const { return (std::max(g.nx, g.ny) + HDG_WALL_FORCE_BLOCK - 1) / HDG_WALL_FORCE_BLOCK; }
+  // F[2 w + c] = sc * (the force functional of section 24) of the modal field Q in the wall mode `wall` with the speeds U;
+  // on a strip the eight values are added over the ranks, so every rank returns the same
+  void wall_force(const double* Q, double sc, int wall, const double* U, double* F) {
+    std::fill(F, F + 8, 0.0);
+    if (periodic) return;  // no walls
+    visc_setup(wall);
+    const int nblk = wall_force_blocks();
+    if (!d_wforce) { d_wforce = dalloc(8); d_wfpart = dalloc(8L * nblk); }
+    const WallSpeed W = wall_speed(U);
+    tally(LC_OTHER, 0.0);
+    tally(LC_OTHER, 0.0);
+    by_degree([&](auto k) { k_wall_force<k()><<<dim3(nblk, 4), HDG_WALL_FORCE_BLOCK, 0, stream>>>(g, d_visctab, wall, visc_wone, W, Q, d_wfpart); });
+    k_wall_force_finish<<<1, 64, 0, stream>>>(nblk, g.nx, g.ny, sc, d_wfpart, d_wforce);
+    if (comm->size > 1) comm->allreduce_sum(d_wforce, 8, stream);
+    HIPCHECK(hipMemcpyAsync(F, d_wforce, sizeof(double) * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
   }
   void viscosity_slot(int j, const double* Q) {
     if (visc_step && (visc_valid >> j & 1u)) return;
@@ -3973,7 +4024,7 @@ struct Engine {
   }
   // the velocity-linear part of a slot: out = nu M^-1 V Q + M^-1 C Q, whichever of the two is on
   void vel_linear_apply(const double* Q, double* out) {
-    if (viscosity_on()) viscosity_apply(Q, visc_nu, visc_wall, out);
+    if (viscosity_on()) viscosity_apply(Q, visc_nu, visc_wall, out, wall_u);
     if (coriolis_on()) coriolis_apply(Q, cor_f0, cor_beta, viscosity_on(), out);
   }
   // F = max over the mesh vertices of |f0 + beta y|, an upper bound of rho(M^-1 C); f_c is linear, so on the structured meshes
@@ -4542,6 +4593,8 @@ struct Engine {
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
     if (coriolis_on()) { f.add("coriolis_f0", cor_f0); f.add("coriolis_beta", cor_beta); }  // only with one of them != 0
+    for (int w = 0; w < 4; w++)  // one line per side with a wall speed, and only then
+      if (wall_u[w] != 0.0) f.add("wall_velocity[" + std::to_string(w) + "]", wall_u[w]);
     if (general) {
       f.add("n_vertices", (long)ck_mesh_nv); f.add("n_cells", (long)ck_mesh_nc);
       f.add_u64("coords_d0", ck_mesh_coords.d0); f.add_u64("coords_d1", ck_mesh_coords.d1);
@@ -5682,6 +5735,62 @@ int hdg_apply_viscosity(hdg_handle* h, int wall, const double* Q, double* out) {
   E.zero(E.wQ2, E.NQ);
   E.viscosity_apply(E.wQ1, 1.0, wall, E.wQ2);
   E.get_Q(E.wQ2, out);
+  HDG_API_END(h)
+}
+
+// ---- moving no-slip walls and the wall force (include/hdg_moving_walls.h)
+// a general mesh has no sides to name: speeds other than zero, and the force, are HDG_ERR_UNSUPPORTED there; 0: go on
+static int moving_walls_gate(hdg_handle* h, const char* call, const double* U, bool force) {
+  if (!h || !h->eng) return HDG_ERR_ARG;
+  if (!h->eng->general) return HDG_OK;
+  if (force) { h->err = std::string(call) + ": general meshes are not supported (the structured unit square only)"; return HDG_ERR_UNSUPPORTED; }
+  if (U && !(U[0] == 0.0 && U[1] == 0.0 && U[2] == 0.0 && U[3] == 0.0)) {
+    h->err = std::string(call) + ": a wall velocity on a general mesh is not supported (the structured unit square only)";
+    return HDG_ERR_UNSUPPORTED;
+  }
+  return HDG_OK;
+}
+int hdg_set_wall_velocity(hdg_handle* h, const double U[4]) {
+  if (const int rc = moving_walls_gate(h, "hdg_set_wall_velocity", U, false)) return rc;
+  HDG_API_BEGIN(h)
+  E.set_wall_velocity(U);
+  HDG_API_END(h)
+}
+int hdg_get_wall_velocity(hdg_handle* h, double U[4]) {
+  HDG_API_BEGIN(h)
+  if (!U) throw std::string("null argument");
+  for (int w = 0; w < 4; w++) U[w] = E.wall_u[w];
+  HDG_API_END(h)
+}
+int hdg_get_wall_force(hdg_handle* h, double F[8]) {
+  if (const int rc = moving_walls_gate(h, "hdg_get_wall_force", nullptr, true)) return rc;
+  HDG_API_BEGIN(h)
+  if (!F) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_get_wall_force: a step is open");
+  E.wall_force(E.curQ, E.visc_nu, E.visc_wall, E.wall_u, F);
+  HDG_API_END(h)
+}
+int hdg_apply_moving_walls(hdg_handle* h, int wall, const double U[4], const double* Q, double* out) {
+  if (const int rc = moving_walls_gate(h, "hdg_apply_moving_walls", U, false)) return rc;
+  HDG_API_BEGIN(h)
+  if (!Q || !out) throw std::string("null argument");
+  hdg::Engine::visc_check_wall("hdg_apply_moving_walls", wall);
+  E.check_wall_velocity("hdg_apply_moving_walls", U, wall);
+  E.visc_setup(wall);
+  E.put_Q(Q, E.wQ1);
+  E.zero(E.wQ2, E.NQ);
+  E.viscosity_apply(E.wQ1, 1.0, wall, E.wQ2, U);
+  E.get_Q(E.wQ2, out);
+  HDG_API_END(h)
+}
+int hdg_apply_wall_force(hdg_handle* h, int wall, const double U[4], const double* Q, double F[8]) {
+  if (const int rc = moving_walls_gate(h, "hdg_apply_wall_force", U, true)) return rc;
+  HDG_API_BEGIN(h)
+  if (!Q || !F) throw std::string("null argument");
+  hdg::Engine::visc_check_wall("hdg_apply_wall_force", wall);
+  E.check_wall_velocity("hdg_apply_wall_force", U, wall);
+  E.put_Q(Q, E.wQ1);
+  E.wall_force(E.wQ1, 1.0, wall, U, F);
   HDG_API_END(h)
 }
 

@@ -795,13 +795,19 @@ struct ViscosityTables {
   int k, nu;
   double h, eta, eta_b, lambda;
   dvec Vol[2], Own[2][3], Nbr[2][3], Wall[2][3];  // Wall[s][1] stays empty
+  // moving no-slip walls, leg edges e = 0 and 2 only: lvec[s][e][r] = int_e ( eta_b psi_r - dn psi_r ),
+  // the load of a wall that moves along itself at unit speed; Wall[s][e] coef(1) = - lvec[s][e].  wone = eta_b h = int_e eta_b.
+  dvec lvec[2][3];
+  double wone;
   static int wall_normal_component(int e) { return e == 0 ? 1 : 0; }
+  // the side of the unit square (bottom, right, top, left) a leg edge (s, e) can lie on, as TracerDiffusionTables::wall_side
+  static int wall_side(int s, int e) { return s == 0 ? (e == 0 ? 0 : 3) : (e == 0 ? 2 : 1); }
 
   ViscosityTables(int k_, double h_) : k(k_), nu(n_scalar(k_ + 1)), h(h_) {
     const int p = k + 1;
     const real rh = h, s2 = std::sqrt((real)2);
     const real eta_ = (real)(p + 1) * (p + 2) / 4 * 2 * (2 + s2) / rh, etab_ = 2 * eta_;
-    eta = (double)eta_; eta_b = (double)etab_;
+    eta = (double)eta_; eta_b = (double)etab_; wone = (double)(etab_ * rh);
     const real nfix[3][2] = {{0, 1}, {1 / s2, 1 / s2}, {1, 0}};
     const real sg[2][3] = {{-1, 1, -1}, {1, -1, 1}}, elen_[3] = {rh, s2 * rh, rh};
     Dubiner U(p);
@@ -838,7 +844,7 @@ struct ViscosityTables {
       const real sgn = s == 0 ? 1 : -1;
       for (int e = 0; e < 3; e++) {
         const real nx = sg[s][e] * nfix[e][0], ny = sg[s][e] * nfix[e][1];  // this cell's outward normal
-        std::vector<real> O((size_t)nu * nu, 0), N((size_t)nu * nu, 0), W((size_t)nu * nu, 0);
+        std::vector<real> O((size_t)nu * nu, 0), N((size_t)nu * nu, 0), W((size_t)nu * nu, 0), lv(nu, 0);
         for (int q = 0; q < nqe; q++) {
           real xi, et;
           edge_ref(s, e, tq[q], xi, et);
@@ -848,16 +854,18 @@ struct ViscosityTables {
           U.eval(xi, et, vn.data(), nx_.data(), ny_.data());
           for (int m = 0; m < nu; m++) { vn[m] /= rh; dnn[m] = -sgn * (nx * nx_[m] + ny * ny_[m]) / (rh * rh); }
           const real w = wq[q] * elen_[e];
-          for (int r = 0; r < nu; r++)
+          for (int r = 0; r < nu; r++) {
             for (int m = 0; m < nu; m++) {
               O[(size_t)r * nu + m] += w * (val[r] * dno[m] / 2 + val[m] * dno[r] / 2 - eta_ * val[r] * val[m]);
               N[(size_t)r * nu + m] += w * (val[r] * dnn[m] / 2 - vn[m] * dno[r] / 2 + eta_ * val[r] * vn[m]);
               W[(size_t)r * nu + m] += w * (val[r] * dno[m] + val[m] * dno[r] - etab_ * val[r] * val[m]);
             }
+            lv[r] += w * (etab_ * val[r] - dno[r]);
+          }
         }
         Own[s][e].assign(O.begin(), O.end());
         Nbr[s][e].assign(N.begin(), N.end());
-        if (e != 1) Wall[s][e].assign(W.begin(), W.end());
+        if (e != 1) { Wall[s][e].assign(W.begin(), W.end()); lvec[s][e].assign(lv.begin(), lv.end()); }
       }
     }
     lambda = 0.0;
@@ -895,6 +903,13 @@ struct ViscosityTables {
       put(Wall[s][0]);
       put(Wall[s][2]);
     }
+    return out;
+  }
+  // device layout with moving walls: packed(), then lvec[0][0], lvec[0][2], lvec[1][0], lvec[1][2] (nu doubles each)
+  dvec packed_moving() const {
+    dvec out = packed();
+    for (int s = 0; s < 2; s++)
+      for (int e = 0; e < 3; e += 2) out.insert(out.end(), lvec[s][e].begin(), lvec[s][e].end());
     return out;
   }
 };

@@ -13,14 +13,21 @@
 // wave the compiler kept a second copy of the accumulator (174 VGPRs at k = 4 against 92).  An interior wave runs seven
 // blocks, a wave that touches a wall nine; a neighbour is read only where there is one.
 // No LDS, no scratch.  Owned rows only; the caller has filled the ghost rows of u (Engine::stencil_in).
+//
+// Moving no-slip walls: MOVING = true runs instead of the plain kernel while a wall speed is set.  The
+// tangential Nitsche term then acts on u.t - U_w, which adds U_w lvec[s][e] (ViscosityTables::packed_moving: four vectors behind
+// the nine blocks) to the tangential component of a cell at a wall, inside the wall branch and before the scaling by nu.  The
+// side w follows from (s, e), both uniform over a workgroup, so the speed is a scalar select among the four kernel arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace hdg {
 
-template <int K>
+struct WallSpeed { double bottom, right, top, left; };  // the Cartesian tangential speed of every side, in the order of the C-ABI
+
+template <int K, bool MOVING>
 __global__ __launch_bounds__(128) void k_viscosity(Geo g, const double* __restrict__ tab, double nu, int no_slip,
-                                                   const double* __restrict__ u, double* __restrict__ out) {
+                                                   const double* __restrict__ u, double* __restrict__ out, WallSpeed W) {
   constexpr int NU = Dim<K>::NU, BL = NU * NU;
   HDG_CELL_PROLOGUE
   const double* __restrict__ T = tab + (long)s * 9 * BL;
@@ -55,8 +62,19 @@ __global__ __launch_bounds__(128) void k_viscosity(Geo g, const double* __restri
       apply(T + (1 + e) * BL, lane_b, has, has);
       apply(T + (4 + e) * BL, has ? (unsigned)cn * 16u : lane_b, has, has);
     }
-    if (e != 1 && __builtin_amdgcn_ballot_w64(!has) != 0)  // a wall: horizontal (e = 0, normal along y) or vertical (e = 2, normal along x)
+    if (e != 1 && __builtin_amdgcn_ballot_w64(!has) != 0) {  // a wall: horizontal (e = 0, normal along y) or vertical (e = 2, normal along x)
       apply(T + (e == 0 ? 7 : 8) * BL, lane_b, !has && (no_slip || e == 2), !has && (no_slip || e == 0));
+      if constexpr (MOVING) {
+        const double* __restrict__ lv = tab + 2 * 9 * BL + (2 * s + (e == 0 ? 0 : 1)) * NU;
+        const double side_u = s == 0 ? (e == 0 ? W.bottom : W.left) : (e == 0 ? W.top : W.right);
+        const double uw = (!has && no_slip) ? side_u : 0.0;
+#pragma unroll
+        for (int r = 0; r < NU; r++) {
+          if (e == 0) F[r].x = fma(uw, lv[r], F[r].x);
+          else F[r].y = fma(uw, lv[r], F[r].y);
+        }
+      }
+    }
   }
 #pragma unroll
   for (int r = 0; r < NU; r++) O.st(pair_bytes(r, g.Nc), lane_b, hdg_d2{nu * F[r].x, nu * F[r].y});

@@ -14,6 +14,10 @@ tracers at fixed values on wall sides, e.g. a heated cavi
 ``--problem cavity --tracer_advection --tracer_diffusivity K --viscosity NU --wall no_slip --buoyancy 1 --tracer_wall left 0.5
 --tracer_wall right -0.5``.  The wall flux of every tracer and side is printed at the end.
 
+``--wall_velocity SIDE U`` moves a no-slip wall along itself at the constant speed U; the viscous force
+through every side is printed at the end.  The lid-driven cavity at Re = 100:
+``--problem cavity --viscosity 1e-2 --wall no_slip --wall_velocity top 1``.
+
 ``--particles FILE`` advects Lagrangian particles through the two structured problems on the device
 and writes their positions to ``--particle_output`` (``particles.npz``).
 
@@ -99,6 +103,10 @@ def build_parser():
                              "viscous diffusion number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
     parser.add_argument("--wall", choices=["free_slip", "no_slip"], default=None,
                         help="walls of the viscous term (with --viscosity; default free_slip)")
+    parser.add_argument("--wall_velocity", metavar=("SIDE", "U"), nargs=2, action="append", default=None,
+                        help="SIDE U: the no-slip wall SIDE (bottom, right, top, left) of the unit square moves along itself at the "
+                             "constant speed U (repeatable; with --viscosity and --wall no_slip); the viscous force through every "
+                             "side is printed at the end")
     parser.add_argument("--coriolis", metavar="F", type=float, nargs="+", default=None,
                         help="rotation F0 [BETA]: the momentum equation gains - (F0 + BETA y) k x u, explicit in time (see the "
                              "printed rotation number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
@@ -272,6 +280,31 @@ def check_viscosity(args):
         raise RuntimeError("--wall needs --viscosity")
     if args.viscosity is not None and not (np.isfinite(args.viscosity) and args.viscosity >= 0):
         raise RuntimeError(f"--viscosity {args.viscosity} is not a finite number >= 0")
+
+
+def wall_velocity(args):
+    """--wall_velocity SIDE U (repeatable) -> {side: speed}, or None without the flag; refuses what the engine would, before
+    any engine exists."""
+    if not args.wall_velocity:
+        return None
+    if args.viscosity is None or args.wall != "no_slip":
+        raise RuntimeError("--wall_velocity needs --viscosity and --wall no_slip")
+    if args.problem == "shear":
+        raise RuntimeError("--wall_velocity: the doubly periodic square of --problem shear has no walls")
+    if args.problem == "kelvinhelmholtz":
+        raise RuntimeError("--wall_velocity: the disk of --problem kelvinhelmholtz is a general mesh (the structured unit square only)")
+    speeds = {}
+    for side, word in args.wall_velocity:
+        if side not in WALL_SIDES:
+            raise RuntimeError(f"--wall_velocity: unknown side {side!r} (one of {', '.join(WALL_SIDES)})")
+        try:
+            u = float(word)
+        except ValueError:
+            u = float("nan")
+        if not np.isfinite(u):
+            raise RuntimeError(f"--wall_velocity {side}: speed {word} is not a finite number")
+        speeds[side] = u
+    return speeds
 
 
 def coriolis_pair(args):
@@ -515,6 +548,7 @@ def main(argv=None):
     check_particles(args)
     check_tracers(args)
     check_viscosity(args)
+    wall_velocity(args)
     check_coriolis(args)
     check_checkpoint(args)
     check_start_from(args)
@@ -543,6 +577,8 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.viscosity is not None:
         several["viscosity"] = args.viscosity
         several["wall"] = args.wall or "free_slip"
+    if args.wall_velocity:
+        several["wall_velocity"] = wall_velocity(args)
     if args.coriolis is not None:
         several["coriolis"] = coriolis_pair(args)
     if args.discretisation == "dg":
@@ -623,6 +659,8 @@ def _run(args, ranks):
         print(f"viscosity = {args.viscosity!r}")
         print(f"wall = {args.wall or 'free_slip'}")
         print(f"viscous diffusion number = {timestepper._engine.viscosity_number()[1]:.6g} (limit {timestepper.viscosity_limit:.6g})")
+    if args.wall_velocity:
+        print("wall velocity = " + ", ".join(f"{side} {float(u)!r}" for side, u in zip(WALL_SIDES, timestepper._engine.wall_velocity()) if u != 0.0))
     if args.coriolis is not None:
         number = timestepper._engine.coriolis_number()[1]
         print(f"coriolis = {' '.join(repr(x) for x in args.coriolis)}")
@@ -726,6 +764,10 @@ def _run(args, ranks):
         sides = ("boundary",) if args.problem == "kelvinhelmholtz" else WALL_SIDES
         for t, row in enumerate(eng.tracer_wall_flux()):
             print(f"tracer wall flux = tracer {t}: " + ", ".join(f"{side} {float(row[w])!r}" for w, side in enumerate(sides)))
+        print()
+    if args.wall_velocity:
+        for side, row in zip(WALL_SIDES, eng.wall_force()):
+            print(f"wall force {side} = {float(row[0])!r} {float(row[1])!r}")
         print()
     log_summary()
     print(f"state digest = {state_digest[0]:016x}{state_digest[1]:016x}")

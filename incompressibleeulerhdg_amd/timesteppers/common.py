@@ -151,6 +151,11 @@ class IncompressibleEuler(ABC):
         self._wall = engine_options.pop("wall", None)
         if self._wall is not None and self._viscosity is None:
             raise ValueError("wall= needs viscosity=")
+        # wall_velocity=: constant tangential speeds of the no-slip walls, a dict {side: speed} or four values (DESIGN.md section
+        # 24); None: no call at all
+        self._wall_velocity = engine_options.pop("wall_velocity", None)
+        if self._wall_velocity is not None and (self._viscosity is None or self._wall != "no_slip"):
+            raise ValueError('wall_velocity= needs viscosity= and wall="no_slip"')
         # coriolis=: f0 or (f0, beta) of the explicit Coriolis term - (f0 + beta y) k x u; None: no call at all
         self._coriolis = engine_options.pop("coriolis", None)
         self._engine_options = engine_options
@@ -194,6 +199,8 @@ class IncompressibleEuler(ABC):
             self._engine.set_viscosity(self._viscosity, "free_slip" if self._wall is None else self._wall)
             self.viscosity_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
             warn_if_diffusion_unstable(self._engine.viscosity_number()[1], self.viscosity_limit, what="viscosity")
+        if self._wall_velocity is not None:  # behind the viscosity: the wall mode has to be no slip
+            self._engine.set_wall_velocity(self._wall_velocity)
         if self._coriolis is not None:  # independent of the tracers and of the viscosity
             f0, beta = (self._coriolis, 0.0) if np.ndim(self._coriolis) == 0 else self._coriolis
             self._engine.set_coriolis(f0, beta)
