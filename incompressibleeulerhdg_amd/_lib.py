@@ -23,6 +23,7 @@ VISCOSITY_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_vi
 CORIOLIS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_coriolis.h"))
 TRACER_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_walls.h"))
 MOVING_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_moving_walls.h"))
+ADAPTIVE_DT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_adaptive_dt.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -95,7 +96,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -245,6 +246,46 @@ MOVING_WALL_SIGNATURES = {
     "hdg_apply_wall_force": [_h, C.c_int, _dp, _dp, _dp],
 }
 
+# adaptive time step: the symbols include/hdg_adaptive_dt.h declares, in a table of their own like the eight above
+class hdg_step_control(C.Structure):
+    """The controller's settings; a zeroed field means its default (include/hdg_adaptive_dt.h)"""
+    _fields_ = [("cfl", C.c_double), ("dt_min", C.c_double), ("dt_max", C.c_double), ("grow", C.c_double), ("band", C.c_double),
+                ("caps", C.c_double * 3)]
+
+
+ADAPTIVE_DT_SIGNATURES = {
+    "hdg_set_dt": [_h, C.c_double],
+    "hdg_get_dt": [_h, _dp],
+    "hdg_get_step_rates": [_h, _dp],
+    "hdg_propose_dt": [_h, C.POINTER(hdg_step_control), C.c_double, C.c_double, _dp],
+    "hdg_step_proposal": [C.POINTER(hdg_step_control), C.c_double, C.c_double, C.c_double, C.c_double, _dp],
+}
+STEP_RATES = ("advection", "tracer_diffusion", "viscosity", "rotation")  # the entries of hdg_get_step_rates
+
+
+def step_control(cfl, dt_min=None, dt_max=None, grow=None, band=None, caps=None):
+    """The hdg_step_control of the given settings; None: the default of the rule (a zeroed field)"""
+    c = hdg_step_control()
+    c.cfl = float(cfl)
+    for name, v in (("dt_min", dt_min), ("dt_max", dt_max), ("grow", grow), ("band", band)):
+        setattr(c, name, 0.0 if v is None else float(v))
+    for i, v in enumerate(caps if caps is not None else ()):
+        c.caps[i] = 0.0 if v is None else float(v)
+    return c
+
+
+def step_proposal(control, A, dt, t, t_final):
+    """The rule of csrc/hdg_step_control.hpp for the rate A and the held step size dt (no engine, no launch).  Raises HDGError
+    HDG_ERR_NOT_CONVERGED when A is not finite, HDG_ERR_ARG when the proposal falls below dt_min or the control is bad."""
+    out = C.c_double()
+    rc = load_library().hdg_step_proposal(C.byref(control), float(A), float(dt), float(t), float(t_final), C.byref(out))
+    if rc == -3:
+        raise HDGError(rc, f"step proposal at t = {t!r}: velocity is not finite (rate {A!r})")
+    if rc != 0:
+        raise HDGError(rc, f"step proposal at t = {t!r}: the proposal dt = {out.value!r} is below dt_min = {control.dt_min!r}"
+                       if out.value == out.value else "step proposal: cfl must be > 0 and no field of the control negative or NaN")
+    return out.value
+
 
 def wall_velocity_array(v):
     """{side: speed} (a missing side stands still) or four values in the order bottom, right, top, left -> (4,) float64"""
@@ -281,7 +322,8 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
-            list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()):
+            list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()) + \
+            list(ADAPTIVE_DT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -727,6 +769,33 @@ class Engine:
         U = None if wall_velocity is None else wall_velocity_array(wall_velocity)
         self._ck(self.lib.hdg_apply_wall_force(self.h, wall_code(wall), _ptr(U), _ptr(Q), _ptr(F)))
         return F
+
+    # --- adaptive time step (include/hdg_adaptive_dt.h)
+    def set_dt(self, dt):
+        """Change the step size between completed steps (finite and > 0, else HDGError HDG_ERR_ARG and nothing changes).  The
+        value already held is a no-op.  On a strip partition every rank has to pass the same value."""
+        self._ck(self.lib.hdg_set_dt(self.h, float(dt)))
+
+    def get_dt(self):
+        """The step size the engine holds"""
+        dt = C.c_double()
+        self._ck(self.lib.hdg_get_dt(self.h, C.byref(dt)))
+        return dt.value
+
+    def step_rates(self):
+        """(4,) in the order of STEP_RATES: A = max_K (max nodal |u| in K) / h_K of the current velocity (diagnostics column
+        'cfl' without its dt; not finite when the velocity is not), kappa_max Lambda, nu Lambda_u and F (0 while the term is
+        off).  Collective on strips: every rank gets the global maximum."""
+        rates = np.zeros(4)
+        self._ck(self.lib.hdg_get_step_rates(self.h, _ptr(rates)))
+        return rates
+
+    def propose_dt(self, control, t, t_final):
+        """The rule of csrc/hdg_step_control.hpp applied to step_rates() and the dt held; `control`: step_control(...).  It sets
+        nothing.  HDGError HDG_ERR_NOT_CONVERGED when the velocity is not finite, HDG_ERR_ARG below dt_min."""
+        out = C.c_double()
+        self._ck(self.lib.hdg_propose_dt(self.h, C.byref(control), float(t), float(t_final), C.byref(out)))
+        return out.value
 
     # --- Coriolis term (include/hdg_coriolis.h; DESIGN.md section 22)
     def set_coriolis(self, f0, beta=0.0):

@@ -27,6 +27,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hdg_step_rate.hpp"
+
 namespace hdg {
 
 constexpr int DIAG_NPART = 8;  // per-workgroup partials of the cell pass: 6 sums, 2 maxima
@@ -105,24 +107,7 @@ __device__ __forceinline__ void diag_cell_acc(const double (&x)[2 * Dim<K>::NU],
     sm[4] += sqK * qq[0];
     sm[5] += 0.5 * t2;
   }
-  double s2 = 0.0;
-#pragma unroll 1
-  for (int n = 0; n < NU; n++) {
-    double vx = 0.0, vy = 0.0;
-    if (Qn) {
-      vx = Qn[2 * n]; vy = Qn[2 * n + 1];
-    } else {
-#pragma unroll
-      for (int m = 0; m < NU; m++) {  // the order of k_q_modal_to_nodal: the values hdg_get_field returns
-        const double a = Vu[n * NU + m];
-        vx = fma(a, x[m], vx);
-        vy = fma(a, x[NU + m], vy);
-      }
-      vx *= vsc; vy *= vsc;
-    }
-    s2 = fmax(s2, __dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)));  // no contraction: |u| as a host computes it
-  }
-  const double sp = sqrt(s2);
+  const double sp = cell_max_speed<K, false>(x, Vu, vsc, Qn);  // hdg_step_rate.hpp: shared with the step-rate kernels
   mx[0] = fmax(mx[0], sp);
   mx[1] = fmax(mx[1], sp / hK);
 }
@@ -133,13 +118,9 @@ __global__ __launch_bounds__(DIAG_BLOCK) void k_diag_cell(Geo g, DevTables T, co
                                                            const double* __restrict__ p, const double* __restrict__ q,
                                                            const double* __restrict__ Qn, double* __restrict__ part) {
   constexpr int NU = Dim<K>::NU, NP = Dim<K>::NP;
-  const int xcd_ = blockIdx.x & 7, q_ = blockIdx.x >> 3;
-  const int jj_ = q_ / (2 * g.nbx), rem_ = q_ - jj_ * 2 * g.nbx;
-  const int s = rem_ / g.nbx;
-  const int i = (rem_ - s * g.nbx) * blockDim.x + threadIdx.x;
-  const int r_ = xcd_ * g.rows_xcd + jj_;
-  const int j = launch_row(g, r_);
-  const bool live = jj_ < g.rows_xcd && r_ < g.wrows && i < g.nx;
+  const CellAt at = cell_at(g);
+  const int s = at.s, i = at.i, j = at.j;
+  const bool live = at.live;
   double sm[6] = {0, 0, 0, 0, 0, 0}, mx[2] = {0, 0};
   if (live) {
     const long c = rowbase(g, s, j) + i;

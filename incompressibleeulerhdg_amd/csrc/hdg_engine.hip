@@ -36,6 +36,7 @@
 #include "../../include/hdg_viscosity.h"
 #include "../../include/hdg_coriolis.h"
 #include "../../include/hdg_moving_walls.h"
+#include "../../include/hdg_adaptive_dt.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -52,6 +53,7 @@
 #include "hdg_krylov_host.hpp"
 #include "hdg_tent_policy.hpp"
 #include "hdg_stage_coeffs.hpp"
+#include "hdg_step_control.hpp"
 #include "hdg_general.hpp"
 #include "hdg_general_kernels.hpp"
 #include "hdg_buoyancy.hpp"
@@ -253,6 +255,13 @@ struct Engine {
     if (it != allocs.end()) allocs.erase(it);
     HIPCHECK(hipFree(p));
     p = nullptr;
+  }
+  // a device allocation of dalloc / upload / upload_ints that is replaced: freed and forgotten (null: nothing)
+  void release_dev(const void* p) {
+    if (!p) return;
+    auto it = std::find(allocs.begin(), allocs.end(), const_cast<void*>(p));
+    if (it != allocs.end()) allocs.erase(it);
+    HIPCHECK(hipFree(const_cast<void*>(p)));
   }
   const double* upload(const dvec& v) {
     double* p = dalloc((long)v.size());
@@ -1605,8 +1614,15 @@ struct Engine {
   void ensure_dinv(int idx, double gamma) {
     if (general) {
       if (dinv_gamma[idx] == gamma && (gdinv[(size_t)idx].nrows || g_hyb[(size_t)idx])) return;
-      if (!opt.general_csr_lift && cfg.tent_precond == 2) g_hyb[(size_t)idx] = upload(assemble_lift_tables(*gtab, *gm, gloc, gamma));
-      else gdinv[(size_t)idx] = upload_csr(assemble_block_jacobi(*gtab, *gm, gloc, gamma));
+      // the tables of another gamma (hdg_set_dt) are freed, not kept
+      if (!opt.general_csr_lift && cfg.tent_precond == 2) {
+        release_dev(g_hyb[(size_t)idx]);
+        g_hyb[(size_t)idx] = upload(assemble_lift_tables(*gtab, *gm, gloc, gamma));
+      } else {
+        DevCsr& D = gdinv[(size_t)idx];
+        release_dev(D.rowptr); release_dev(D.col); release_dev(D.val);
+        D = upload_csr(assemble_block_jacobi(*gtab, *gm, gloc, gamma));
+      }
       dinv_gamma[idx] = gamma;
       return;
     }
@@ -4130,6 +4146,19 @@ struct Engine {
   const double *diag_hmin = nullptr, *diag_gVu = nullptr;  // general meshes: shortest edge per cell, unscaled modal -> nodal
   const int* diag_ecl = nullptr;                            // general meshes: (3 c + l) of the cells of every edge
   int diag_ncb = 0, diag_neb = 0;
+  // general meshes: the shortest edge of every cell and the unscaled modal -> nodal matrix (the diagnostics and the step rate)
+  void diag_general_geo() {
+    if (diag_hmin) return;
+    const GMesh& M = *gm;
+    dvec hm((size_t)M.nc);
+    for (int c = 0; c < M.nc; c++) {
+      double h = M.elen[(size_t)M.cedge[3 * (size_t)c]];
+      for (int l = 1; l < 3; l++) h = std::min(h, M.elen[(size_t)M.cedge[3 * (size_t)c + l]]);
+      hm[(size_t)c] = h;
+    }
+    diag_hmin = upload(hm);
+    diag_gVu = upload(gtab->Vu);
+  }
   void diag_alloc() {
     if (diag_part) return;
     if (general) {
@@ -4142,15 +4171,8 @@ struct Engine {
           const int c = M.ecell[2 * (size_t)e + sd];
           if (c >= 0) ecl[2 * (size_t)e + sd] = 3 * c + M.elocal[2 * (size_t)e + sd];
         }
-      dvec hm((size_t)M.nc);
-      for (int c = 0; c < M.nc; c++) {
-        double h = M.elen[(size_t)M.cedge[3 * (size_t)c]];
-        for (int l = 1; l < 3; l++) h = std::min(h, M.elen[(size_t)M.cedge[3 * (size_t)c + l]]);
-        hm[(size_t)c] = h;
-      }
       diag_ecl = upload_ints(ecl);
-      diag_hmin = upload(hm);
-      diag_gVu = upload(gtab->Vu);
+      diag_general_geo();
     } else {
       diag_ncb = (int)cell_grid().x;
       diag_neb = (int)corner_grid().x;
@@ -4409,6 +4431,99 @@ struct Engine {
     diag_record();
     probe_record();
     particles_step();
+  }
+
+  // ------------------------------------------------------------------ adaptive time step (hdg_step_rate.hpp, hdg_step_control.hpp;
+  // DESIGN.md section 25).  cfg.dt is read where it is used -- gamma = a_ii dt at the solve sites, the stage coefficients of
+  // hdg_stage_coeffs.hpp, the three stability reports -- and ensure_dinv follows gamma, so a new dt is a new cfg.dt and what
+  // remembers the old one: the Chebyshev history of the stages and the predictor of the particles.
+  double* d_rate = nullptr;  // word 0: this rank's maximum as a bit pattern; words 1 .. size: the gathered ones (strips);
+                             // behind them one word per workgroup of the rate kernel
+  // The monolithic and the DG step key a preconditioner set by tau / dt (get_pset): the sets of the step sizes left behind are
+  // freed, so an adaptive run holds the set of the construction and that of the dt in use.  Structured meshes only: on a
+  // general mesh a set is an assembled operator set with its algebraic hierarchy, which is kept.
+  void drop_other_psets() {
+    if (general || psets.size() <= 1) return;
+    for (size_t i = 1; i < psets.size(); i++) {
+      PSet& ps = psets[i];
+      for (int sh = 0; sh < 2; sh++) {
+        release_dev(ps.dt.Ainv[sh]); release_dev(ps.dt.W[sh]); release_dev(ps.dt.Y[sh]); release_dev(ps.dt.SK[sh]);
+        release_dev(ps.bsm[sh]);
+      }
+      for (int t = 0; t < 3; t++) for (int vv = 0; vv < 3; vv++) release_dev(ps.dt.trDinv[t][vv]);
+      release_dev(ps.cdm);
+    }
+    psets.resize(1);
+    use_pset(0);
+  }
+  void set_dt(double v) {
+    if (!std::isfinite(v) || !(v > 0.0)) throw std::string("hdg_set_dt: dt = " + std::to_string(v) + " is not a finite value > 0");
+    if (step_open) throw std::string("hdg_set_dt: a step is open (between hdg_begin_step and the end of the step)");
+    if (v == cfg.dt) return;  // nothing at all: the steps after it are those of a run without the call
+    cfg.dt = v;
+    ch.assign((size_t)s + 1, ChebStage{});
+    drop_other_psets();
+    if (pa_n > 0) particles_launch(PF_PREDICT, 1, v, nullptr);  // X* of this dt from the k1 in place
+  }
+  // A = max_K (max nodal |u| in K) / h_K of the modal device velocity Q: NaN when it is not finite anywhere
+  double advective_rate(const double* Q) {
+    const int nb = general ? (gm->nc + STEP_RATE_BLOCK - 1) / STEP_RATE_BLOCK : (int)cell_grid().x;
+    if (!d_rate) d_rate = dalloc(1L + comm->size + nb);
+    unsigned long long* word = (unsigned long long*)d_rate;
+    unsigned long long* part = word + 1 + comm->size;
+    tally(LC_OTHER, bQ());
+    if (general) {
+      diag_general_geo();
+      by_degree([&](auto k) { k_g_step_rate<k()><<<nb, STEP_RATE_BLOCK, 0, stream>>>(gm->nc, ggeo.inv_sdet, diag_gVu, diag_hmin, Q, part); });
+    } else {
+      by_degree([&](auto k) { k_step_rate<k()><<<cell_grid(), bs(), 0, stream>>>(g, dt.Vu, Q, part); });
+    }
+    tally(LC_OTHER, 0.0);
+    k_step_rate_reduce<<<1, 1024, 0, stream>>>(nb, part, word);
+    const double* src = d_rate;
+    if (comm->size > 1) {  // the maxima of every rank, gathered as the diagnostics gather theirs; taken below
+      comm->allgather(d_rate, d_rate + 1, 1, stream);
+      n_gather++;
+      src = d_rate + 1;
+    }
+    std::vector<unsigned long long> bits((size_t)comm->size);
+    HIPCHECK(hipMemcpyAsync(bits.data(), src, sizeof(unsigned long long) * bits.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    const unsigned long long top = *std::max_element(bits.begin(), bits.end());
+    if (top > 0x7ff0000000000000ull) return std::numeric_limits<double>::quiet_NaN();  // a NaN pattern, of either sign
+    double A;
+    std::memcpy(&A, &top, sizeof(A));
+    return A;
+  }
+  // the four rates whose product with dt has to stay bounded; [1..3] are what the three reports multiply by dt
+  void step_rates(double* rates) {
+    if (step_open) throw std::string("hdg_get_step_rates: a step is open (between hdg_begin_step and the end of the step)");
+    rates[0] = advective_rate(curQ);
+    rates[1] = rates[2] = rates[3] = 0.0;
+    double kmax = 0.0;
+    for (double x : tr_kappa) kmax = std::max(kmax, x);
+    double out2[2];
+    if (kmax > 0.0) { tracer_diffusion_number(out2); rates[1] = kmax * out2[0]; }
+    if (visc_nu > 0.0) { viscosity_number(visc_nu, visc_wall, out2); rates[2] = visc_nu * out2[0]; }
+    if (cor_f0 != 0.0 || cor_beta != 0.0) rates[3] = coriolis_bound(cor_f0, cor_beta);
+  }
+  double propose_dt(const hdg_step_control& control, double t, double t_final) {
+    if (!step_control_valid(control))
+      throw std::string("hdg_propose_dt: cfl must be > 0 and no field of the control may be negative or NaN");
+    if (!std::isfinite(t) || !std::isfinite(t_final)) throw std::string("hdg_propose_dt: t and t_final must be finite");
+    double rates[4], p;
+    step_rates(rates);
+    switch (step_proposal(control, rates[0], cfg.dt, t, t_final, p)) {
+      case StepVerdict::Ok: break;
+      case StepVerdict::NotFinite: throw NotConverged{"hdg_propose_dt: velocity is not finite"};
+      case StepVerdict::BelowMin: {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "hdg_propose_dt: the proposal dt = %.17g is below dt_min = %.17g", p, control.dt_min);
+        throw std::string(buf);
+      }
+      case StepVerdict::BadControl: throw std::string("hdg_propose_dt: bad control");
+    }
+    return p;
   }
 
   // ------------------------------------------------------------------ checkpoint and restart (hdg_checkpoint.hpp)
@@ -5819,6 +5934,38 @@ int hdg_apply_coriolis(hdg_handle* h, double f0, double beta, const double* Q, d
   E.zero(E.wQ2, E.NQ);
   E.coriolis_apply(E.wQ1, f0, beta, false, E.wQ2);
   E.get_Q(E.wQ2, out);
+  HDG_API_END(h)
+}
+
+// ---- adaptive time step (include/hdg_adaptive_dt.h)
+int hdg_set_dt(hdg_handle* h, double dt) {
+  HDG_API_BEGIN(h)
+  E.set_dt(dt);
+  HDG_API_END(h)
+}
+int hdg_get_dt(const hdg_handle* h, double* dt) {
+  if (!h || !h->eng || !dt) return HDG_ERR_ARG;
+  *dt = h->eng->cfg.dt;
+  return HDG_OK;
+}
+int hdg_get_step_rates(hdg_handle* h, double rates[4]) {
+  HDG_API_BEGIN(h)
+  if (!rates) throw std::string("null argument");
+  E.step_rates(rates);
+  HDG_API_END(h)
+}
+int hdg_step_proposal(const hdg_step_control* control, double A, double dt, double t, double t_final, double* dt_new) {
+  if (!control || !dt_new) return HDG_ERR_ARG;
+  switch (hdg::step_proposal(*control, A, dt, t, t_final, *dt_new)) {
+    case hdg::StepVerdict::Ok: return HDG_OK;
+    case hdg::StepVerdict::NotFinite: return HDG_ERR_NOT_CONVERGED;
+    default: return HDG_ERR_ARG;
+  }
+}
+int hdg_propose_dt(hdg_handle* h, const hdg_step_control* control, double t, double t_final, double* dt_new) {
+  HDG_API_BEGIN(h)
+  if (!control || !dt_new) throw std::string("null argument");
+  *dt_new = E.propose_dt(*control, t, t_final);
   HDG_API_END(h)
 }
 

@@ -30,6 +30,11 @@ two runs ended in the same engine state.
 timestepper with ``--start_nx``, ``--start_degree`` and ``--start_dt`` (each defaults to the run's own value) loads FILE, and its
 state is L2 projected onto the run's spaces on the device; the meshes must be nested.
 
+``--cfl C`` holds the CFL number at C with a step size that changes during the run: ``--dt`` is the first
+step size and, without ``--dt_max``, the largest; the controller decides before the first step and after every
+``--adapt_every``-th one, and a proposal below ``--dt_min`` or more than ``--max_steps`` steps stop the run.  One line at the end
+gives the number of steps and the range of the step sizes.  Not with ``--checkpoint`` / ``--restart``.
+
 ``--gpus N`` (N > 1) runs the two structured problems on N strips (one process per rank, include/hdg_mi355x.h:
 hdg_create_distributed): the driver starts ``python -m torch.distributed.run --nproc-per-node=N`` with the same arguments
 as a child process and returns its exit status.  Each rank chooses RCCL when every rank has a device of its own and the
@@ -153,6 +158,15 @@ def build_parser():
                         help="with --start_from: the degree of the run that wrote FILE (default: --degree)")
     parser.add_argument("--start_dt", metavar="DT", type=float, default=None,
                         help="with --start_from: the timestep size of the run that wrote FILE (default: --dt)")
+    parser.add_argument("--cfl", metavar="C", type=float, default=None,
+                        help="adaptive time step: hold the CFL number dt max |u| / h at C; --dt is the first step size (and the "
+                             "largest without --dt_max); not with --checkpoint / --restart")
+    parser.add_argument("--dt_min", metavar="D", type=float, default=None, help="with --cfl: a proposed step size below D stops the run")
+    parser.add_argument("--dt_max", metavar="D", type=float, default=None, help="with --cfl: the largest step size (default: --dt)")
+    parser.add_argument("--adapt_every", metavar="M", type=int, default=None,
+                        help="with --cfl: the controller decides before the first step and after every M-th one (default 1)")
+    parser.add_argument("--max_steps", metavar="N", type=int, default=None,
+                        help="with --cfl: stop the run with an error after N steps (default 10 ceil(tfinal / dt)); sizes the row logs")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -346,6 +360,40 @@ def check_checkpoint(args):
     for path in files:
         if not os.path.isfile(path):
             raise RuntimeError(f"--restart: no checkpoint file {path}")
+
+
+def check_adaptive(args):
+    """--cfl and its options, before any process is started or any engine is built: what solve(cfl=...) refuses."""
+    if args.cfl is None:
+        for name in ("dt_min", "dt_max", "adapt_every", "max_steps"):
+            if getattr(args, name) is not None:
+                raise RuntimeError(f"--{name} needs --cfl")
+        return
+    if not (np.isfinite(args.cfl) and args.cfl > 0):
+        raise RuntimeError(f"--cfl must be a finite number > 0 (got {args.cfl})")
+    if args.adapt_every is not None and args.adapt_every < 1:
+        raise RuntimeError(f"--adapt_every must be at least 1 (got {args.adapt_every})")
+    if args.max_steps is not None and args.max_steps < 1:
+        raise RuntimeError(f"--max_steps must be at least 1 (got {args.max_steps})")
+    dt_min, dt_max = args.dt_min or 0.0, args.dt if args.dt_max is None else args.dt_max
+    if not (np.isfinite(dt_min) and dt_min >= 0) or not (dt_max > 0) or dt_min > dt_max:
+        raise RuntimeError(f"--dt_min and --dt_max must satisfy 0 <= dt_min <= dt_max, dt_max > 0 (got {dt_min}, {dt_max})")
+    for bad, what in ((bool(args.checkpoint), "--checkpoint"), (bool(args.restart), "--restart"),
+                      (args.test_pressure_solver, "--test_pressure_solver (no time loop)")):
+        if bad:
+            raise RuntimeError(f"--cfl does not go with {what}" + (": a checkpoint carries the step size of --dt in its fingerprint "
+                               "and does not hold the time series of an adaptive run" if what in ("--checkpoint", "--restart") else ""))
+
+
+def adaptive_keywords(args):
+    """The keyword arguments of solve for --cfl and its options"""
+    if args.cfl is None:
+        return {}
+    kw = {"cfl": args.cfl}
+    for name in ("dt_min", "dt_max", "adapt_every", "max_steps"):
+        if getattr(args, name) is not None:
+            kw[name] = getattr(args, name)
+    return kw
 
 
 MAX_START_RATIO = 16  # csrc/hdg_transfer.hpp: MAX_RATIO
@@ -551,6 +599,7 @@ def main(argv=None):
     wall_velocity(args)
     check_coriolis(args)
     check_checkpoint(args)
+    check_adaptive(args)
     check_start_from(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(argv, args.gpus)  # nothing here has touched the GPU
@@ -744,8 +793,13 @@ def _run(args, ranks):
         kw["checkpoint"], kw["checkpoint_every"] = args.checkpoint, args.checkpoint_every or 0
     if args.restart:
         kw["restart"] = args.restart
+    kw.update(adaptive_keywords(args))
     Q, p = timestepper.solve(Q_0, p_0, q_0, model_problem.f_rhs(), args.tfinal, warmup=args.warmup, **kw)
     state_digest = eng.state_digest()  # of this rank's strip
+    if timestepper.step_sizes is not None:  # --cfl (not with --warmup, whose one step is --dt)
+        dts = timestepper.step_sizes[:, 1]
+        print(f"steps = {len(dts)}, dt in [{float(dts.min())!r}, {float(dts.max())!r}], last dt = {float(dts[-1])!r}" if len(dts) else "steps = 0")
+        print()
     if args.diagnostics:
         report_solver_events(eng.solver_events())
         if ranks.rank == 0:

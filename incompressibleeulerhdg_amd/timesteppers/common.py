@@ -9,7 +9,7 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from .._lib import DIAGNOSTICS, HDG_STATE_CURRENT, POINT_COLUMNS, Engine
+from .._lib import DIAGNOSTICS, HDG_STATE_CURRENT, POINT_COLUMNS, Engine, HDGError, step_control, step_proposal
 from ..auxilliary.logging import PerformanceLog
 from ..mesh import Function, FunctionSpace
 
@@ -165,6 +165,9 @@ class IncompressibleEuler(ABC):
         self.diagnostics = None  # solve(..., diagnostics=True): dict of the recorded series
         self.probes = None  # solve(..., probes=xy): dict of the recorded point values
         self.particles = None  # solve(..., particles=xy): dict of the recorded particle positions
+        self.step_sizes = None  # solve(..., cfl=C): one row (t, dt, A dt) per step taken
+        self.step_decisions = None  # ... and one row (t, A, dt held, dt proposed) per decision of the controller
+        self._t_adaptive = None  # the start time of the next step while an adaptive run is under way
 
     # -- engine and function spaces ------------------------------------------------------------
     def _create_engine(self, **kw):
@@ -348,6 +351,114 @@ class IncompressibleEuler(ABC):
     def _end_solve(self):
         """After the recorders have finished, before the final fields are fetched."""
 
+    def _call_back(self, t, tracer):
+        """The callbacks after a step that reached the time t"""
+        if self.callbacks:
+            Q, p = self._current()
+            qt = self._tracer_function() if tracer else None
+            for callback in self.callbacks:
+                callback(*self._functions(Q, p, self._callback_names), t, q_tracer=qt)
+
+    def _time(self, k):
+        """The time at which step k starts: k dt at a fixed step size, the running sum of the step sizes in an adaptive run"""
+        return k * self._dt if self._t_adaptive is None else self._t_adaptive
+
+    # -- adaptive time step (include/hdg_adaptive_dt.h; DESIGN.md section 25) ----------------------------------------
+    def _step_controller(self, T_final, warmup, checkpoint, restart, cfl, dt_min, dt_max, adapt_every, max_steps):
+        """solve(..., cfl=, dt_min=, dt_max=, adapt_every=, max_steps=) checked, before the engine is touched: None without
+        cfl= (and for a warm-up run, whose one step is the constructor's), else (every, max_steps, dt_min, dt_max)."""
+        if cfl is None:
+            for name, v in (("dt_min", dt_min), ("dt_max", dt_max), ("max_steps", max_steps)):
+                if v is not None:
+                    raise ValueError(f"{name}= needs cfl=")
+            if adapt_every != 1:
+                raise ValueError("adapt_every= needs cfl=")
+            return None
+        if not (np.isfinite(cfl) and cfl > 0):
+            raise ValueError(f"cfl must be a finite number > 0 (got {cfl})")
+        if int(adapt_every) != adapt_every or adapt_every < 1:
+            raise ValueError(f"adapt_every must be an integer >= 1 (got {adapt_every})")
+        if checkpoint is not None or restart is not None:
+            raise ValueError("cfl= does not go with checkpoint= or restart=: a checkpoint carries the step size of the "
+                             "constructor in its fingerprint and does not hold the time series of an adaptive run")
+        dt_max = self._dt if dt_max is None else dt_max
+        dt_min = 0.0 if dt_min is None else dt_min
+        if not (np.isfinite(dt_min) and dt_min >= 0) or not (dt_max > 0) or dt_min > dt_max:
+            raise ValueError(f"dt_min and dt_max must satisfy 0 <= dt_min <= dt_max, dt_max > 0 (got {dt_min}, {dt_max})")
+        if not (np.isfinite(T_final) and T_final > 0):
+            raise ValueError(f"cfl= needs a finite T_final > 0 (got {T_final})")
+        if max_steps is None:
+            max_steps = 10 * int(np.ceil(T_final / self._dt))
+        if int(max_steps) != max_steps or max_steps < 1:
+            raise ValueError(f"max_steps must be an integer >= 1 (got {max_steps})")
+        if warmup:
+            return None
+        return int(adapt_every), int(max_steps), float(dt_min), float(dt_max)
+
+    def _step_caps(self, rates):
+        """The upper limits of dt from the explicit terms, in the order of hdg_step_control.caps: the real-axis limit of the
+        tableau over kappa_max Lambda and over nu Lambda_u, its imaginary-axis limit over F (only when that limit is
+        positive); None: no limit."""
+        cfg, s = self._engine.cfg, self._engine.nstages  # the tableau the engine steps with: a term may have been switched
+        a_expl, b_expl = list(cfg.a_expl)[:s * s], list(cfg.b_expl)[:s]  # on through the engine, not through the constructor
+        caps = [None, None, None]
+        if rates[1] > 0 or rates[2] > 0:
+            real = explicit_stability_limit(a_expl, b_expl)
+            caps[0] = real / rates[1] if rates[1] > 0 else None
+            caps[1] = real / rates[2] if rates[2] > 0 else None
+        if rates[3] > 0:
+            imaginary = explicit_imaginary_limit(a_expl, b_expl)
+            caps[2] = imaginary / rates[3] if imaginary > 0 else None
+        return [None if c is None or not np.isfinite(c) else c for c in caps]
+
+    def _adaptive_loop(self, controller, cfl, f_rhs, tracer, T_final):
+        """The time loop with cfl=: the controller decides before the first step and after every `every`-th one, the step
+        size changes only when the proposal differs from the one held; returns the number of steps taken."""
+        eng = self._engine
+        every, max_steps, dt_min, dt_max = controller
+        dt0 = self._dt
+        rates = eng.step_rates()
+        control = step_control(cfl, dt_min=dt_min, dt_max=dt_max, caps=self._step_caps(rates))
+        sizes, decisions = [], []
+        t, k, A = 0.0, 0, rates[0]
+        try:
+            while T_final - t > 1.0e-12 * T_final:
+                if k == max_steps:
+                    raise RuntimeError(f"max_steps = {max_steps} steps taken and the run is at t = {t!r}, short of T_final = {T_final!r}")
+                if k % every == 0:
+                    if k > 0:
+                        A = eng.step_rates()[0]
+                    held = eng.get_dt()
+                    proposal = step_proposal(control, A, held, t, T_final)
+                    decisions.append((t, A, held, proposal))
+                    if proposal != held:
+                        eng.set_dt(proposal)
+                        self._dt = proposal
+                self._t_adaptive = t
+                with PerformanceLog("timestep"):
+                    self._advance(k, f_rhs, tracer)
+                sizes.append((t, self._dt, A * self._dt))
+                t, k = t + self._dt, k + 1
+                self._call_back(t, tracer)
+        except BaseException:
+            self._end_adaptive(sizes, decisions, dt0, failed=True)
+            raise
+        self._end_adaptive(sizes, decisions, dt0)
+        return k
+
+    def _end_adaptive(self, sizes, decisions, dt0, failed=False):
+        """The stepper and its engine hold the constructor's step size again.  failed: the loop raised, perhaps inside an open
+        step, where the engine refuses a new dt: that refusal must not hide the error that is on its way."""
+        self.step_sizes = np.array(sizes, dtype=float).reshape(-1, 3)
+        self.step_decisions = np.array(decisions, dtype=float).reshape(-1, 4)
+        self._t_adaptive = None
+        self._dt = dt0
+        try:
+            self._engine.set_dt(dt0)
+        except HDGError:
+            if not failed:
+                raise
+
     def _current(self):
         """The current nodal velocity and pressure"""
         return self._engine.get_field(HDG_STATE_CURRENT, lam=False)[:2]
@@ -399,16 +510,21 @@ class IncompressibleEuler(ABC):
         return k0, t0, saved["tracer"]
 
     def _solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, checkpoint=None, checkpoint_every=0, restart=None,
-               **requests):
+               cfl=None, dt_min=None, dt_max=None, adapt_every=1, max_steps=None, **requests):
         """The time loop of every stepper; ``requests``: the per-step outputs asked for, by the names of RECORDERS (each
         class there says what counts as asked for) and ``particle_every``.  Each one asked for leaves its dict in the attribute of its name.
 
         ``checkpoint=PATH`` writes the engine's state (Engine.save_checkpoint) after every ``checkpoint_every``-th step
         (0: never in between) and after the last one; ``restart=PATH`` continues such a file: the state, the tracers and the
         recorders are the saved ones (the initial-condition arguments are ignored and may be None) and the loop runs from
-        the saved step to the end, so the run is the uninterrupted one bit for bit."""
+        the saved step to the end, so the run is the uninterrupted one bit for bit.
+
+        ``cfl=C`` holds the CFL number at C with a step size that changes during the run:
+        ``self.step_sizes`` then has one row (t, dt, A dt) per step taken, and the recorders take their times from it."""
         eng = self._engine
-        nt = self.get_timesteps(T_final, warmup)
+        controller = self._step_controller(T_final, warmup, checkpoint, restart, cfl, dt_min, dt_max, adapt_every, max_steps)
+        self.step_sizes = self.step_decisions = None
+        nt = self.get_timesteps(T_final, warmup) if controller is None else controller[1]  # adaptive: the size of the row logs
         if checkpoint is not None and int(checkpoint_every) < 0:
             raise ValueError(f"checkpoint_every must be >= 0 (got {checkpoint_every})")
         self._forcing_profile = None
@@ -430,18 +546,17 @@ class IncompressibleEuler(ABC):
             callback.reset()
             callback(*self._functions(*self._current(), self._callback_names), t0,
                      q_tracer=self.q_tracers if len(self.q_tracers) > 1 else self.q_tracer)
-        for k in range(k0, nt):
+        if controller is not None:
+            self._adaptive_loop(controller, cfl, f_rhs, tracer, T_final)
+        for k in (range(k0, nt) if controller is None else ()):
             with PerformanceLog("timestep"):
                 t = self._advance(k, f_rhs, tracer)
             if checkpoint is not None and (k + 1 == nt or (checkpoint_every and (k + 1) % int(checkpoint_every) == 0)):
                 self._write_checkpoint(checkpoint, k + 1, t)
-            if self.callbacks:
-                Q, p = self._current()
-                qt = self._tracer_function() if tracer else None
-                for callback in self.callbacks:
-                    callback(*self._functions(Q, p, self._callback_names), t, q_tracer=qt)
+            self._call_back(t, tracer)
+        times = None if self.step_sizes is None else np.append(self.step_sizes[:, 0], self.step_sizes[-1:, :2].sum())
         for name, rec in recorders:
-            setattr(self, name, rec.finish(eng))
+            setattr(self, name, rec.finish(eng, times))
         self._end_solve()
         Q, p = self._current()
         if tracer:
@@ -450,7 +565,8 @@ class IncompressibleEuler(ABC):
 
     @abstractmethod
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
+              particles=None, particle_every=1, cfl=None, dt_min=None, dt_max=None, adapt_every=1, max_steps=None,
+              checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final; returns the final velocity and pressure (common.py:131-144)."""
 
 
@@ -465,13 +581,13 @@ class _Diagnostics:
     def start(self, eng, nt):
         eng.set_diagnostics(nt + 1)
 
-    def finish(self, eng):
-        """t and the nine series"""
+    def finish(self, eng, times=None):
+        """t and the nine series; times: the time of every row of an adaptive run (None: k dt)"""
         try:
             rows = eng.diagnostics(reset=True)
         finally:
             eng.set_diagnostics(0)
-        out = {"t": np.arange(rows.shape[0]) * self.dt}
+        out = {"t": np.arange(rows.shape[0]) * self.dt if times is None else times[:rows.shape[0]].copy()}
         out.update((name, rows[:, i].copy()) for i, name in enumerate(DIAGNOSTICS))
         return out
 
@@ -487,14 +603,14 @@ class _Probes:
     def start(self, eng, nt):
         eng.set_probes(self.xy, nt + 1)
 
-    def finish(self, eng):
+    def finish(self, eng, times=None):
         """t, xy, u (nt+1, n, 2), p, q, omega (nt+1, n)"""
         try:
             rows = eng.probes(reset=True)
         finally:
             eng.set_probes(None, 0)
         c = {name: i for i, name in enumerate(POINT_COLUMNS)}
-        return {"t": np.arange(rows.shape[0]) * self.dt, "xy": self.xy.copy(),
+        return {"t": np.arange(rows.shape[0]) * self.dt if times is None else times[:rows.shape[0]].copy(), "xy": self.xy.copy(),
                 "u": rows[:, :, [c["ux"], c["uy"]]].copy(), "p": rows[:, :, c["p"]].copy(),
                 "q": rows[:, :, c["q"]].copy(), "omega": rows[:, :, c["omega"]].copy()}
 
@@ -512,13 +628,14 @@ class _Particles:
     def start(self, eng, nt):
         eng.set_particles(self.xy, nt // self.every + 1, self.every)
 
-    def finish(self, eng):
+    def finish(self, eng, times=None):
         """t, xy (rows, n, 2), clamped, lost"""
         try:
             rows, counts = eng.particles(reset=True)
         finally:
             eng.set_particles(None, 0)
-        return {"t": np.arange(rows.shape[0]) * self.every * self.dt, "xy": rows,
+        return {"t": np.arange(rows.shape[0]) * self.every * self.dt if times is None else times[::self.every][:rows.shape[0]].copy(),
+                "xy": rows,
                 "clamped": counts["clamped"], "lost": counts["lost"]}
 
 

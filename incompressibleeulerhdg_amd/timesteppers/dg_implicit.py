@@ -28,14 +28,17 @@ class IncompressibleEulerDGImplicit(IncompressibleEuler):
                             nstages=1, a_expl=[[0]], a_impl=[[1]], b_expl=[1], b_impl=[1], c_expl=[0])
 
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
+              particles=None, particle_every=1, cfl=None, dt_min=None, dt_max=None, adapt_every=1, max_steps=None,
+              checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``, ``particles``, ``checkpoint``,
-        ``checkpoint_every``, ``restart``: see IncompressibleEulerHDGIMEX.solve."""
+        ``checkpoint_every``, ``restart``, ``cfl``, ``dt_min``, ``dt_max``, ``adapt_every``, ``max_steps``: see
+        IncompressibleEulerHDGIMEX.solve."""
         return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
                            particles=particles, particle_every=particle_every, checkpoint=checkpoint,
-                           checkpoint_every=checkpoint_every, restart=restart)
+                           checkpoint_every=checkpoint_every, restart=restart, cfl=cfl, dt_min=dt_min, dt_max=dt_max,
+                           adapt_every=adapt_every, max_steps=max_steps)
 
     def _advance(self, k, f_rhs, tracer):
-        self._set_forcing(0, f_rhs, k * self._dt)  # dg_implicit.py:125; dg_implicit.py:100-102, p_0 -= mean, is done by hdg_set_state
+        self._set_forcing(0, f_rhs, self._time(k))  # dg_implicit.py:125; dg_implicit.py:100-102, p_0 -= mean, is done by hdg_set_state
         self.niter.update(self._engine.dg_implicit_step())
         return (k + 1) * self._dt

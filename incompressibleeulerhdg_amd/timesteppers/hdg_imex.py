@@ -110,7 +110,8 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
 
     # -- time loop (hdg_imex.py:505-660) ----------------------------------------------------------
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, fused=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
+              particles=None, particle_every=1, cfl=None, dt_min=None, dt_max=None, adapt_every=1, max_steps=None,
+              checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final with nt timesteps; returns (Q, p).
 
         ``fused=True`` runs each step as one device-resident ``hdg_step`` call instead of the
@@ -126,11 +127,18 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
         and after the last one (strips: each rank writes ``PATH.<rank>``); ``restart=PATH`` continues such a file to
         T_final -- the run is then the uninterrupted one bit for bit, recorded series included; the initial-condition
         arguments are ignored and may be None.
+        ``cfl=C`` holds the CFL number dt max |u| / h at C with a step size that changes during the run (DESIGN.md section
+        25): the constructor's dt is the first step size and, without ``dt_max``, the largest; the controller decides before
+        the first step and after every ``adapt_every``-th one and also keeps dt below the limits of the explicit terms; a
+        proposal below ``dt_min`` raises HDGError, more than ``max_steps`` steps (default 10 ceil(T_final / dt)) RuntimeError.
+        ``self.step_sizes`` then holds one row (t, dt, A dt) per step and the recorders take their times from it.  Not with
+        ``checkpoint`` / ``restart``.
         """
         self._fused = fused
         return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
                            particles=particles, particle_every=particle_every, checkpoint=checkpoint,
-                           checkpoint_every=checkpoint_every, restart=restart)
+                           checkpoint_every=checkpoint_every, restart=restart, cfl=cfl, dt_min=dt_min, dt_max=dt_max,
+                           adapt_every=adapt_every, max_steps=max_steps)
 
     _callback_names = _result_names = ("Q", "p")
 
@@ -148,7 +156,7 @@ class IncompressibleEulerHDGIMEX(IncompressibleEuler):
 
     def _advance(self, k, f_rhs, tracer):
         eng, s = self._engine, self.nstages
-        tn = k * self._dt
+        tn = self._time(k)
         for i in range(s):
             self._set_forcing(i, f_rhs, tn + self._c_expl[i] * self._dt)
         self._set_forcing(s, f_rhs, tn + self._dt)  # _b_new (hdg_imex.py:629)

@@ -34,15 +34,18 @@ class IncompressibleEulerHDGImplicit(IncompressibleEuler):
                             b_impl=[1], c_expl=[0])
 
     def solve(self, Q_initial, p_initial, q_initial, f_rhs, T_final, warmup=False, diagnostics=False, probes=None,
-              particles=None, particle_every=1, checkpoint=None, checkpoint_every=0, restart=None):
+              particles=None, particle_every=1, cfl=None, dt_min=None, dt_max=None, adapt_every=1, max_steps=None,
+              checkpoint=None, checkpoint_every=0, restart=None):
         """Propagate the solution to T_final; returns (Q, p).  ``diagnostics``, ``probes``, ``particles``, ``checkpoint``,
-        ``checkpoint_every``, ``restart``: see IncompressibleEulerHDGIMEX.solve."""
+        ``checkpoint_every``, ``restart``, ``cfl``, ``dt_min``, ``dt_max``, ``adapt_every``, ``max_steps``: see
+        IncompressibleEulerHDGIMEX.solve."""
         return self._solve(Q_initial, p_initial, q_initial, f_rhs, T_final, warmup, diagnostics=diagnostics, probes=probes,
                            particles=particles, particle_every=particle_every, checkpoint=checkpoint,
-                           checkpoint_every=checkpoint_every, restart=restart)
+                           checkpoint_every=checkpoint_every, restart=restart, cfl=cfl, dt_min=dt_min, dt_max=dt_max,
+                           adapt_every=adapt_every, max_steps=max_steps)
 
     def _advance(self, k, f_rhs, tracer):
-        self._set_forcing(0, f_rhs, k * self._dt)  # forcing at the START of the step (hdg_implicit.py:100)
+        self._set_forcing(0, f_rhs, self._time(k))  # forcing at the START of the step (hdg_implicit.py:100)
         it_t, it_p = self._engine.implicit_step()
         self.niter_tentative.update(it_t)
         self.niter_pressure.update(it_p)
