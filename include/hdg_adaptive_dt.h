@@ -14,7 +14,9 @@
  *   rates[0]  A = max_K (max nodal |u| in K) / h_K of the current velocity: the CFL number of the diagnostics row without
  *             its factor dt (the same nodes, the same h_K = shortest edge of K)
  *   rates[1]  kappa_max Lambda   of the tracer diffusion          (0 while it is off)
- *   rates[2]  nu Lambda_u        of the viscous term              (0 while it is off)
+ *   rates[2]  nu Lambda_u        of the viscous term              (0 while it is off); while the linear drag of
+ *             include/hdg_drag.h is on, nu Lambda_u + S: the real-axis rate of the whole velocity-linear part (both
+ *             spectra are real and non-positive, so the rates add); with the drag off it is what it was
  *   rates[3]  F = max |f_c|      of the Coriolis term             (0 while it is off)
  * rates[1..3] are the numbers the three stability reports divide by: report = rate * dt.
  *

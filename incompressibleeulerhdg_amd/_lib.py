@@ -24,6 +24,7 @@ CORIOLIS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_cor
 TRACER_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_walls.h"))
 MOVING_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_moving_walls.h"))
 ADAPTIVE_DT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_adaptive_dt.h"))
+DRAG_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_drag.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -96,7 +97,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER, DRAG_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -262,6 +263,16 @@ ADAPTIVE_DT_SIGNATURES = {
 }
 STEP_RATES = ("advection", "tracer_diffusion", "viscosity", "rotation")  # the entries of hdg_get_step_rates
 
+# linear drag and volume penalisation: the symbols include/hdg_drag.h declares, in a table of their own like the nine above
+DRAG_SIGNATURES = {
+    "hdg_set_drag": [_h, _dp, _dp, _ip],
+    "hdg_get_drag": [_h, _dp, _dp],
+    "hdg_apply_drag": [_h, _dp, _dp, _dp, _dp],
+    "hdg_get_drag_force": [_h, _dp],
+    "hdg_apply_drag_force": [_h, _dp, _dp, _ip, _dp, _dp],
+}
+HDG_DRAG_REGIONS = 4
+
 
 def step_control(cfl, dt_min=None, dt_max=None, grow=None, band=None, caps=None):
     """The hdg_step_control of the given settings; None: the default of the rule (a zeroed field)"""
@@ -323,7 +334,7 @@ def load_library():
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
             list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()) + \
-            list(ADAPTIVE_DT_SIGNATURES.items()):
+            list(ADAPTIVE_DT_SIGNATURES.items()) + list(DRAG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -784,8 +795,8 @@ class Engine:
 
     def step_rates(self):
         """(4,) in the order of STEP_RATES: A = max_K (max nodal |u| in K) / h_K of the current velocity (diagnostics column
-        'cfl' without its dt; not finite when the velocity is not), kappa_max Lambda, nu Lambda_u and F (0 while the term is
-        off).  Collective on strips: every rank gets the global maximum."""
+        'cfl' without its dt; not finite when the velocity is not), kappa_max Lambda, nu Lambda_u (plus S while the drag is
+        on: the real-axis rate of the velocity-linear part) and F (0 while the term is off).  Collective on strips: every rank gets the global maximum."""
         rates = np.zeros(4)
         self._ck(self.lib.hdg_get_step_rates(self.h, _ptr(rates)))
         return rates
@@ -796,6 +807,119 @@ class Engine:
         out = C.c_double()
         self._ck(self.lib.hdg_propose_dt(self.h, C.byref(control), float(t), float(t_final), C.byref(out)))
         return out.value
+
+    # --- linear drag and volume penalisation (include/hdg_drag.h)
+    def cell_vertices(self):
+        """(N_c, 3, 2): the vertices of this engine's cells (a rank's own on a strip) in the vertex order of the drag
+        coefficients, read off the node coordinates: the velocity nodes contain the cell vertices."""
+        from .output import cell_vertex_nodes
+
+        X = self.node_coordinates()[0].reshape(self.n_cells, -1, 2)
+        eng = self
+
+        class _Mesh:  # what cell_vertex_nodes asks of a mesh: the first two cells' vertices and the tolerance scale
+            general = eng.general
+            nx, ny = eng.cfg.nx, eng.cfg.ny
+            L = eng.cfg.length if eng.cfg.periodic else 1.0
+
+            def num_cells(self):
+                return eng.n_cells
+
+        class _Space:
+            value_size = 2
+
+            def mesh(self):
+                return mesh
+
+        mesh, space = _Mesh(), _Space()
+        if self.general:
+            mesh.vertices, mesh.cells = self._vertices, self._cells
+            v = self._vertices[self._cells]
+            a, b = v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+            mesh.volume = float(np.sum(0.5 * np.abs(a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])))
+            space.coordinates = X
+        else:  # a strip's rows start at its own offset: the first square of the rank against the first square of the mesh
+            space.coordinates = X - np.array([0.0, X[0, :, 1].min()])
+        idx = cell_vertex_nodes(space)
+        out = np.empty((self.n_cells, 3, 2))
+        for s in range(2):
+            out[s::2] = X[s::2][:, idx[s]]
+        return out
+
+    def _drag_sigma(self, sigma):
+        """scalar | (N_c, 3) | callable sigma(x, y) at the cell vertices -> (N_c, 3) float64"""
+        if callable(sigma):
+            V = self.cell_vertices()
+            sigma = np.asarray(sigma(V[..., 0], V[..., 1]), dtype=np.float64) * np.ones((self.n_cells, 3))
+        elif np.ndim(sigma) == 0:
+            sigma = np.full((self.n_cells, 3), float(sigma))
+        return _arr(sigma, (self.n_cells, 3))
+
+    def _drag_target(self, target):
+        """None | (N_c n_u, 2) | callable u_s(x, y) -> (u_x, u_y) at the velocity nodes"""
+        if target is None:
+            return None
+        if callable(target):
+            X = self.node_coordinates()[0]
+            ux, uy = target(X[:, 0], X[:, 1])
+            target = np.stack([ux * np.ones(len(X)), uy * np.ones(len(X))], axis=-1)
+        return _arr(target, self.shape_Q)
+
+    def _drag_region(self, region):
+        """None | N_c tags | callable r(x, y) at the centroids -> (N_c,) int32"""
+        if region is None:
+            return None
+        if callable(region):
+            ctr = self.cell_vertices().mean(axis=1)
+            region = np.asarray(region(ctr[:, 0], ctr[:, 1])) * np.ones(self.n_cells, dtype=np.int64)
+        region = np.ascontiguousarray(region, dtype=np.int32)
+        if region.shape != (self.n_cells,):
+            raise ValueError(f"expected {self.n_cells} region tags, got shape {region.shape}")
+        return region
+
+    def set_drag(self, sigma, target=None, region=None):
+        """- sigma (u - u_s) in the momentum equation, explicit in time.  sigma >= 0: a scalar (uniform friction), (N_c, 3)
+        vertex values per cell, or a callable sigma(x, y) evaluated at the cell vertices; None or all zeros: off.  target: u_s
+        as a nodal velocity field or a callable (x, y) -> (u_x, u_y), None: at rest.  region: tags 0 .. 3 per cell for
+        drag_force(), an array or a callable evaluated at the centroids.  Collective on strips."""
+        sigma = None if sigma is None else self._drag_sigma(sigma)
+        target, region = self._drag_target(target), self._drag_region(region)
+        self._ck(self.lib.hdg_set_drag(self.h, _ptr(sigma), _ptr(target), None if region is None else region.ctypes.data_as(_ip)))
+
+    def drag(self):
+        """(N_c, 3): the coefficients as they are set; zeros while the term is off."""
+        sigma = np.zeros((self.n_cells, 3))
+        self._ck(self.lib.hdg_get_drag(self.h, _ptr(sigma), None))
+        return sigma
+
+    def drag_number(self):
+        """(S, S dt): S = the largest vertex value of sigma (over all ranks), an upper bound of the spectral radius of M^-1 D."""
+        out = np.zeros(2)
+        self._ck(self.lib.hdg_get_drag(self.h, None, _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def apply_drag(self, Q, sigma, target=None):
+        """- M^-1 D (Q - u_s) of a nodal velocity-space field for the given sigma and target (test hook; it sets nothing)."""
+        Q = _arr(Q, self.shape_Q)
+        out = np.empty(self.shape_Q)
+        self._ck(self.lib.hdg_apply_drag(self.h, _ptr(self._drag_sigma(sigma)), _ptr(self._drag_target(target)), _ptr(Q), _ptr(out)))
+        return out
+
+    def drag_force(self):
+        """(4, 3): per region (F_x, F_y, P), the force of the term on the fluid, - int sigma (u - u_s), and its rate of work,
+        - int sigma (u - u_s) . u, of the current velocity with the setting held.  The force on a body is the negative."""
+        F = np.zeros((HDG_DRAG_REGIONS, 3))
+        self._ck(self.lib.hdg_get_drag_force(self.h, _ptr(F)))
+        return F
+
+    def drag_force_of(self, Q, sigma, target=None, region=None):
+        """(4, 3): the same functionals of a nodal velocity-space field (test hook; it sets nothing)."""
+        Q = _arr(Q, self.shape_Q)
+        F = np.zeros((HDG_DRAG_REGIONS, 3))
+        region = self._drag_region(region)
+        self._ck(self.lib.hdg_apply_drag_force(self.h, _ptr(self._drag_sigma(sigma)), _ptr(self._drag_target(target)),
+                                               None if region is None else region.ctypes.data_as(_ip), _ptr(Q), _ptr(F)))
+        return F
 
     # --- Coriolis term (include/hdg_coriolis.h; DESIGN.md section 22)
     def set_coriolis(self, f0, beta=0.0):

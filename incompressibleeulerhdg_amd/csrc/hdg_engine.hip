@@ -35,6 +35,7 @@
 #include "../../include/hdg_buoyancy.h"
 #include "../../include/hdg_viscosity.h"
 #include "../../include/hdg_coriolis.h"
+#include "../../include/hdg_drag.h"
 #include "../../include/hdg_moving_walls.h"
 #include "../../include/hdg_adaptive_dt.h"
 #include "hdg_options.hpp"
@@ -60,6 +61,8 @@
 #include "hdg_viscosity.hpp"
 #include "hdg_wall_force.hpp"
 #include "hdg_coriolis.hpp"
+#include "hdg_drag_host.hpp"
+#include "hdg_drag.hpp"
 #include "hdg_tracer_walls.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
@@ -3994,7 +3997,6 @@ struct Engine {
   const double* d_cortab = nullptr;  // structured: Y_0, Y_1 transposed; general: L_1, L_2
   const double* d_coryv = nullptr;   // general: the ordinates of a cell's three vertices, nc x 3
   bool coriolis_on() const { return cor_f0 != 0.0 || cor_beta != 0.0; }
-  bool vel_linear_on() const { return viscosity_on() || coriolis_on(); }
   void coriolis_check(const char* who, double f0, double beta) const {
     if (step_open) throw std::string(who) + ": a step is open (between hdg_begin_step and the end of the step)";
     if (!std::isfinite(f0) || !std::isfinite(beta))
@@ -4038,10 +4040,12 @@ struct Engine {
     });
     fl.set(out, 0);
   }
-  // the velocity-linear part of a slot: out = nu M^-1 V Q + M^-1 C Q, whichever of the two is on
+  // the velocity-linear part of a slot: out = nu M^-1 V Q + M^-1 C Q - M^-1 D (Q - u_s), whichever of the three are on; the
+  // first one that runs writes the slot, the others add to it in place (the drag kernel last, section 26)
   void vel_linear_apply(const double* Q, double* out) {
     if (viscosity_on()) viscosity_apply(Q, visc_nu, visc_wall, out, wall_u);
     if (coriolis_on()) coriolis_apply(Q, cor_f0, cor_beta, viscosity_on(), out);
+    if (drag_on()) drag_apply(drag_set, Q, -1.0, drag_set.load, viscosity_on() || coriolis_on(), out);
   }
   // F = max over the mesh vertices of |f0 + beta y|, an upper bound of rho(M^-1 C); f_c is linear, so on the structured meshes
   // the two ends of the ordinate decide
@@ -4053,6 +4057,126 @@ struct Engine {
     }
     if (cfg.periodic) return std::fabs(f0);
     return std::max(std::fabs(f0), std::fabs(f0 + beta * g.h * g.nyg));
+  }
+  // ---- linear drag and volume penalisation: - sigma (u - u_s), sigma >= 0 linear per cell.  M^-1 D is
+  // block diagonal per cell like M^-1 C, so the term rides in the same vectors: visc[j] is the velocity-linear part of slot j,
+  // nu M^-1 V Q^(j) + M^-1 C Q^(j) - M^-1 D (Q^(j) - u_s).  k_drag runs last: it accumulates when viscosity or rotation wrote
+  // the slot and writes otherwise.  The target enters as one vector M^-1 D u_s built at set time by the same kernel, so the
+  // slot stays affine in Q.  No ghost rows, no exchange; general meshes run on one rank.  Host packing: hdg_drag_host.hpp.
+  struct DragSet {
+    double* coef = nullptr;  // structured: three planes of Nc in the kernels' cell order; general: nc x 3
+    int* region = nullptr;   // structured: Nc tags in the kernels' cell order; general: nc
+    double* load = nullptr;  // M^-1 D u_s (NQ), or null: u_s = 0
+    double S = 0.0;          // the largest vertex value of this rank
+  };
+  DragSet drag_set;
+  double drag_S = 0.0;  // the largest vertex value over all ranks; 0: off
+  std::vector<double> drag_sigma;  // the setting as given (public numbering): what hdg_get_drag returns
+  ckpt::Digest drag_dig[3];        // the coefficient planes, the target and the tags, as a checkpoint's fingerprint names them
+  bool drag_has_target = false;
+  const double* d_dragtab = nullptr;  // L_1, L_2
+  double *d_dforce = nullptr, *d_dfpart = nullptr;
+  double* d_dragS = nullptr;  // strips: 1 + size words for the collective maximum
+  bool drag_on() const { return drag_S > 0.0; }
+  bool vel_linear_on() const { return viscosity_on() || coriolis_on() || drag_on(); }
+  long drag_cells() const { return general ? (long)gm->nc : 2L * g.nx * g.ny; }
+  void drag_setup() {
+    if (d_dragtab) return;
+    if (general && comm->size > 1) throw std::string("drag on a general mesh: single rank only");
+    d_dragtab = upload(CoriolisTables(K).general());
+  }
+  void drag_release(DragSet& D) {
+    release_dev(D.coef); release_dev(D.region); release_dev(D.load);
+    D = DragSet{};
+  }
+  // out = sgn M^-1 D Q + load (null: none), or out += that (acc), on the owned rows
+  void drag_apply(const DragSet& D, const double* Q, double sgn, const double* load, bool acc, double* out) {
+    tally(LC_OTHER, ((acc ? 3.0 : 2.0) + (load ? 1.0 : 0.0)) * bQ() + 24.0 * (double)drag_cells());
+    auto go = [&](auto k, auto a, auto l) {
+      if (general) k_g_drag<k(), a(), l()><<<dim3((gm->nc + 63) / 64), 64, 0, stream>>>(gm->nc, d_dragtab, D.coef, sgn, Q, load, out);
+      else k_drag<k(), a(), l()><<<cell_grid(), bs(), 0, stream>>>(g, d_dragtab, D.coef, sgn, Q, load, out);
+    };
+    by_degree([&](auto k) {
+      if (acc) { if (load) go(k, std::true_type{}, std::true_type{}); else go(k, std::true_type{}, std::false_type{}); }
+      else { if (load) go(k, std::false_type{}, std::true_type{}); else go(k, std::false_type{}, std::false_type{}); }
+    });
+    fl.set(out, 0);
+  }
+  // the device form of a setting that drag_validate has passed; sigma not null.  Uses wQ1.
+  DragSet drag_build(const double* sigma, const double* target, const int* region) {
+    drag_setup();
+    DragSet D;
+    const long nc = drag_cells();
+    D.S = drag_bound(sigma, nc);
+    D.coef = const_cast<double*>(upload(general ? drag_pack_general(sigma, nc) : drag_pack_planes(sigma, g.nx, g.ny, g.R, GH)));
+    D.region = const_cast<int*>(upload_ints(general ? (region ? std::vector<int>(region, region + nc) : std::vector<int>((size_t)nc, 0))
+                                                    : drag_pack_regions(region, g.nx, g.ny, g.R, GH)));
+    bool any = false;
+    if (target)
+      for (long n = 0; n < NQb && !any; n++) any = target[n] != 0.0;
+    if (any) {
+      D.load = dalloc(NQ);
+      put_Q(target, wQ1);
+      drag_apply(D, wQ1, 1.0, nullptr, false, D.load);
+    }
+    return D;
+  }
+  void drag_check(const char* who, const double* sigma, const double* target, const int* region) const {
+    if (step_open) throw std::string(who) + ": a step is open (between hdg_begin_step and the end of the step)";
+    const std::string bad = drag_validate(sigma, drag_cells(), target, NQb, region);
+    if (!bad.empty()) throw std::string(who) + ": " + bad;
+  }
+  void set_drag(const double* sigma, const double* target, const int* region) {
+    if (step_open) throw std::string("hdg_set_drag: a step is open (between hdg_begin_step and the end of the step)");
+    if (general && comm->size > 1) throw std::string("drag on a general mesh: single rank only");
+    const long nc = drag_cells();
+    const std::string bad = drag_validate(sigma, nc, target, NQb, region);
+    double S = bad.empty() ? drag_bound(sigma, nc) : -1.0;
+    bool other = false;
+    if (comm->size > 1) {  // collective: the bound is a global maximum, and a fault anywhere refuses the call everywhere
+      if (!d_dragS) d_dragS = dalloc(1L + comm->size);
+      HIPCHECK(hipMemcpyAsync(d_dragS, &S, sizeof(double), hipMemcpyHostToDevice, stream));
+      comm->allgather(d_dragS, d_dragS + 1, 1, stream);
+      n_gather++;
+      std::vector<double> all((size_t)comm->size);
+      HIPCHECK(hipMemcpyAsync(all.data(), d_dragS + 1, sizeof(double) * all.size(), hipMemcpyDeviceToHost, stream));
+      HIPCHECK(hipStreamSynchronize(stream));
+      for (double x : all) { if (x < 0.0) other = true; else S = S < 0.0 ? S : std::max(S, x); }
+    }
+    if (!bad.empty()) throw "hdg_set_drag: " + bad;
+    if (other) throw std::string("hdg_set_drag: another rank refused its arrays");
+    std::vector<double> zeros;
+    if (!sigma && S > 0.0) { zeros.assign((size_t)(3 * nc), 0.0); sigma = zeros.data(); }  // a rank of a strip whose cells carry none
+    drag_release(drag_set);
+    drag_sigma.clear();
+    drag_has_target = false;
+    drag_S = S;
+    visc_valid = 0;
+    if (S == 0.0) return;  // off: the slot vectors stay allocated, nothing reads them
+    drag_set = drag_build(sigma, target, region);
+    visc_alloc();
+    drag_sigma.assign(sigma, sigma + 3 * nc);
+    drag_has_target = drag_set.load != nullptr;
+    drag_dig[0] = ckpt::digest_bytes(sigma, sizeof(double) * 3 * (size_t)nc);
+    if (drag_has_target) drag_dig[1] = ckpt::digest_bytes(target, sizeof(double) * (size_t)NQb);
+    const std::vector<int> tags = region ? std::vector<int>(region, region + nc) : std::vector<int>((size_t)nc, 0);
+    drag_dig[2] = ckpt::digest_bytes(tags.data(), sizeof(int) * tags.size());
+  }
+  // F[3 r + 0 .. 2] = (F_x, F_y, P) of region r for the modal field Q and the setting D; added over the ranks of a strip
+  void drag_force(const DragSet& D, const double* Q, double* F) {
+    const int nb = general ? (gm->nc + 127) / 128 : (int)cell_grid().x;
+    if (!d_dforce) { d_dforce = dalloc(HDG_DRAG_FORCE_NVAL); d_dfpart = dalloc((long)HDG_DRAG_FORCE_NVAL * nb); }
+    tally(LC_OTHER, ((D.load ? 2.0 : 1.0)) * bQ() + 28.0 * (double)drag_cells());
+    auto go = [&](auto k, auto l) {
+      if (general) k_g_drag_force<k(), l()><<<nb, 128, 0, stream>>>(gm->nc, ggeo.detJ, d_dragtab, D.coef, D.region, Q, D.load, d_dfpart);
+      else k_drag_force<k(), l()><<<cell_grid(), bs(), 0, stream>>>(g, d_dragtab, D.coef, D.region, Q, D.load, d_dfpart);
+    };
+    by_degree([&](auto k) { if (D.load) go(k, std::true_type{}); else go(k, std::false_type{}); });
+    tally(LC_OTHER, 0.0);
+    k_drag_force_finish<<<1, 256, 0, stream>>>(nb, d_dfpart, d_dforce);
+    if (comm->size > 1) comm->allreduce_sum(d_dforce, HDG_DRAG_FORCE_NVAL, stream);
+    HIPCHECK(hipMemcpyAsync(F, d_dforce, sizeof(double) * HDG_DRAG_FORCE_NVAL, hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
   }
   // hdg_imex.py:560 and the i = 0 term of _tracer_final_residual
   void tracer_begin_step() {
@@ -4505,6 +4629,7 @@ struct Engine {
     double out2[2];
     if (kmax > 0.0) { tracer_diffusion_number(out2); rates[1] = kmax * out2[0]; }
     if (visc_nu > 0.0) { viscosity_number(visc_nu, visc_wall, out2); rates[2] = visc_nu * out2[0]; }
+    if (drag_on()) rates[2] += drag_S;  // both spectra are real and non-positive: the rates add (section 26)
     if (cor_f0 != 0.0 || cor_beta != 0.0) rates[3] = coriolis_bound(cor_f0, cor_beta);
   }
   double propose_dt(const hdg_step_control& control, double t, double t_final) {
@@ -4708,6 +4833,11 @@ struct Engine {
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
     if (coriolis_on()) { f.add("coriolis_f0", cor_f0); f.add("coriolis_beta", cor_beta); }  // only with one of them != 0
+    if (drag_on()) {  // only while the term is on: the setting as it was given, by its digests (section 26)
+      f.add_u64("drag_sigma_d0", drag_dig[0].d0); f.add_u64("drag_sigma_d1", drag_dig[0].d1);
+      if (drag_has_target) { f.add_u64("drag_target_d0", drag_dig[1].d0); f.add_u64("drag_target_d1", drag_dig[1].d1); }
+      f.add_u64("drag_region_d0", drag_dig[2].d0); f.add_u64("drag_region_d1", drag_dig[2].d1);
+    }
     for (int w = 0; w < 4; w++)  // one line per side with a wall speed, and only then
       if (wall_u[w] != 0.0) f.add("wall_velocity[" + std::to_string(w) + "]", wall_u[w]);
     if (general) {
@@ -5934,6 +6064,52 @@ int hdg_apply_coriolis(hdg_handle* h, double f0, double beta, const double* Q, d
   E.zero(E.wQ2, E.NQ);
   E.coriolis_apply(E.wQ1, f0, beta, false, E.wQ2);
   E.get_Q(E.wQ2, out);
+  HDG_API_END(h)
+}
+
+// ---- linear drag (include/hdg_drag.h)
+int hdg_set_drag(hdg_handle* h, const double* sigma, const double* target, const int* region) {
+  HDG_API_BEGIN(h)
+  E.set_drag(sigma, target, region);
+  HDG_API_END(h)
+}
+int hdg_get_drag(hdg_handle* h, double* sigma, double out2[2]) {
+  HDG_API_BEGIN(h)
+  if (sigma) {
+    if (E.drag_on()) std::copy(E.drag_sigma.begin(), E.drag_sigma.end(), sigma);
+    else std::fill(sigma, sigma + 3 * E.drag_cells(), 0.0);
+  }
+  if (out2) { out2[0] = E.drag_S; out2[1] = E.drag_S * E.cfg.dt; }
+  HDG_API_END(h)
+}
+int hdg_apply_drag(hdg_handle* h, const double* sigma, const double* target, const double* Q, double* out) {
+  HDG_API_BEGIN(h)
+  if (!sigma || !Q || !out) throw std::string("null argument");
+  E.drag_check("hdg_apply_drag", sigma, target, nullptr);
+  hdg::Engine::DragSet D = E.drag_build(sigma, target, nullptr);
+  E.put_Q(Q, E.wQ1);
+  E.zero(E.wQ2, E.NQ);
+  E.drag_apply(D, E.wQ1, -1.0, D.load, false, E.wQ2);
+  E.get_Q(E.wQ2, out);
+  E.drag_release(D);
+  HDG_API_END(h)
+}
+int hdg_get_drag_force(hdg_handle* h, double F[12]) {
+  HDG_API_BEGIN(h)
+  if (!F) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_get_drag_force: a step is open");
+  std::fill(F, F + 12, 0.0);
+  if (E.drag_on()) E.drag_force(E.drag_set, E.curQ, F);
+  HDG_API_END(h)
+}
+int hdg_apply_drag_force(hdg_handle* h, const double* sigma, const double* target, const int* region, const double* Q, double F[12]) {
+  HDG_API_BEGIN(h)
+  if (!sigma || !Q || !F) throw std::string("null argument");
+  E.drag_check("hdg_apply_drag_force", sigma, target, region);
+  hdg::Engine::DragSet D = E.drag_build(sigma, target, region);
+  E.put_Q(Q, E.wQ1);
+  E.drag_force(D, E.wQ1, F);
+  E.drag_release(D);
   HDG_API_END(h)
 }
 

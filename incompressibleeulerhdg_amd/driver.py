@@ -54,7 +54,7 @@ from ._lib import DIAGNOSTICS, HDG_MAX_TRACERS, POINT_COLUMNS, WALL_SIDES
 from .auxilliary.callbacks import AnimationCallback
 from .auxilliary.logging import log_summary
 from .mesh import Function, FunctionSpace, PeriodicSquareMesh, UnitDiskMesh, UnitSquareMesh
-from .model_problems import Cavity, DoubleLayerShearFlow, KelvinHelmholtz, RotatingTaylorGreen, TaylorGreen
+from .model_problems import CylinderWake, DraggedTaylorGreen, Cavity, DoubleLayerShearFlow, KelvinHelmholtz, RotatingTaylorGreen, TaylorGreen
 from .output import VTKFile
 from .timesteppers import (
     IncompressibleEulerHDGIMEXARS2_232,
@@ -78,7 +78,7 @@ TIMESTEPPERS = {
 def build_parser():
     """Same flags and defaults as driver.py:26-176."""
     parser = argparse.ArgumentParser("Mesh specifications and polynomial degree")
-    parser.add_argument("--problem", choices=["taylorgreen", "kelvinhelmholtz", "shear", "cavity"], type=str, default="taylorgreen", help="model problem to solve")
+    parser.add_argument("--problem", choices=["taylorgreen", "kelvinhelmholtz", "shear", "cavity", "cylinder"], type=str, default="taylorgreen", help="model problem to solve")
     parser.add_argument("--nx", metavar="nx", type=int, default=8, help="number of grid cells in x-direction")
     parser.add_argument("--refinement", metavar="refinement", type=int, default=2, help="refinement level for unit disk mesh")
     parser.add_argument("--degree", metavar="degree", type=int, default=1, help="polynomial degree")
@@ -115,6 +115,13 @@ def build_parser():
     parser.add_argument("--coriolis", metavar="F", type=float, nargs="+", default=None,
                         help="rotation F0 [BETA]: the momentum equation gains - (F0 + BETA y) k x u, explicit in time (see the "
                              "printed rotation number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
+    parser.add_argument("--drag", metavar="R", type=float, default=None,
+                        help="uniform linear friction: the momentum equation gains - R u, explicit in time (see the printed drag "
+                             "number); with --problem taylorgreen the forcing keeps the manufactured solution exact")
+    parser.add_argument("--obstacle_drag", metavar="S", type=float, default=None,
+                        help="with --problem cylinder: sigma inside the disc and at the crest of the fringe (default: the value that "
+                             "puts (nu Lambda_u + S) dt at half the real-axis limit of the explicit tableau)")
+    parser.add_argument("--stream", metavar="U", type=float, default=None, help="with --problem cylinder: the free stream (U, 0) (default 1)")
     parser.add_argument("--buoyancy", metavar="B", type=float, nargs="+", default=None,
                         help="Boussinesq buoyancy (with --tracer_advection): the momentum equation gains sum_t B_t q_t g; one "
                              "value for all tracers or exactly --tracers values, 0 keeps a tracer passive; explicit in time")
@@ -341,6 +348,52 @@ def check_coriolis(args):
     if args.problem == "taylorgreen" and args.forcing == "constant":
         raise RuntimeError("--coriolis with --problem taylorgreen needs --forcing exponential (with constant forcing the "
                            "manufactured forcing is not separable)")
+
+
+def check_drag(args):
+    """--drag R and --problem cylinder [--obstacle_drag S] [--stream U], before any engine exists"""
+    if args.drag is not None:
+        if not np.isfinite(args.drag) or args.drag < 0:
+            raise RuntimeError(f"--drag {args.drag} is not a finite number >= 0")
+        if args.problem == "taylorgreen" and args.forcing == "constant":
+            raise RuntimeError("--drag with --problem taylorgreen needs --forcing exponential (with constant forcing the "
+                               "manufactured forcing is not separable)")
+        if args.problem == "taylorgreen" and args.coriolis is not None:
+            raise RuntimeError("--drag with --coriolis: the manufactured forcing of --problem taylorgreen covers one of the two")
+    if args.problem != "cylinder":
+        for name in ("obstacle_drag", "stream"):
+            if getattr(args, name) is not None:
+                raise RuntimeError(f"--{name} needs --problem cylinder")
+        return
+    if args.viscosity is None or not args.viscosity > 0:
+        raise RuntimeError("--problem cylinder needs --viscosity NU > 0 (the wake of a penalised body needs a viscous scale)")
+    if args.discretisation == "dg":
+        raise RuntimeError("--problem cylinder runs on the doubly periodic square, which the DG discretisation does not have")
+    if args.tracer_wall or args.wall_velocity or args.wall == "no_slip":
+        raise RuntimeError("--problem cylinder: the doubly periodic square has no walls")
+    if args.coriolis is not None and len(args.coriolis) == 2 and args.coriolis[1] != 0:
+        raise RuntimeError("--coriolis: BETA != 0 is not available on the doubly periodic square of --problem cylinder")
+    if args.obstacle_drag is not None and (not np.isfinite(args.obstacle_drag) or args.obstacle_drag <= 0):
+        raise RuntimeError(f"--obstacle_drag {args.obstacle_drag} is not a finite number > 0")
+    if args.stream is not None and (not np.isfinite(args.stream) or args.stream == 0):
+        raise RuntimeError(f"--stream {args.stream} is not a finite number != 0")
+
+
+def cylinder_drag(args, timestepper):
+    """The CylinderWake of the run and its obstacle_drag.  The default puts (nu Lambda_u + S) dt at half the real-axis limit of
+    the explicit tableau; a viscous number that is above half the limit on its own is refused (before the first step)."""
+    from .timesteppers.common import explicit_stability_limit
+
+    eng = timestepper._engine
+    s = eng.nstages
+    limit = explicit_stability_limit(list(eng.cfg.a_expl)[:s * s], list(eng.cfg.b_expl)[:s])
+    viscous = eng.viscosity_number()[1]
+    if viscous >= 0.5 * limit:
+        raise RuntimeError(f"--problem cylinder: the viscous diffusion number {viscous:.6g} alone is above half the stability limit "
+                           f"{limit:.6g} of the explicit tableau, which leaves no room for the penalisation; reduce --dt or --viscosity")
+    S = args.obstacle_drag if args.obstacle_drag is not None else (0.5 * limit - viscous) / args.dt
+    L = 2 * np.pi
+    return CylinderWake(timestepper._V_Q, timestepper._V_p, L, L / args.nx, S, stream=1.0 if args.stream is None else args.stream)
 
 
 def check_checkpoint(args):
@@ -598,6 +651,7 @@ def main(argv=None):
     check_viscosity(args)
     wall_velocity(args)
     check_coriolis(args)
+    check_drag(args)
     check_checkpoint(args)
     check_adaptive(args)
     check_start_from(args)
@@ -630,6 +684,8 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
         several["wall_velocity"] = wall_velocity(args)
     if args.coriolis is not None:
         several["coriolis"] = coriolis_pair(args)
+    if args.drag is not None and args.problem != "cylinder":  # the wake sets its own field once Lambda_u is known
+        several["drag"] = args.drag
     if args.discretisation == "dg":
         # driver.py:203-213
         assert not args.use_projection_method, "Can not use projection method with DG discretsation"
@@ -669,13 +725,18 @@ def start_from(args, ranks, timestepper):
 
 def _run(args, ranks):
     callbacks = [AnimationCallback("evolution.pvd")] if args.animation else None  # driver.py:187
-    if args.problem == "shear":
+    if args.problem in ("shear", "cylinder"):
         mesh = PeriodicSquareMesh(args.nx, args.nx, L=2 * np.pi, quadrilateral=False)  # driver.py:182-183
     elif args.problem == "kelvinhelmholtz":
         mesh = UnitDiskMesh(refinement_level=args.refinement)  # driver.py:184-185
     else:
         mesh = UnitSquareMesh(args.nx, args.nx, quadrilateral=False)  # driver.py:181
     timestepper = make_timestepper(args, ranks, mesh, args.degree, args.dt, callbacks)
+    wake = None
+    if args.problem == "cylinder":
+        wake = cylinder_drag(args, timestepper)
+        r = args.drag or 0.0
+        timestepper.set_drag((lambda x, y: wake.sigma(x, y) + r) if r else wake.sigma, wake.target, wake.region)
 
     print("+-------------------------------------------------+")
     print("! timesteppers for incompressible Euler equations !")
@@ -715,6 +776,14 @@ def _run(args, ranks):
         print(f"coriolis = {' '.join(repr(x) for x in args.coriolis)}")
         print(f"rotation number F dt = {number:.6g} (growth per inertial period "
               f"{(timestepper.rotation_growth * 2 * np.pi / number if number > 0 else 0.0):.6g})")
+    if args.drag is not None:
+        print(f"drag = {args.drag!r}")
+    if wake is not None:
+        print(f"obstacle drag = {wake.S!r}")
+        print(f"stream = {wake.U!r}")
+    if args.drag is not None or wake is not None:
+        S, number = timestepper._engine.drag_number()
+        print(f"drag: S = {S:.6g}, S dt = {number:.6g}")
     print(f"timestepping method = {timestepper.label}")
     print()
 
@@ -752,6 +821,11 @@ def _run(args, ranks):
         model_problem = KelvinHelmholtz(timestepper._V_Q, timestepper._V_p)  # driver.py:336-337
     elif args.problem == "cavity":
         model_problem = Cavity(timestepper._V_Q, timestepper._V_p)
+    elif args.problem == "cylinder":
+        model_problem = wake
+    elif args.drag is not None:
+        model_problem = DraggedTaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa,
+                                           viscosity=args.viscosity or 0.0, drag=args.drag)
     else:
         if args.coriolis is not None:
             model_problem = RotatingTaylorGreen(timestepper._V_Q, timestepper._V_p, args.forcing, args.kappa,
@@ -823,10 +897,15 @@ def _run(args, ranks):
         for side, row in zip(WALL_SIDES, eng.wall_force()):
             print(f"wall force {side} = {float(row[0])!r} {float(row[1])!r}")
         print()
+    if wake is not None:  # the force on the body is the negative of the term's force on the fluid of region 1
+        force = eng.drag_force()[1]
+        cd, cl = wake.coefficients(force)
+        print(f"disc: force on the body = {float(-force[0])!r} {float(-force[1])!r}, C_D = {float(cd)!r}, C_L = {float(cl)!r}")
+        print()
     log_summary()
     print(f"state digest = {state_digest[0]:016x}{state_digest[1]:016x}")
     print()
-    if args.problem in ("shear", "kelvinhelmholtz", "cavity"):
+    if args.problem in ("shear", "kelvinhelmholtz", "cavity", "cylinder"):
         # no exact solution (the reference's driver calls model_problem.solution, which these problems lack: it stops here
         # with an AttributeError); write the final fields
         if args.output:

@@ -8,7 +8,7 @@ import numpy as np
 
 from .mesh import Function
 
-__all__ = ["TaylorGreen", "RotatingTaylorGreen", "KelvinHelmholtz", "DoubleLayerShearFlow", "SeparableForcing"]
+__all__ = ["TaylorGreen", "RotatingTaylorGreen", "DraggedTaylorGreen", "CylinderWake", "KelvinHelmholtz", "DoubleLayerShearFlow", "SeparableForcing"]
 
 
 class SeparableForcing:
@@ -105,6 +105,81 @@ class RotatingTaylorGreen(TaylorGreen):
             return c * qx - fc * qy, c * qy + fc * qx  # k x Q = (-Q_y, Q_x)
 
         return SeparableForcing(self.V_Q.interpolate(profile), lambda t: np.exp(-k * t))
+
+
+class DraggedTaylorGreen(TaylorGreen):
+    """The Taylor-Green vortex under a drag towards rest: drag = sigma(x, y) >= 0 of - sigma u.
+
+    The solution is TaylorGreen's: the forcing gains + sigma Q, which cancels the term.  With the exponential time factor the
+    forcing stays separable, profile (-kappa + 2 pi^2 nu + sigma) Q_s times exp(-kappa t); the discrete term matches the profile
+    exactly for a sigma that is linear over the square.  With forcing="constant" the two parts carry different time factors, so
+    that combination is refused.  drag=None is TaylorGreen itself."""
+
+    def __init__(self, V_Q, V_p, forcing="exponential", kappa=0.5, viscosity=0.0, drag=None):
+        if drag is not None and forcing != "exponential":
+            raise ValueError("DraggedTaylorGreen: forcing='constant' is not separable with a drag (the two time factors differ)")
+        super().__init__(V_Q, V_p, forcing, kappa, viscosity)
+        self.drag = (lambda x, y, r=float(drag): r + 0.0 * x) if drag is not None and not callable(drag) else drag
+
+    def f_rhs(self):
+        if self.drag is None:
+            return super().f_rhs()
+        k, c = self.kappa, -self.kappa + 2.0 * np.pi ** 2 * self.viscosity
+
+        def profile(x, y):
+            qx, qy = self.Q_stationary(x, y)
+            s = self.drag(x, y)
+            return (c + s) * qx, (c + s) * qy
+
+        return SeparableForcing(self.V_Q.interpolate(profile), lambda t: np.exp(-k * t))
+
+
+class CylinderWake:
+    """Flow past a disc on the doubly periodic square [0, L]^2 by volume penalisation: a uniform stream
+    (U, 0); a disc of radius L / 16 at (L / 4, L / 2) held at rest by sigma = S inside, with a tanh edge one cell (h) wide
+    (region 1); a sin^2 fringe over the last eighth in x that drives the flow back to the stream (region 2, u_s = (U, 0)), which
+    makes the periodic box an open channel.  sigma, target and region are what Engine.set_drag takes.  No exact solution."""
+
+    def __init__(self, V_Q, V_p, L, h, obstacle_drag, stream=1.0, fringe_drag=None):
+        self.V_Q, self.V_p = V_Q, V_p
+        self.L, self.h, self.S, self.U = float(L), float(h), float(obstacle_drag), float(stream)
+        self.fringe = self.S if fringe_drag is None else float(fringe_drag)
+        self.radius, self.centre = self.L / 16.0, (self.L / 4.0, self.L / 2.0)
+        self.Q_initial = lambda x, y: (self.U + 0.0 * x, 0.0 * y)
+        self.p_initial = lambda x, y: 0.0 * x
+
+    def _disc(self, x, y):
+        r = np.hypot(x - self.centre[0], y - self.centre[1])
+        return 0.5 * (1.0 - np.tanh((r - self.radius) / (0.5 * self.h)))
+
+    def _fringe(self, x):
+        z = (x - 0.875 * self.L) / (0.125 * self.L)
+        return np.where(z > 0.0, np.sin(np.pi * np.clip(z, 0.0, 1.0)) ** 2, 0.0)
+
+    def sigma(self, x, y):
+        disc = self._disc(x, y)
+        return self.S * np.where(disc > 1e-8, disc, 0.0) + self.fringe * self._fringe(x)  # exactly zero away from both
+
+    def target(self, x, y):
+        return self.U * (x >= (0.875 - 1e-12) * self.L), 0.0 * y  # the fringe's own edge included: sigma vanishes there, not u_s
+
+    def region(self, x, y):
+        return np.where(self._fringe(x) > 0.0, 2, np.where(self._disc(x, y) > 1e-8, 1, 0))
+
+    def coefficients(self, force):
+        """(C_D, C_L) from the force on the fluid of region 1, Engine.drag_force()[1]: the body feels the negative"""
+        q = 0.5 * self.U ** 2 * 2.0 * self.radius
+        return -force[0] / q, -force[1] / q
+
+    def initial_condition(self):
+        return self.Q_initial, self.p_initial
+
+    def f_rhs(self):
+        """Zero forcing."""
+        return None
+
+    def solution(self, t, integrate_pressure=None):
+        return None
 
 
 class KelvinHelmholtz:

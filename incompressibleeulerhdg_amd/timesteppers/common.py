@@ -158,6 +158,13 @@ class IncompressibleEuler(ABC):
             raise ValueError('wall_velocity= needs viscosity= and wall="no_slip"')
         # coriolis=: f0 or (f0, beta) of the explicit Coriolis term - (f0 + beta y) k x u; None: no call at all
         self._coriolis = engine_options.pop("coriolis", None)
+        # drag=, drag_target=, drag_region=: sigma, u_s and the region tags of the explicit damping - sigma (u - u_s) (DESIGN.md
+        # section 26), each as Engine.set_drag takes it; drag=None: no call at all
+        self._drag = engine_options.pop("drag", None)
+        self._drag_target = engine_options.pop("drag_target", None)
+        self._drag_region = engine_options.pop("drag_region", None)
+        if self._drag is None and (self._drag_target is not None or self._drag_region is not None):
+            raise ValueError("drag_target= and drag_region= need drag=")
         self._engine_options = engine_options
         self._engine = None
         # common.py:72-73
@@ -211,7 +218,19 @@ class IncompressibleEuler(ABC):
             self.rotation_limit = explicit_imaginary_limit(opts["a_expl"], opts["b_expl"])
             self.rotation_growth = explicit_imaginary_growth(opts["a_expl"], opts["b_expl"], number)
             warn_if_rotation_unstable(number, self.rotation_growth, self.rotation_limit, self.rotation_growth_limit)
+        if self._drag is not None:  # independent of the other terms
+            self.set_drag(self._drag, self._drag_target, self._drag_region)
         return self._engine
+
+    def set_drag(self, sigma, target=None, region=None):
+        """Engine.set_drag and the stability report: the spectrum of - M^-1 D is real and non-positive like the viscous one and
+        the two add, so (nu Lambda_u + S) dt is held against the real-axis limit of the explicit tableau."""
+        eng = self._engine
+        eng.set_drag(sigma, target, region)
+        s = eng.nstages
+        self.drag_limit = explicit_stability_limit(list(eng.cfg.a_expl)[:s * s], list(eng.cfg.b_expl)[:s])
+        viscous = eng.viscosity_number()[1] if eng.viscosity()[0] > 0 else 0.0
+        warn_if_diffusion_unstable(viscous + eng.drag_number()[1], self.drag_limit, what="drag")
 
     def _as_nodal_velocity(self, Q):
         """Accept a callable (x, y) -> (ux, uy) [the reference passes UFL expressions], a Function or
@@ -397,8 +416,8 @@ class IncompressibleEuler(ABC):
 
     def _step_caps(self, rates):
         """The upper limits of dt from the explicit terms, in the order of hdg_step_control.caps: the real-axis limit of the
-        tableau over kappa_max Lambda and over nu Lambda_u, its imaginary-axis limit over F (only when that limit is
-        positive); None: no limit."""
+        tableau over kappa_max Lambda and over nu Lambda_u (plus S while the drag is on: rates[2] is the rate of the whole
+        velocity-linear part), its imaginary-axis limit over F (only when that limit is positive); None: no limit."""
         cfg, s = self._engine.cfg, self._engine.nstages  # the tableau the engine steps with: a term may have been switched
         a_expl, b_expl = list(cfg.a_expl)[:s * s], list(cfg.b_expl)[:s]  # on through the engine, not through the constructor
         caps = [None, None, None]
