@@ -25,6 +25,7 @@ TRACER_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_
 MOVING_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_moving_walls.h"))
 ADAPTIVE_DT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_adaptive_dt.h"))
 DRAG_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_drag.h"))
+STREAMFUNCTION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_streamfunction.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -97,7 +98,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER, DRAG_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER, DRAG_HEADER, STREAMFUNCTION_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -273,6 +274,16 @@ DRAG_SIGNATURES = {
 }
 HDG_DRAG_REGIONS = 4
 
+# stream function of the velocity: the symbols include/hdg_streamfunction.h declares, in a table of their own like the ten above
+STREAMFUNCTION_SIGNATURES = {
+    "hdg_streamfunction": [_h, _dp, C.c_double, _dp, _dp],
+    "hdg_apply_cg_stiffness": [_h, _dp, _dp],
+    "hdg_psi_transfer": [_h, C.c_int, _dp, _dp],
+    "hdg_apply_psi_preconditioner": [_h, C.c_int, _dp, _dp],
+    "hdg_psi_vertex_count": [_h, _lp],
+}
+STREAMFUNCTION_INFO = ("iterations", "residual", "defect", "u_l2", "mean_flow_x", "mean_flow_y", "psi_min", "psi_max")
+
 
 def step_control(cfl, dt_min=None, dt_max=None, grow=None, band=None, caps=None):
     """The hdg_step_control of the given settings; None: the default of the rule (a zeroed field)"""
@@ -334,7 +345,7 @@ def load_library():
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
             list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()) + \
-            list(ADAPTIVE_DT_SIGNATURES.items()) + list(DRAG_SIGNATURES.items()):
+            list(ADAPTIVE_DT_SIGNATURES.items()) + list(DRAG_SIGNATURES.items()) + list(STREAMFUNCTION_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -969,6 +980,51 @@ class Engine:
         Q = None if Q is None else _arr(Q, self.shape_Q)
         out = np.empty(self.cg_size())
         self._ck(self.lib.hdg_vorticity(self.h, _ptr(Q), _ptr(out)))
+        return out
+
+    # --- stream function (include/hdg_streamfunction.h)
+    def streamfunction(self, Q=None, rtol=1e-12):
+        """(psi, info): the stream function of the nodal velocity-space field Q (None: the current velocity) at the dofs of
+        cg_coordinates(), and a dict with the entries of STREAMFUNCTION_INFO (iterations as an int).  Between steps only."""
+        Q = None if Q is None else _arr(Q, self.shape_Q)
+        psi = np.empty(self._psi_sizes()[1])
+        info = np.zeros(8)
+        self._ck(self.lib.hdg_streamfunction(self.h, _ptr(Q), float(rtol), _ptr(psi), _ptr(info)))
+        out = dict(zip(STREAMFUNCTION_INFO, (float(v) for v in info)))
+        out["iterations"] = int(info[0])
+        return psi, out
+
+    def _psi_sizes(self):
+        """(vertices, n_cg); the vertex count first, so that a refusal is the stream function's own (a strip: HDG_ERR_UNSUPPORTED)"""
+        return self.psi_vertex_count(), self.cg_size()
+
+    def psi_vertex_count(self):
+        n = C.c_long()
+        self._ck(self.lib.hdg_psi_vertex_count(self.h, C.byref(n)))
+        return n.value
+
+    def apply_cg_stiffness(self, x):
+        """K x, K the stiffness matrix of the continuous space (test hook; it sets nothing)."""
+        ncg = self._psi_sizes()[1]
+        x = _arr(x, (ncg,))
+        out = np.empty(ncg)
+        self._ck(self.lib.hdg_apply_cg_stiffness(self.h, _ptr(x), _ptr(out)))
+        return out
+
+    def psi_transfer(self, values, transpose=False):
+        """The nested P1 interpolation P from the mesh vertices to the continuous space, or its transpose (test hook)."""
+        nv, ncg = self._psi_sizes()
+        values = _arr(values, (ncg if transpose else nv,))
+        out = np.empty(nv if transpose else ncg)
+        self._ck(self.lib.hdg_psi_transfer(self.h, 1 if transpose else 0, _ptr(values), _ptr(out)))
+        return out
+
+    def apply_psi_preconditioner(self, r, form=0):
+        """B r, B the preconditioner of the stream-function solve (form 0) or the diagonal alone (form 1) (test hook)."""
+        ncg = self._psi_sizes()[1]
+        r = _arr(r, (ncg,))
+        out = np.empty(ncg)
+        self._ck(self.lib.hdg_apply_psi_preconditioner(self.h, int(form), _ptr(r), _ptr(out)))
         return out
 
     def cg_to_broken(self, values):

@@ -28,8 +28,11 @@ class Callback(ABC):
 class AnimationCallback(Callback):
     """Save fields to disk (callbacks.py:30-85)."""
 
-    def __init__(self, filename):
+    with_streamfunction = False  # AnimationCallback(filename, streamfunction=True): psi next to the vorticity
+
+    def __init__(self, filename, streamfunction=False):
         self.filename = filename
+        self.with_streamfunction = bool(streamfunction)  # psi of every time level next to the vorticity (hdg_streamfunction)
         self._V_vort = None
         self.reset()
 
@@ -47,8 +50,19 @@ class AnimationCallback(Callback):
         omega_cg = eng.vorticity(Q.dat.data)
         return Function(self._V_vort, eng.cg_to_broken(omega_cg), "vorticity")
 
+    def streamfunction(self, Q):
+        """psi in CG_{k+1} with (grad psi, grad tau) = (Q, curl tau), on the same node set."""
+        V_Q = Q.function_space()
+        eng = V_Q._engine
+        if self._V_vort is None or self._V_vort.mesh() is not V_Q.mesh():
+            self._V_vort = FunctionSpace(V_Q.mesh(), "CG", V_Q.degree, V_Q.coordinates)
+        psi, _ = eng.streamfunction(Q.dat.data)
+        return Function(self._V_vort, eng.cg_to_broken(psi), "streamfunction")
+
     def __call__(self, Q, p, t, q_tracer=None):
         fields = [Q, p, self.vorticity(Q)]
+        if self.with_streamfunction:
+            fields.append(self.streamfunction(Q))
         if isinstance(q_tracer, (list, tuple)):  # several tracers (n_tracers > 1): every member, by its own name
             fields.extend(q_tracer)
         elif q_tracer is not None:

@@ -49,6 +49,7 @@ __device__ __forceinline__ long cg_dof(const CgTabs& C, int type, int I, int J, 
 //            MODE 1: y = Vinv^T x_d          (x: broken velocity, modal; component d)   -> right-hand side of the projection
 //            MODE 2: x_d = Vinv * (nodal values gathered from cg)                        -> the projection, modal, component d
 //            MODE 3: y = Vinv^T w,  w_m = -int_K (d_x psi_m Q_y - d_y psi_m Q_x) + int_{dK on boundary} psi_m (n x Q)
+//            MODE 4: MODE 3 without the boundary term: the right-hand side of the stream function (hdg_streamfunction.hpp)
 // y: scalar cell vector with NU planes y[n*Nc + c]
 template <int K, int MODE>
 __global__ __launch_bounds__(128) void k_cg_cell(Geo g, CgTabs C, DevTables T, const double* __restrict__ Mloc, const double* __restrict__ Vinv,
@@ -102,6 +103,7 @@ __global__ __launch_bounds__(128) void k_cg_cell(Geo g, CgTabs C, DevTables T, c
     }
 #pragma unroll
     for (int e = 0; e < 3; e++) {
+      if (MODE == 4) break;
       long cn;
       if (nbr(s, e, i, j, g, cn)) continue;
       // boundary edge: + int_e psi_m (n_x Q_y - n_y Q_x), outward normal = sig * n_e

@@ -38,6 +38,7 @@
 #include "../../include/hdg_drag.h"
 #include "../../include/hdg_moving_walls.h"
 #include "../../include/hdg_adaptive_dt.h"
+#include "../../include/hdg_streamfunction.h"
 #include "hdg_options.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
@@ -48,6 +49,7 @@
 #include "hdg_trace_tile.hpp"
 #include "hdg_trace_tile3.hpp"
 #include "hdg_cg.hpp"
+#include "hdg_streamfunction.hpp"
 #include "hdg_tables.hpp"
 #include "hdg_mfma_pack.hpp"
 #include "hdg_small_dense.hpp"
@@ -584,6 +586,8 @@ struct Engine {
     if (cstream) { (void)hipStreamDestroy(cstream); cstream = nullptr; }
     if (h_cgm) { (void)hipHostFree(h_cgm); h_cgm = nullptr; }
     for (int q = 0; q < 2; q++) if (cgm_ev[q]) { (void)hipEventDestroy(cgm_ev[q]); cgm_ev[q] = nullptr; }
+    if (psi_h) { (void)hipHostFree(psi_h); psi_h = nullptr; }
+    for (int q = 0; q < 2; q++) if (psi_ev[q]) { (void)hipEventDestroy(psi_ev[q]); psi_ev[q] = nullptr; }
     if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
     delete tab;
     tab = nullptr;
@@ -3515,6 +3519,190 @@ struct Engine {
     by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_b); });
     cg_solve();
   }
+  // ================================================================== stream function (hdg_streamfunction.hpp)
+  // psi in CG_{k+1} with (grad psi, grad tau) = int (u_x d_y tau - u_y d_x tau) dx: conjugate gradients on the stiffness matrix,
+  // preconditioned by the diagonal plus one V-cycle of the P1 vertex grid.  Structured meshes on one rank.  Built on first use; the
+  // vectors are the scratch vectors of the mass solves (cg_rr, cg_zz, cg_pp, cg_Ap2; result in cg_x), the vertex grid is vplan's.
+  PsiTabs psit;
+  bool psi_ready = false;
+  const double *psi_Kloc = nullptr, *psi_Iphi = nullptr, *psi_Dxy = nullptr;
+  double *psi_dg = nullptr, *psi_part = nullptr, *psi_sc = nullptr, *psi_h = nullptr;
+  hipEvent_t psi_ev[2] = {nullptr, nullptr};
+  int psi_nb = 0;
+  // the launch tallies as they were: the V-cycle and the fills count themselves, and a diagnostic between two steps must not
+  // show in the census of the step path
+  struct TallyGuard {
+    Engine& e;
+    long calls[HDG_N_LAUNCH_CLASSES];
+    double bytes[HDG_N_LAUNCH_CLASSES];
+    explicit TallyGuard(Engine& e_) : e(e_) { std::memcpy(calls, e.lc_calls, sizeof(calls)); std::memcpy(bytes, e.lc_bytes, sizeof(bytes)); }
+    ~TallyGuard() { std::memcpy(e.lc_calls, calls, sizeof(calls)); std::memcpy(e.lc_bytes, bytes, sizeof(bytes)); }
+  };
+  void psi_setup() {
+    cg_setup();
+    if (psi_ready) return;
+    if (general || comm->size > 1) throw std::string("the stream function is implemented for structured meshes on a single rank");
+    const int p = K + 1;
+    std::vector<real> xi, eta;
+    triangleNodes(p, cfg.equispaced_nodes, xi, eta);
+    std::vector<real> gl = cfg.equispaced_nodes ? std::vector<real>() : gllPoints(p);
+    if (cfg.equispaced_nodes) for (int q = 0; q <= p; q++) gl.push_back((real)q / p);
+    std::memset(&psit, 0, sizeof(psit));
+    for (int t = 0; t < p - 1; t++) psit.et[t] = (double)gl[t + 1];
+    for (int sh = 0; sh < 2; sh++)
+      for (int q = 0; q < cgt.nint; q++) {
+        const int n = cgt.intr[sh][q];
+        psit.plam[sh][q][0] = (double)((real)1 - xi[n] - eta[n]);
+        psit.plam[sh][q][1] = (double)xi[n];
+        psit.plam[sh][q][2] = (double)eta[n];
+      }
+    for (int e = 0; e < 6; e++) {  // the vertex an entry of CgTabs::vtx stands for is local node vtx[e][3] of its cell
+      const short* f = cgt.vtx[e];
+      const int slot = xi[f[3]] > 0.5 ? 1 : eta[f[3]] > 0.5 ? 2 : 0;
+      for (int q = 0; q < cgt.nint; q++) psit.vlam[e][q] = psit.plam[f[0]][q][slot];
+    }
+    // element stiffness matrices in the nodal basis (phi_a = sum_m Vinv[m][a] psi_m) and the integrals of the modal basis
+    dvec Kl((size_t)2 * NU * NU, 0.0), Ip((size_t)2 * NU, 0.0), Dn((size_t)4 * NU * NU, 0.0);
+    for (int sh = 0; sh < 2; sh++) {
+      std::vector<real> gx((size_t)tab->nqc * NU, 0), gy((size_t)tab->nqc * NU, 0);
+      for (int q = 0; q < tab->nqc; q++)
+        for (int a = 0; a < NU; a++)
+          for (int m = 0; m < NU; m++) {
+            gx[(size_t)q * NU + a] += (real)tab->Vuinv[m * NU + a] * tab->cGx[sh][q * NU + m];
+            gy[(size_t)q * NU + a] += (real)tab->Vuinv[m * NU + a] * tab->cGy[sh][q * NU + m];
+          }
+      for (int a = 0; a < NU; a++)
+        for (int b = 0; b < NU; b++) {
+          real acc = 0;
+          for (int q = 0; q < tab->nqc; q++)
+            acc += (real)tab->cw[q] * (gx[(size_t)q * NU + a] * gx[(size_t)q * NU + b] + gy[(size_t)q * NU + a] * gy[(size_t)q * NU + b]);
+          Kl[((size_t)sh * NU + a) * NU + b] = (double)acc;
+        }
+      for (int l = 0; l < NU; l++) {
+        real acc = 0;
+        for (int q = 0; q < tab->nqc; q++) acc += (real)tab->cw[q] * tab->cPhi[sh][q * NU + l];
+        Ip[(size_t)sh * NU + l] = (double)acc;
+        for (int n = 0; n < NU; n++) {  // mode l of d_x phi_n, d_y phi_n (the basis is orthonormal)
+          real ax = 0, ay = 0;
+          for (int q = 0; q < tab->nqc; q++) {
+            ax += (real)tab->cw[q] * gx[(size_t)q * NU + n] * tab->cPhi[sh][q * NU + l];
+            ay += (real)tab->cw[q] * gy[(size_t)q * NU + n] * tab->cPhi[sh][q * NU + l];
+          }
+          Dn[((size_t)(2 * sh) * NU + l) * NU + n] = (double)ax;
+          Dn[((size_t)(2 * sh + 1) * NU + l) * NU + n] = (double)ay;
+        }
+      }
+    }
+    psi_Kloc = upload(Kl);
+    psi_Iphi = upload(Ip);
+    psi_Dxy = upload(Dn);
+    psi_dg = dalloc(cgt.ncg);
+    psi_nb = std::min(std::min(dot_blocks, vec_blocks(cgt.ncg)), 1024);
+    psi_part = dalloc(std::max<long>(4L * cell_grid().x, 2L * psi_nb));
+    psi_sc = dalloc(32);
+    HIPCHECK(hipHostMalloc((void**)&psi_h, sizeof(double) * 8));
+    for (int q = 0; q < 2; q++) HIPCHECK(hipEventCreateWithFlags(&psi_ev[q], hipEventDisableTiming));
+    {  // diag(K): the gather of the diagonals of the element matrices
+      dvec dgv((size_t)NU * g.Nc, 0.0);
+      const long plane = (long)g.R * g.nx;  // cells of one shape (rowbase)
+      for (int n = 0; n < NU; n++)
+        for (long cc = 0; cc < g.Nc; cc++) dgv[(size_t)n * g.Nc + cc] = Kl[((size_t)(cc / plane) * NU + n) * NU + n];
+      HIPCHECK(hipMemcpyAsync(cg_y, dgv.data(), sizeof(double) * dgv.size(), hipMemcpyHostToDevice, stream));
+      by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, psi_dg); });
+      HIPCHECK(hipStreamSynchronize(stream));
+    }
+    if (vplan.lev.empty()) {  // a configuration whose trace preconditioner has no vertex grid: the same plan, built here
+      vplan = vertex_plan(g.nx, periodic, opt);
+      for (const VLevel& v : vplan.lev) { mg_x.push_back(dalloc(v.nv)); mg_b.push_back(dalloc(v.nv)); mg_r.push_back(dalloc(v.nv)); }
+      build_dense_tail();
+    }
+    psi_ready = true;
+  }
+  long psi_vertices() const { return vplan.lev[0].nv; }
+  void psi_stiff(const double* x, double* y) {  // y = K x
+    by_degree([&](auto k) { k_psi_stiff<k()><<<cell_grid(), bs(), 0, stream>>>(g, cgt, psi_Kloc, x, cg_y); });
+    by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, y); });
+  }
+  void psi_restrict(const double* r, double* rc) {  // rc = P^T r on the vertex grid
+    by_degree([&](auto k) { k_psi_restrict<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, psit, r, rc); });
+  }
+  void psi_prolong(const double* xc, const double* r, double* out) {  // out = r / diag(K) + P xc (either part may be absent)
+    by_degree([&](auto k) { k_psi_prolong<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, psit, xc, r, psi_dg, out); });
+  }
+  // z = B r.  Default: r / diag(K) + P V(P^T r), V one cycle of the vertex grid; jacobi: the first term alone
+  void psi_precond(bool jacobi, const double* r, double* z) {
+    if (jacobi) { psi_prolong(nullptr, r, z); return; }
+    psi_restrict(r, mg_b[0]);
+    vcycle(vplan, 0, nullptr);
+    psi_prolong(mg_x[0], r, z);
+  }
+  void psi_dot(const double* a, const double* b, int mode, double tol2, double* hflag) {
+    k_psi_dot<<<psi_nb, HDG_PSI_BLOCK, 0, stream>>>(cgt.ncg, a, b, psi_part);
+    k_psi_scalars<<<1, HDG_PSI_BLOCK, 0, stream>>>(psi_nb, mode, tol2, psi_part, psi_sc, hflag);
+  }
+  // the stream function of a broken velocity (modal, device); gauged result in cg_x, info as in include/hdg_streamfunction.h
+  void streamfunction(const double* vel_in, double rtol, double* info) {
+    psi_setup();
+    const long n = cgt.ncg;
+    const bool jacobi = opt.psi_jacobi;
+    const double tol2 = rtol * rtol;
+    const int nvb = vec_blocks(n);
+    by_degree([&](auto k) { k_cg_cell<k(), 4><<<cell_grid(), bs(), 0, stream>>>(g, cgt, dt, cg_Mloc, dt.Vuinv, cg_Wx[0], cg_Wy[0], cg_Wx[1], cg_Wy[1],
+                                                                     cg_Eb, nullptr, const_cast<double*>(vel_in), 0, cg_y); });
+    by_degree([&](auto k) { k_cg_gather<k()><<<corner_grid_all(), bs(), 0, stream>>>(g_all, cgt, cg_y, cg_rr); });
+    // the right-hand side sums to zero up to rounding; what is left would be an inconsistent part no iteration removes
+    k_psi_dot<<<psi_nb, HDG_PSI_BLOCK, 0, stream>>>(n, cg_rr, nullptr, psi_part);
+    k_psi_finish<1><<<1, HDG_PSI_BLOCK, 0, stream>>>(psi_nb, psi_part, psi_sc + 8);
+    k_psi_shift_mean<<<nvb, 256, 0, stream>>>(n, psi_sc + 8, cg_rr);
+    HIPCHECK(hipMemsetAsync(cg_x, 0, sizeof(double) * n, stream));
+    psi_precond(jacobi, cg_rr, cg_zz);
+    psi_dot(cg_rr, cg_zz, 2, tol2, psi_h);
+    HIPCHECK(hipStreamSynchronize(stream));
+    int its = 0;
+    double rel2 = 0.0;
+    if (!(psi_h[1] == psi_h[1])) throw NotConverged{"stream function: the right-hand side is not finite"};
+    if (psi_h[0] != 1.0) {
+      bool done = false;
+      k_psi_dir<<<nvb, 256, 0, stream>>>(n, psi_sc, cg_zz, cg_pp);
+      for (int it = 1; it <= 2001 && !done; it++) {
+        psi_stiff(cg_pp, cg_Ap2);
+        psi_dot(cg_pp, cg_Ap2, 0, tol2, nullptr);
+        k_psi_update<<<nvb, 256, 0, stream>>>(n, psi_sc, cg_pp, cg_Ap2, cg_x, cg_rr);
+        psi_precond(jacobi, cg_rr, cg_zz);
+        psi_dot(cg_rr, cg_zz, 1, tol2, psi_h + 4 * (it & 1));
+        HIPCHECK(hipEventRecord(psi_ev[it & 1], stream));
+        k_psi_dir<<<nvb, 256, 0, stream>>>(n, psi_sc, cg_zz, cg_pp);
+        if (it >= 2) {  // the flag of the previous iteration has arrived by now; x has taken one more (harmless) step
+          HIPCHECK(hipEventSynchronize(psi_ev[(it - 1) & 1]));
+          const double* f = psi_h + 4 * ((it - 1) & 1);
+          if (!(f[1] == f[1])) throw NotConverged{"stream function: NaN residual"};
+          if (f[0] == 1.0) { its = it - 1; rel2 = f[2] > 0.0 ? f[1] / f[2] : 0.0; done = true; }
+        }
+      }
+      if (!done) throw NotConverged{"stream function: the conjugate gradient iteration did not converge in 2000 iterations"};
+    }
+    // gauge (mean over the boundary vertices | over all vertices of the periodic square), extrema, defect and mean flow
+    k_psi_gauge_mean<<<1, HDG_PSI_BLOCK, 0, stream>>>(g.nx, periodic ? 0 : 1, cg_x, psi_sc + 8);
+    k_psi_shift<<<psi_nb, HDG_PSI_BLOCK, 0, stream>>>(n, psi_sc + 8, cg_x, psi_part);
+    k_psi_minmax<<<1, HDG_PSI_BLOCK, 0, stream>>>(psi_nb, psi_part, psi_sc + 10);
+    const int ncb = (int)cell_grid().x;
+    for (int d = 0; d < 2; d++)  // curl psi as a broken velocity in the scratch vector of the test hooks
+      by_degree([&](auto k) { k_psi_curl<k()><<<cell_grid(), bs(), 0, stream>>>(g, cgt, psi_Dxy, cg_x, d, wQ2); });
+    auto defect = [&](const double* ub, double* res) {
+      by_degree([&](auto k) { k_psi_defect<k()><<<cell_grid(), bs(), 0, stream>>>(g, psi_Iphi, wQ2, vel_in, ub, psi_part); });
+      k_psi_finish<4><<<1, HDG_PSI_BLOCK, 0, stream>>>(ncb, psi_part, res);
+    };
+    defect(nullptr, psi_sc + 12);
+    if (periodic) {
+      k_psi_mean_flow<<<1, 64, 0, stream>>>(psi_sc + 12, (double)g.h * g.nx * (double)g.h * g.ny, psi_sc + 16);
+      defect(psi_sc + 16, psi_sc + 12);
+    }
+    double hs[24];
+    HIPCHECK(hipMemcpyAsync(hs, psi_sc, sizeof(hs), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    info[0] = its; info[1] = std::sqrt(rel2); info[2] = std::sqrt(std::max(hs[15], 0.0)); info[3] = std::sqrt(hs[14]);
+    info[4] = periodic ? hs[16] : 0.0; info[5] = periodic ? hs[17] : 0.0; info[6] = hs[10]; info[7] = hs[11];
+  }
   void cg_coordinates(double* xy) const {  // physical position of every continuous dof
     if (general) { std::memcpy(xy, gcg->xy.data(), sizeof(double) * gcg->xy.size()); return; }
     const int p = cgt.p;
@@ -5696,6 +5884,79 @@ int hdg_cg_to_broken(hdg_handle* h, const double* cg_values, double* broken) {
   else { E.by_degree([&](auto k) { hdg::k_cg_to_broken<k()><<<E.cell_grid(), E.bs(), 0, E.stream>>>(E.g, E.cgt, E.cg_b, E.hQ_dev); }); }
   if (hipMemcpyAsync(broken, E.hQ_dev, sizeof(double) * E.NQb / 2, hipMemcpyDeviceToHost, E.stream) != hipSuccess)
     throw hdg::HipError{"hipMemcpyAsync failed"};
+  HDG_API_END(h)
+}
+// ---- stream function (include/hdg_streamfunction.h)
+// structured meshes on one rank, between steps; 0: go on
+static int psi_refusal(hdg_handle* h, const char* call) {
+  if (!h || !h->eng) return HDG_ERR_ARG;
+  if (h->eng->general) { h->err = std::string(call) + ": general meshes are not supported (structured meshes only)"; return HDG_ERR_UNSUPPORTED; }
+  if (h->eng->comm->size > 1) { h->err = std::string(call) + ": strip partitions are not supported (one rank only)"; return HDG_ERR_UNSUPPORTED; }
+  if (h->eng->step_open) { h->err = std::string(call) + ": a step is open (between hdg_begin_step and the end of the step)"; return HDG_ERR_ARG; }
+  return 0;
+}
+static void psi_copy(hdg::Engine& E, void* dst, const void* src, long n, hipMemcpyKind kind) {
+  if (hipMemcpyAsync(dst, src, sizeof(double) * n, kind, E.stream) != hipSuccess) throw hdg::HipError{"hipMemcpyAsync failed"};
+}
+int hdg_streamfunction(hdg_handle* h, const double* Q, double rtol, double* psi, double info[8]) {
+  if (const int rc = psi_refusal(h, "hdg_streamfunction")) return rc;
+  HDG_API_BEGIN(h)
+  if (!psi || !info) throw std::string("null argument");
+  if (!(rtol > 0.0 && rtol < 1.0)) throw std::string("hdg_streamfunction: rtol must lie in (0, 1)");
+  hdg::Engine::TallyGuard keep(E);
+  const double* src = E.curQ;
+  if (Q) { E.put_Q(Q, E.wQ1); src = E.wQ1; }
+  E.streamfunction(src, rtol, info);
+  psi_copy(E, psi, E.cg_x, E.cgt.ncg, hipMemcpyDeviceToHost);
+  HDG_API_END(h)
+}
+int hdg_apply_cg_stiffness(hdg_handle* h, const double* x, double* y) {
+  if (const int rc = psi_refusal(h, "hdg_apply_cg_stiffness")) return rc;
+  HDG_API_BEGIN(h)
+  if (!x || !y) throw std::string("null argument");
+  hdg::Engine::TallyGuard keep(E);
+  E.psi_setup();
+  psi_copy(E, E.cg_b, x, E.cgt.ncg, hipMemcpyHostToDevice);
+  E.psi_stiff(E.cg_b, E.cg_x);
+  psi_copy(E, y, E.cg_x, E.cgt.ncg, hipMemcpyDeviceToHost);
+  HDG_API_END(h)
+}
+int hdg_psi_transfer(hdg_handle* h, int dir, const double* in, double* out) {
+  if (const int rc = psi_refusal(h, "hdg_psi_transfer")) return rc;
+  HDG_API_BEGIN(h)
+  if (!in || !out) throw std::string("null argument");
+  if (dir != 0 && dir != 1) throw std::string("hdg_psi_transfer: dir must be 0 (P) or 1 (P^T)");
+  hdg::Engine::TallyGuard keep(E);
+  E.psi_setup();
+  if (dir == 0) {
+    psi_copy(E, E.mg_b[0], in, E.psi_vertices(), hipMemcpyHostToDevice);
+    E.psi_prolong(E.mg_b[0], nullptr, E.cg_x);
+    psi_copy(E, out, E.cg_x, E.cgt.ncg, hipMemcpyDeviceToHost);
+  } else {
+    psi_copy(E, E.cg_b, in, E.cgt.ncg, hipMemcpyHostToDevice);
+    E.psi_restrict(E.cg_b, E.mg_b[0]);
+    psi_copy(E, out, E.mg_b[0], E.psi_vertices(), hipMemcpyDeviceToHost);
+  }
+  HDG_API_END(h)
+}
+int hdg_apply_psi_preconditioner(hdg_handle* h, int form, const double* r, double* z) {
+  if (const int rc = psi_refusal(h, "hdg_apply_psi_preconditioner")) return rc;
+  HDG_API_BEGIN(h)
+  if (!r || !z) throw std::string("null argument");
+  if (form != 0 && form != 1) throw std::string("hdg_apply_psi_preconditioner: form must be 0 (the solve's) or 1 (the diagonal alone)");
+  hdg::Engine::TallyGuard keep(E);
+  E.psi_setup();
+  psi_copy(E, E.cg_rr, r, E.cgt.ncg, hipMemcpyHostToDevice);
+  E.psi_precond(form == 1 || E.opt.psi_jacobi, E.cg_rr, E.cg_zz);
+  psi_copy(E, z, E.cg_zz, E.cgt.ncg, hipMemcpyDeviceToHost);
+  HDG_API_END(h)
+}
+int hdg_psi_vertex_count(hdg_handle* h, long* n_vertices) {
+  if (const int rc = psi_refusal(h, "hdg_psi_vertex_count")) return rc;
+  HDG_API_BEGIN(h)
+  if (!n_vertices) throw std::string("null argument");
+  E.psi_setup();
+  *n_vertices = E.psi_vertices();
   HDG_API_END(h)
 }
 int hdg_apply_tracer_advection(hdg_handle* h, const double* q, const double* u, int project, double* out) {

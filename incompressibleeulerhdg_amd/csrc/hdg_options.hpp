@@ -92,6 +92,7 @@ struct Options {
   double cg_floor_c = 32.0;        // rounding floor |M r| <= c eps |x|: sqrt(75) ~ 10 with a factor three
   int cg_force_replace = 0;        // test hook: force a residual replacement at this iteration
   bool cg_mass_one_by_one = false;  // continuous-space mass solves one right-hand side at a time
+  bool psi_jacobi = false;          // stream function: the diagonal alone as preconditioner, no vertex-grid cycle (the comparison test)
 
   // ---- stage bookkeeping of an IMEX step
   // the stage right-hand side formed inside the pressure-gradient kernel, pointer exchanges instead of copies (off: the
@@ -172,6 +173,7 @@ inline Options options_from_env() {
   real("HDG_CG_FLOOR_C", o.cg_floor_c);
   integer("HDG_CG_FORCE_REPLACE", o.cg_force_replace);
   flag("HDG_CG_MASS_ONE_BY_ONE", o.cg_mass_one_by_one);
+  flag("HDG_PSI_JACOBI", o.psi_jacobi);
 
   unless("HDG_NO_GLUE_FUSION", o.glue_fusion);
 

@@ -174,6 +174,9 @@ def build_parser():
                         help="with --cfl: the controller decides before the first step and after every M-th one (default 1)")
     parser.add_argument("--max_steps", metavar="N", type=int, default=None,
                         help="with --cfl: stop the run with an error after N steps (default 10 ceil(tfinal / dt)); sizes the row logs")
+    parser.add_argument("--streamfunction", action="store_true", default=False,
+                        help="after the run print the extrema of the stream function, their positions, the defect "
+                             "|u - ubar - curl psi| and the iteration count; with --animation psi is written next to the vorticity")
     parser.add_argument("--gpus", type=int, default=1,
                         help="number of ranks (strip partition of the square meshes, one process per rank)")
     return parser
@@ -196,6 +199,28 @@ def check_multi_gpu(args):
     for bad, what in refused:
         if bad:
             raise RuntimeError(f"--gpus {args.gpus} does not support {what}")
+
+
+def check_streamfunction(args):
+    """Refuse --streamfunction where the engine has no stream function, before any process is started or any engine is built."""
+    if not args.streamfunction:
+        return
+    if args.gpus > 1:
+        raise RuntimeError(f"--streamfunction does not support --gpus {args.gpus} (the continuous space is single-rank)")
+    if args.problem == "kelvinhelmholtz":
+        raise RuntimeError("--streamfunction does not support --problem kelvinhelmholtz (the stream function runs on the square meshes only)")
+
+
+def report_streamfunction(timestepper):
+    """One line: the extrema of psi of the current velocity and where they lie, the defect and the iteration count."""
+    eng = timestepper._engine
+    psi, info = eng.streamfunction()
+    xy = eng.cg_coordinates()
+    lo, hi = int(np.argmin(psi)), int(np.argmax(psi))
+    print(f"stream function: min = {float(psi[lo])!r} at ({float(xy[lo, 0])!r}, {float(xy[lo, 1])!r}), "
+          f"max = {float(psi[hi])!r} at ({float(xy[hi, 0])!r}, {float(xy[hi, 1])!r}), "
+          f"defect = {info['defect']!r}, iterations = {info['iterations']}")
+    print()
 
 
 def check_particles(args):
@@ -646,6 +671,7 @@ def main(argv=None):
     if args.discretisation == "conforming":
         raise RuntimeError(f"discretisation '{args.discretisation}' is out of scope of the MI355X hot path")
     check_multi_gpu(args)
+    check_streamfunction(args)
     check_particles(args)
     check_tracers(args)
     check_viscosity(args)
@@ -724,7 +750,9 @@ def start_from(args, ranks, timestepper):
 
 
 def _run(args, ranks):
-    callbacks = [AnimationCallback("evolution.pvd")] if args.animation else None  # driver.py:187
+    callbacks = None
+    if args.animation:  # driver.py:187
+        callbacks = [AnimationCallback("evolution.pvd", streamfunction=True) if args.streamfunction else AnimationCallback("evolution.pvd")]
     if args.problem in ("shear", "cylinder"):
         mesh = PeriodicSquareMesh(args.nx, args.nx, L=2 * np.pi, quadrilateral=False)  # driver.py:182-183
     elif args.problem == "kelvinhelmholtz":
@@ -902,6 +930,8 @@ def _run(args, ranks):
         cd, cl = wake.coefficients(force)
         print(f"disc: force on the body = {float(-force[0])!r} {float(-force[1])!r}, C_D = {float(cd)!r}, C_L = {float(cl)!r}")
         print()
+    if args.streamfunction:
+        report_streamfunction(timestepper)
     log_summary()
     print(f"state digest = {state_digest[0]:016x}{state_digest[1]:016x}")
     print()

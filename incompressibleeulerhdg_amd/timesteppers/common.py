@@ -318,6 +318,18 @@ class IncompressibleEuler(ABC):
         vals = self._engine.compute_diagnostics(self._as_nodal_velocity(Q), self._as_nodal_pressure(p), qn)
         return {name: float(v) for name, v in zip(DIAGNOSTICS, vals)}
 
+    # -- stream function (include/hdg_streamfunction.h) ------------------------------------------
+    def streamfunction(self, Q=None):
+        """The stream function psi in CG_{k+1} of the velocity Q (what _as_nodal_velocity accepts; None: the current state),
+        solved on the device and returned on the node set of the velocity space, like the vorticity of AnimationCallback.
+        Its attribute ``info`` holds the dict of Engine.streamfunction (iterations, defect, mean flow, extrema)."""
+        eng = self._engine
+        psi, info = eng.streamfunction(None if Q is None else self._as_nodal_velocity(Q))
+        V_psi = FunctionSpace(self._mesh, "CG", self._V_Q.degree, self._V_Q.coordinates)
+        out = Function(V_psi, eng.cg_to_broken(psi), "streamfunction")
+        out.info = info
+        return out
+
     # -- point values (include/hdg_mi355x.h: hdg_evaluate_points / hdg_set_probes; DESIGN.md section 13) ------------------
     def evaluate_points(self, xy, Q=None, p=None, q=None):
         """Values of the given fields (what _as_nodal_* accepts, None: NaN) at the points xy (n, 2), computed on the device:
