@@ -40,6 +40,7 @@
 #include "../../include/hdg_adaptive_dt.h"
 #include "../../include/hdg_streamfunction.h"
 #include "hdg_options.hpp"
+#include "hdg_cg_pending.hpp"
 #include "hdg_dispatch.hpp"
 #include "hdg_comm.hpp"
 #include "hdg_kernels.hpp"
@@ -139,6 +140,21 @@ struct Engine {
   double* h_res = nullptr;  // pinned host mirror of d_res
   double* cell_ss = nullptr;  // |z_K|^2 per cell (Chebyshev convergence checks)
   double* d_cgs = nullptr;  // device-resident CG scalars (k_cg_alpha / k_cg_beta)
+  // ring of the deferred p / x updates of trace_cg_sr (XpRide, hdg_cg_pending.hpp): the z of iteration j in cg_zring[j mod M]
+  // (slot 0 is cg_z; the others are allocated when a solve first asks for them), d_zring the same table on the device,
+  // d_cgh (alpha, beta, c) per slot
+  double* cg_zring[CG_XP_MAX_BATCH] = {nullptr};
+  const double** d_zring = nullptr;
+  double* d_cgh = nullptr;
+  void ensure_zring(int M) {
+    if (cg_zring[0] == cg_z && cg_zring[M - 1]) return;
+    if (!d_cgh) { d_cgh = dalloc(3 * CG_XP_MAX_BATCH); d_zring = (const double**)dalloc(CG_XP_MAX_BATCH); }
+    cg_zring[0] = cg_z;
+    for (int k = 1; k < M; k++)
+      if (!cg_zring[k]) cg_zring[k] = dalloc(NLv);
+    HIPCHECK(hipMemcpyAsync(d_zring, cg_zring, sizeof(double*) * CG_XP_MAX_BATCH, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
   double* h_cgs = nullptr;  // pinned snapshot of d_cgs for the lagged convergence check
   hipEvent_t cg_ev = nullptr;
   int dot_blocks = 0;
@@ -2165,17 +2181,24 @@ struct Engine {
   // leg launches of the V-cycle (k_p1_down / k_p1_up side jobs, hdg_vertex_mg.hpp: SideXP), a share of the pairs per leg by
   // weight (VertexPlan::side_weight_sum); what the legs did not take (no Legs level, rounding of the shares) is done by
   // finish() as a launch of its own.  (A second stream underneath the cycle was measured and removed: DESIGN.md section 9.)
-  // The CG sets pending and x, trace_precond brackets the cycle with begin / finish, the V-cycle takes its slices.
+  // The CG queues its updates and sets x, trace_precond brackets the cycle with begin / finish, the V-cycle takes its slices.
+  // Up to opt.cg_xp_batch consecutive updates are queued (hdg_cg_pending.hpp) and applied in ONE pass over p and x, entry by
+  // entry and in order -- the bits of one pass each, M + 5 vector passes instead of 6 M: the preconditioner writes the z of
+  // iteration j to slot j mod M of a ring of trace vectors (cg_zring), the kernel that forms the CG scalars leaves (alpha, beta, c)
+  // at the same slot of d_cgh, and the cycle that finds the ring full carries the batch.
   struct XpRide {
     Engine* e;
-    bool pending = false;  // the CG has queued the p / x half of its update
-    double* x = nullptr;   // the iterate it updates
-    long done = 0;         // pairs already handed to side jobs
-    double wsum = 0.0;     // sum of the leg weights of one cycle
+    CgPending q;          // the queued updates
+    double* x = nullptr;  // the iterate they update
+    bool due = false;     // the cycle between begin and finish has to apply the queue: its post kernel overwrites the oldest z
+    long done = 0;        // pairs already handed to side jobs
+    double wsum = 0.0;    // sum of the leg weights of one cycle
     bool riding = false;
+    XpBatch batch(const CgBatch& b) const { return XpBatch{e->d_zring, e->d_cgh, q.slot(b.first), q.M, b.count}; }
     void begin(const VertexPlan& pl) {
       done = 0; riding = false;
-      if (!pending) return;
+      due = q.count() > 0 && q.full();
+      if (!due) return;
       // strips: the finest level is distributed (vcycle_distributed_top launches its legs itself); the replicated levels carry the update
       wsum = pl.side_weight_sum(e->mg_distributed() ? 1 : 0, e->opt.cg_xp_w0);
       riding = wsum > 0.0;
@@ -2188,20 +2211,32 @@ struct Engine {
       long cnt = (long)std::ceil((double)total * VertexPlan::side_weight(lev, e->opt.cg_xp_w0) / wsum);
       cnt = std::min(cnt, total - done);
       if (cnt <= 0) return sj;
-      sj = SideXP{e->d_cgs, e->cg_z, e->tr_one, e->cg_p, x, done, done + cnt};
+      sj = SideXP{batch(q.all()), e->tr_one, e->cg_p, x, done, done + cnt};
       done += cnt;
       const long blocks = (cnt + HDG_P1_THREADS - 1) / HDG_P1_THREADS;
       extra_rows = (int)((blocks + nt - 1) / nt);
       return sj;
     }
-    void finish() {
-      if (!pending) return;
-      pending = false;
-      const long taken = riding ? done : 0;
-      riding = false; done = 0;
+    // the updates of b on the pairs from `taken` on, as a launch of its own; the census counts the passes of the whole batch here
+    void apply(const CgBatch& b, long taken) {
+      if (b.count <= 0) return;
       const long NLv = e->NLv;
+      e->lc_bytes[LC_VEC] += e->bL() * (b.count + 5);  // reads p, x, n and count z, writes p, x (the launch: counted with the r / s half)
       if (taken < (NLv >> 1) || (NLv & 1))
-        k_cg_sr_update_xp<<<e->vec_blocks(NLv - 2 * taken), 256, 0, e->stream>>>(NLv, e->d_cgs, e->cg_z, e->tr_one, e->cg_p, x, taken);
+        k_cg_sr_update_xp<<<e->vec_blocks(NLv - 2 * taken), 256, 0, e->stream>>>(NLv, batch(b), e->tr_one, e->cg_p, x, taken);
+    }
+    // everything queued, oldest first (what the legs of the cycle in flight did not take of it)
+    void finish() {
+      const long taken = riding ? done : 0;
+      riding = false; done = 0; due = false;
+      apply(q.all(), taken);
+      q.applied();
+    }
+    // normal exit of the solve: everything but the newest update, which is the step beyond the tested iterate
+    void finish_exit() {
+      riding = false; done = 0; due = false;
+      apply(q.all_but_newest(), 0);
+      q.drop();
     }
   };
   XpRide xp{this};
@@ -2447,10 +2482,10 @@ struct Engine {
         typedef TraceTile3<KK> T3;
         if (tile3()) k_trace_pre_tile3<KK><<<grid_pre, T3::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
         else k_trace_pre_tile<KK><<<grid_pre, TT::NTHREADS, 0, stream>>>(ntx, nty_pre, g, pre, pdt(), r, c0, c1, c2, ch_d, wL2);
-        xp.begin(vplan);  // the deferred half of the CG update: on the legs of the vertex-grid cycle ...
-        if (!xp.riding) xp.finish();  // ... or, where no leg can carry it, as a launch of its own
+        xp.begin(vplan);  // a full batch of deferred CG updates: on the legs of the vertex-grid cycle ...
+        if (xp.due && !xp.riding) xp.finish();  // ... or, where no leg can carry it, as a launch of its own
         coarse_correction(wL2);
-        xp.finish();  // what the legs did not take; the post kernel overwrites z
+        if (xp.due) xp.finish();  // what the legs did not take; the post kernel overwrites the oldest z of the batch
         tally(LC_TRACE_SMOOTH, (w_out ? 4 : 3) * bL() + nvtx);
         const long nblk = (long)ntx * nty;
         double* part = nullptr;
@@ -2664,13 +2699,14 @@ struct Engine {
   // already taken the step to x_{k+1}, which is harmless (a further CG step) and keeps the host off the critical path.
   // Returns the number of iterations the convergence test needed (the extra step is not counted).
   int trace_cg_sr(double* b, double* x, double rtol, int maxit, bool strict) {
-    auto leave = [&]() {  // a deferred p / x update left over at the exit is the step beyond the tested iterate: dropped
-      xp.pending = false;
+    auto leave = [&]() {  // whatever is still queued is given up (an exception; after finish_exit: the step beyond the tested iterate)
+      xp.q.drop(); xp.due = false; xp.riding = false;
       defer_tile_reduce = false; tile_nblk_deferred = 0;
     };
     try {
       defer_tile_reduce = comm->size == 1 && opt.cg_fused_scalars;
       const int its = trace_cg_sr_body(b, x, rtol, maxit, strict, opt.cg_split_update && use_trace_tile());
+      xp.finish_exit();  // the queued updates up to the tested iterate
       leave();
       return its;
     } catch (...) {
@@ -2688,6 +2724,12 @@ struct Engine {
     double *const r_cur = cg_r, *const s_cur = cg_s;
     const int nvb = vec_blocks(NLv);
     HIPCHECK(hipMemsetAsync(d_cgs, 0, sizeof(double) * 8, stream));
+    // the ring of the deferred p / x updates.  One rank only: on strips the whole-array update carries the stale ghost rows of z
+    // into those of x, and ring slots are work vectors a checkpoint does not hold
+    xp.q.reset(split && comm->size == 1 ? opt.cg_xp_batch : 1);
+    xp.x = x;
+    if (split) ensure_zring(xp.q.M);
+    double* zc = cg_z;  // z of the current iteration: its slot of the ring
     double norm0 = -1.0;
     int its = 0;
     // Residual replacement (round 4; replaces the "attainable accuracy" exit of round 3, which accepted a stalled
@@ -2726,39 +2768,44 @@ struct Engine {
     };
     while (true) {
       bool have_dots = false;
-      const bool have_w = trace_precond(r_cur, cg_z, cg_Ap, &have_dots);
-      if (!have_w) trace_apply(cg_z, nullptr, 0.0, 1.0, cg_Ap);  // w = T z
-      if (!have_dots) multidot(NLv, cg_z, {tr_one, r_cur, cg_z, cg_Ap}, nullptr, KL, true);  // (z,n), (z,r), (z,z), (z,w), (n,r) -> d_res
+      const int slot = xp.q.write_slot();
+      if (split) zc = cg_zring[slot];
+      double* const hist = split ? d_cgh + 3 * slot : nullptr;  // (alpha, beta, c) for the deferred update of this iteration
+      const bool have_w = trace_precond(r_cur, zc, cg_Ap, &have_dots);
+      if (!have_w) trace_apply(zc, nullptr, 0.0, 1.0, cg_Ap);  // w = T z
+      if (!have_dots) multidot(NLv, zc, {tr_one, r_cur, zc, cg_Ap}, nullptr, KL, true);  // (z,n), (z,r), (z,z), (z,w), (n,r) -> d_res
       tally(LC_OTHER, 0.0);
-      tally(LC_VEC, bL() * 11);  // k_cg_sr_update: reads z, n, w, p, s, x, r; writes p, s, x, r
+      // k_cg_sr_update: reads z, n, w, p, s, x, r; writes p, s, x, r.  Split: k_cg_sr_update_r reads w, s, r and writes s, r; the
+      // p / x half is counted where a batch is applied (XpRide::apply)
+      tally(LC_VEC, bL() * (split ? 5 : 11));
       if (have_dots && tile_nblk_deferred > 0) {
-        k_cg_sr_reduce_scalars<<<1, 1024, 0, stream>>>(tile_nblk_deferred, tile_part, d_res, d_cgs, tr_one_nn, restart ? 1 : 0, direct_host() ? h_cgs : nullptr);
+        k_cg_sr_reduce_scalars<<<1, 1024, 0, stream>>>(tile_nblk_deferred, tile_part, d_res, d_cgs, tr_one_nn, restart ? 1 : 0, direct_host() ? h_cgs : nullptr, hist);
         tile_nblk_deferred = 0;
         n_reduce++;
       } else
-        k_cg_sr_scalars<<<1, 1, 0, stream>>>(d_res, d_cgs, tr_one_nn, restart ? 1 : 0, direct_host() ? h_cgs : nullptr);  // + snapshot in pinned memory
+        k_cg_sr_scalars<<<1, 1, 0, stream>>>(d_res, d_cgs, tr_one_nn, restart ? 1 : 0, direct_host() ? h_cgs : nullptr, hist);  // + snapshot in pinned memory
       if (!direct_host()) HIPCHECK(hipMemcpyAsync(h_cgs, d_cgs, sizeof(double) * 8, hipMemcpyDeviceToHost, stream));
       HIPCHECK(hipEventRecord(cg_ev, stream));
       if (split) {
-        // r first (the next preconditioner application waits for it); p and x when that application reaches its V-cycle
+        // r first (the next preconditioner application waits for it); p and x with their batch, when the ring is full
         k_cg_sr_update_r<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_Ap, s_cur, r_cur);
-        xp.pending = true; xp.x = x;
+        xp.q.push();
       } else
-        k_cg_sr_update<<<nvb, 256, 0, stream>>>(NLv, d_cgs, cg_z, tr_one, cg_Ap, cg_p, s_cur, x, r_cur);
+        k_cg_sr_update<<<nvb, 256, 0, stream>>>(NLv, d_cgs, zc, tr_one, cg_Ap, cg_p, s_cur, x, r_cur);
       fl.set(s_cur, restart ? fl.get(cg_Ap) : std::min(fl.get(s_cur), fl.get(cg_Ap)));
       fl.set(r_cur, std::min(fl.get(r_cur), fl.get(s_cur)));
       fl.set(x, 0);
       const bool was_true = true_residual;
       restart = false; true_residual = false;
-      // snapshot of iteration `its` (cg_z is intact: the next preconditioner application has not been queued)
+      // snapshot of iteration `its` (zc is intact: the next preconditioner application has not been queued)
       HIPCHECK(hipEventSynchronize(cg_ev));
       const bool breakdown = h_cgs[6] == 1.0;  // alpha was set to 0: the update just queued leaves x alone
       double zz = h_cgs[4];
       if (h_cgs[6] == 2.0) {  // z almost parallel to the null vector: measure the projected norm explicitly
-        xp.finish();  // (the deferred update reads the unprojected z)
-        axpby(NLv, -h_cgs[3], tr_one, 1.0, cg_z);
-        fl.set(cg_z, 0);
-        zz = dot(NLv, cg_z, cg_z, KL);
+        xp.finish();  // (the deferred updates read the unprojected z)
+        axpby(NLv, -h_cgs[3], tr_one, 1.0, zc);
+        fl.set(zc, 0);
+        zz = dot(NLv, zc, zc, KL);
         HIPCHECK(hipMemsetAsync(d_cgs + 6, 0, sizeof(double), stream));
       }
       if (!(zz == zz)) throw NotConverged{"trace CG: NaN residual"};

@@ -2189,8 +2189,10 @@ __global__ void k_cg_p_dev(long N, const double* __restrict__ z, const double* _
 // recurrence s = w + beta s.  A n = 0 and A symmetric: (w, z') = (w, z) up to rounding.
 //   res = (z,n), (z,r), (z,z), (z,w), (n,r);  nn = (n,n);  sc[] as above
 // Zero residual (gamma = 0): alpha = beta = 0, the update is the identity and the host returns after the snapshot.
+// hist (may be null): (alpha, beta, c) of this iteration once more, at its slot of the history the deferred p / x updates read
+// (XpBatch below; hdg_cg_pending.hpp).
 __global__ void k_cg_sr_scalars(const double* __restrict__ res, double* __restrict__ sc, double nn, int first,
-                                double* __restrict__ hsc = nullptr) {
+                                double* __restrict__ hsc = nullptr, double* __restrict__ hist = nullptr) {
   const double c = res[0] / nn;
   const double rzn = res[1] - c * res[4];
   const double zz = res[2] - c * res[0];
@@ -2207,6 +2209,7 @@ __global__ void k_cg_sr_scalars(const double* __restrict__ res, double* __restri
   sc[2] = (rzn == 0.0) ? 0.0 : beta;
   sc[1] = alpha;
   sc[0] = rzn;
+  if (hist) { hist[0] = alpha; hist[1] = sc[2]; hist[2] = c; }
   if (hsc) {  // snapshot for the host's lagged convergence check (pinned memory; read after the event behind this kernel)
 #pragma unroll
     for (int q = 0; q < 8; q++) hsc[q] = sc[q];
@@ -2257,22 +2260,64 @@ __global__ void k_cg_sr_update_r(long N, const double* __restrict__ sc, const do
     r[it_] = fma(-alpha, sv, r[it_]);
   }
 }
-__global__ void k_cg_sr_update_xp(long N, const double* __restrict__ sc, const double* __restrict__ z, const double* __restrict__ nvec,
-                                  double* __restrict__ p, double* __restrict__ x, long ibeg = 0) {
-  const double alpha = sc[1], beta = sc[2], c = sc[3];
-  HDG_VEC_PROLOGUE
-  for (long i = ibeg + tid_; i < NP2_; i += stride_) {  // pairs before ibeg: done by the side jobs of the V-cycle legs
-    const hdg_d2 zp = fma2(-c, as2(nvec)[i], as2(z)[i]);
-    const hdg_d2 xv = as2(x)[i];
-    const hdg_d2 pv = (beta == 0.0) ? zp : fma2(beta, as2(p)[i], zp);
-    as2(p)[i] = pv;
-    as2(x)[i] = fma2(alpha, pv, xv);
+// A batch of queued p / x updates, oldest first (hdg_cg_pending.hpp): update j < n has its z in ring[(s0 + j) % M] and its
+// (alpha, beta, c) in hist[3 ((s0 + j) % M) ..].  ring is a device table of the M trace vectors, so that a kernel indexes
+// memory and not its own arguments.
+struct XpBatch {
+  const double* const* ring;
+  const double* hist;
+  int s0, M, n;
+};
+#define HDG_XP_GROUP 4  // z vectors whose loads are issued together (the leg kernels keep their registers: four pairs more)
+// the n updates of pair i, in order, p and x held in registers: per update the expressions of k_cg_sr_update, and p is not
+// loaded where the first beta is zero
+__device__ __forceinline__ void xp_batch_pair(const XpBatch& b, long i, const double* __restrict__ nvec, double* __restrict__ p,
+                                              double* __restrict__ x) {
+  const hdg_d2 nv = as2(nvec)[i];
+  hdg_d2 xv = as2(x)[i];
+  hdg_d2 pv = (b.hist[3 * b.s0 + 1] == 0.0) ? hdg_d2{0.0, 0.0} : as2(p)[i];
+  int slot = b.s0;
+  for (int j0 = 0; j0 < b.n; j0 += HDG_XP_GROUP) {
+    hdg_d2 zv[HDG_XP_GROUP];
+    int sl = slot;
+#pragma unroll
+    for (int q = 0; q < HDG_XP_GROUP; q++) {
+      if (j0 + q < b.n) {
+        zv[q] = as2(b.ring[sl])[i];
+        sl = sl + 1 == b.M ? 0 : sl + 1;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < HDG_XP_GROUP; q++) {
+      if (j0 + q < b.n) {
+        const double alpha = b.hist[3 * slot], beta = b.hist[3 * slot + 1], c = b.hist[3 * slot + 2];
+        const hdg_d2 zp = fma2(-c, nv, zv[q]);
+        pv = (beta == 0.0) ? zp : fma2(beta, pv, zp);
+        xv = fma2(alpha, pv, xv);
+        slot = slot + 1 == b.M ? 0 : slot + 1;
+      }
+    }
   }
+  as2(p)[i] = pv;
+  as2(x)[i] = xv;
+}
+__global__ void k_cg_sr_update_xp(long N, XpBatch b, const double* __restrict__ nvec, double* __restrict__ p, double* __restrict__ x,
+                                  long ibeg = 0) {
+  HDG_VEC_PROLOGUE
+  for (long i = ibeg + tid_; i < NP2_; i += stride_) xp_batch_pair(b, i, nvec, p, x);  // pairs before ibeg: done by the side jobs of the V-cycle legs
   if (tail_) {
-    const double zp = fma(-c, nvec[it_], z[it_]);
-    const double pv = (beta == 0.0) ? zp : fma(beta, p[it_], zp);
+    const double nv = nvec[it_];
+    double pv = p[it_], xv = x[it_];
+    int slot = b.s0;
+    for (int j = 0; j < b.n; j++) {
+      const double alpha = b.hist[3 * slot], beta = b.hist[3 * slot + 1], c = b.hist[3 * slot + 2];
+      const double zp = fma(-c, nv, b.ring[slot][it_]);
+      pv = (beta == 0.0) ? zp : fma(beta, pv, zp);
+      xv = fma(alpha, pv, xv);
+      slot = slot + 1 == b.M ? 0 : slot + 1;
+    }
     p[it_] = pv;
-    x[it_] = fma(alpha, pv, x[it_]);
+    x[it_] = xv;
   }
 }
 // y = a*x + b*y
@@ -2417,7 +2462,8 @@ __global__ void k_reduce_parts(int nblocks, int nv, const double* __restrict__ p
 // Second reduction stage of the tile preconditioner's five inner products AND the scalars of the single-reduction CG in
 // one launch (one rank: no all-reduce in between): one workgroup of 1024 threads, fixed summation order (deterministic).
 __global__ __launch_bounds__(1024) void k_cg_sr_reduce_scalars(int nblocks, const double* __restrict__ part, double* __restrict__ res,
-                                                               double* __restrict__ sc, double nn, int first, double* __restrict__ hsc) {
+                                                               double* __restrict__ sc, double nn, int first, double* __restrict__ hsc,
+                                                               double* __restrict__ hist = nullptr) {
   double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
   for (int b = threadIdx.x; b < nblocks; b += 1024) {  // part[q * nblocks + tile]: as the tile kernels leave it
@@ -2458,6 +2504,7 @@ __global__ __launch_bounds__(1024) void k_cg_sr_reduce_scalars(int nblocks, cons
   sc[2] = (rzn == 0.0) ? 0.0 : beta;
   sc[1] = alpha;
   sc[0] = rzn;
+  if (hist) { hist[0] = alpha; hist[1] = sc[2]; hist[2] = c; }
   if (hsc) {
 #pragma unroll
     for (int q = 0; q < 8; q++) hsc[q] = sc[q];

@@ -88,6 +88,9 @@ struct Options {
   bool cg_two_reductions = false;  // device scalars with two reductions per iteration (default: one)
   bool cg_split_update = true;     // r, s first, then p, x on the legs of the V-cycle (off: one update launch)
   bool cg_fused_scalars = true;    // one rank: the CG scalars formed by the kernel that sums the tile partials
+  // p / x updates applied in one pass, which is also the ring of z vectors and scalars they wait in (1: one per iteration; at
+  // most 16).  C3 step, ms: 1: 77.1, 2: 75.7, 3: 75.3, 4: 74.4-75.2, 6: 73.9-74.8, 8: 74.6
+  int cg_xp_batch = 6;
   double cg_xp_w0 = 1.6;           // share of the p / x update the finest level's legs carry (they run 18 us, the others 6-8)
   double cg_floor_c = 32.0;        // rounding floor |M r| <= c eps |x|: sqrt(75) ~ 10 with a factor three
   int cg_force_replace = 0;        // test hook: force a residual replacement at this iteration
@@ -169,6 +172,7 @@ inline Options options_from_env() {
   flag("HDG_CG_TWO_REDUCTIONS", o.cg_two_reductions);
   unless("HDG_CG_NO_SPLIT_UPDATE", o.cg_split_update);
   unless("HDG_CG_NO_FUSED_SCALARS", o.cg_fused_scalars);
+  integer("HDG_CG_XP_BATCH", o.cg_xp_batch);
   real("HDG_CG_XP_W0", o.cg_xp_w0);
   real("HDG_CG_FLOOR_C", o.cg_floor_c);
   integer("HDG_CG_FORCE_REPLACE", o.cg_force_replace);
@@ -181,6 +185,7 @@ inline Options options_from_env() {
   o.overlap = o.overlap && !no_overlap;
   o.mg_dense_tail = o.mg_dense_tail && o.mg_tail;
   o.mg_dense_tail_periodic = o.mg_dense_tail && o.mg_fuse;
+  o.cg_xp_batch = o.cg_xp_batch < 1 ? 1 : (o.cg_xp_batch > 16 ? 16 : o.cg_xp_batch);  // CG_XP_MAX_BATCH (hdg_cg_pending.hpp)
   return o;
 }
 

@@ -141,25 +141,18 @@ __global__ void k_p1_prolong_add(int nc, const double* __restrict__ xc, double* 
 // Side job of a leg launch (Engine::trace_cg_sr, one rank): the legs are latency-bound (8 barrier-separated LDS phases on a
 // grid of at most 33 x 33 tiles) and leave HBM idle, so the half of the CG update that nothing reads before the next
 // update -- p = (z - c n) + beta p ; x += alpha p (k_cg_sr_update_xp) -- rides along: the workgroups of the tile rows
-// >= nrows of a leg launch each take 1024 sixteen-byte pairs of the slice [i0, i1) instead of a tile.  (A second stream for
-// the same purpose gained 14 us per CG iteration of the 64 possible: two cross-stream dependencies cost 17 us.)
+// >= nrows of a leg launch each take 1024 sixteen-byte pairs of the slice [i0, i1) instead of a tile, and apply to them the whole
+// batch of queued updates in order (XpBatch, hdg_cg_pending.hpp: one pass over p and x for up to 16 iterations).  (A second stream
+// for the same purpose gained 14 us per CG iteration of the 64 possible: two cross-stream dependencies cost 17 us.)
 struct SideXP {
-  const double* sc;
-  const double* z;
+  XpBatch b;  // the queued updates the slice applies in one pass (hdg_kernels.hpp)
   const double* nvec;
   double* p;
   double* x;
   long i0, i1;
 };
 __device__ __forceinline__ void side_xp(const SideXP& sj, long blk, long nblk) {
-  const double alpha = sj.sc[1], beta = sj.sc[2], c = sj.sc[3];
-  for (long i = sj.i0 + blk * HDG_P1_THREADS + threadIdx.x; i < sj.i1; i += nblk * HDG_P1_THREADS) {
-    const hdg_d2 zp = fma2(-c, as2(sj.nvec)[i], as2(sj.z)[i]);
-    const hdg_d2 xv = as2(sj.x)[i];
-    const hdg_d2 pv = (beta == 0.0) ? zp : fma2(beta, as2(sj.p)[i], zp);
-    as2(sj.p)[i] = pv;
-    as2(sj.x)[i] = fma2(alpha, pv, xv);
-  }
+  for (long i = sj.i0 + blk * HDG_P1_THREADS + threadIdx.x; i < sj.i1; i += nblk * HDG_P1_THREADS) xp_batch_pair(sj.b, i, sj.nvec, sj.p, sj.x);
 }
 // by = the tile row of a workgroup that has one; side rows do their share of the side job and leave (hdg_side_rows.hpp)
 #define HDG_P1_SIDE_JOB                                                                                              \
