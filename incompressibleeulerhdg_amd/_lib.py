@@ -26,6 +26,7 @@ MOVING_WALL_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_
 ADAPTIVE_DT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_adaptive_dt.h"))
 DRAG_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_drag.h"))
 STREAMFUNCTION_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_streamfunction.h"))
+TRACER_IMPLICIT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "hdg_tracer_implicit.h"))
 
 HDG_MAX_STAGES = 5
 HDG_MAX_TRACERS = 16
@@ -98,7 +99,7 @@ class hdg_config(C.Structure):
 def build_library(force=False, verbose=False):
     """Compile the HIP engine for gfx950 into the package directory (in-tree, travels with gpurun)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER, DRAG_HEADER, STREAMFUNCTION_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    srcs = [HEADER, CHECKPOINT_HEADER, TRANSFER_HEADER, TRACER_DIFFUSION_HEADER, BUOYANCY_HEADER, VISCOSITY_HEADER, CORIOLIS_HEADER, TRACER_WALL_HEADER, MOVING_WALL_HEADER, ADAPTIVE_DT_HEADER, DRAG_HEADER, STREAMFUNCTION_HEADER, TRACER_IMPLICIT_HEADER] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -282,6 +283,13 @@ STREAMFUNCTION_SIGNATURES = {
     "hdg_apply_psi_preconditioner": [_h, C.c_int, _dp, _dp],
     "hdg_psi_vertex_count": [_h, _lp],
 }
+# implicit tracer diffusion: the symbols include/hdg_tracer_implicit.h declares, in a table of their own like the eleven above
+TRACER_IMPLICIT_SIGNATURES = {
+    "hdg_set_tracer_diffusion_mode": [_h, C.c_int, C.c_double, C.c_int],
+    "hdg_get_tracer_diffusion_solve": [_h, C.c_int, _ip, _dp],
+    "hdg_solve_tracer_diffusion": [_h, C.c_int, _dp, _dp, _dp, _ip],
+}
+TRACER_DIFFUSION_MODES = {"explicit": 0, "implicit": 1}
 STREAMFUNCTION_INFO = ("iterations", "residual", "defect", "u_l2", "mean_flow_x", "mean_flow_y", "psi_min", "psi_max")
 
 
@@ -345,7 +353,8 @@ def load_library():
     for name, args in list(SIGNATURES.items()) + list(CHECKPOINT_SIGNATURES.items()) + list(TRANSFER_SIGNATURES.items()) + \
             list(TRACER_DIFFUSION_SIGNATURES.items()) + list(BUOYANCY_SIGNATURES.items()) + list(VISCOSITY_SIGNATURES.items()) + \
             list(CORIOLIS_SIGNATURES.items()) + list(TRACER_WALL_SIGNATURES.items()) + list(MOVING_WALL_SIGNATURES.items()) + \
-            list(ADAPTIVE_DT_SIGNATURES.items()) + list(DRAG_SIGNATURES.items()) + list(STREAMFUNCTION_SIGNATURES.items()):
+            list(ADAPTIVE_DT_SIGNATURES.items()) + list(DRAG_SIGNATURES.items()) + list(STREAMFUNCTION_SIGNATURES.items()) + \
+            list(TRACER_IMPLICIT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -700,6 +709,38 @@ class Engine:
         out = np.empty(self.shape_p)
         self._ck(self.lib.hdg_apply_tracer_wall_diffusion(self.h, kind.ctypes.data_as(_ip), _ptr(value), _ptr(q), _ptr(out)))
         return out
+
+    # --- implicit tracer diffusion (include/hdg_tracer_implicit.h)
+    def set_tracer_diffusion_mode(self, mode, rtol=1e-10, max_iterations=2000):
+        """mode: 'explicit' (the default of an engine) or 'implicit' (or the integers 0 / 1 of the C-ABI).  Implicit: a step
+        transports the tracers without their diffusion and ends with one backward-Euler solve per tracer with kappa_t != 0,
+        conjugate gradients on the device to |r| <= rtol |b| (a Lie splitting, first order in dt)."""
+        code = TRACER_DIFFUSION_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(code, str):
+            raise ValueError(f"tracer_diffusion must be one of {sorted(TRACER_DIFFUSION_MODES)} (got {mode!r})")
+        self._ck(self.lib.hdg_set_tracer_diffusion_mode(self.h, int(code), float(rtol), int(max_iterations)))
+        self._tracer_diffusion_mode = int(code)
+
+    def tracer_diffusion_mode(self):
+        """'explicit' or 'implicit', as it is set"""
+        return "implicit" if getattr(self, "_tracer_diffusion_mode", 0) == 1 else "explicit"
+
+    def tracer_diffusion_solve(self):
+        """(iterations (n_tracers,) int, relative residuals (n_tracers,)) of the last implicit solve; zeros for a tracer with
+        kappa_t = 0 and before any solve."""
+        its, res = np.zeros(self.n_tracers, dtype=np.int32), np.zeros(self.n_tracers)
+        self._ck(self.lib.hdg_get_tracer_diffusion_solve(self.h, self.n_tracers, its.ctypes.data_as(_ip), _ptr(res)))
+        return its, res
+
+    def solve_tracer_diffusion(self, tau, q):
+        """(x, iterations): x[t] solves (I - tau[t] M^-1 D_w) x = q[t] + tau[t] M^-1 l_w for n <= n_tracers nodal DG_k fields
+        q (n, *shape_p), field t with the walls set for tracer t, to the rtol that is set (test hook; it sets nothing)."""
+        tau = np.ascontiguousarray(np.asarray(tau, dtype=np.float64).reshape(-1))
+        q = _arr(q, (len(tau),) + tuple(self.shape_p))
+        out = np.empty_like(q)
+        its = np.zeros(len(tau), dtype=np.int32)
+        self._ck(self.lib.hdg_solve_tracer_diffusion(self.h, len(tau), _ptr(tau), _ptr(q), _ptr(out), its.ctypes.data_as(_ip)))
+        return out, its
 
     # --- Boussinesq buoyancy (include/hdg_buoyancy.h; DESIGN.md section 20)
     def set_buoyancy(self, beta, gravity=(0.0, -1.0)):

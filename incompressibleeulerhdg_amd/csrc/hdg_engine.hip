@@ -39,6 +39,7 @@
 #include "../../include/hdg_moving_walls.h"
 #include "../../include/hdg_adaptive_dt.h"
 #include "../../include/hdg_streamfunction.h"
+#include "../../include/hdg_tracer_implicit.h"
 #include "hdg_options.hpp"
 #include "hdg_cg_pending.hpp"
 #include "hdg_dispatch.hpp"
@@ -67,6 +68,7 @@
 #include "hdg_drag_host.hpp"
 #include "hdg_drag.hpp"
 #include "hdg_tracer_walls.hpp"
+#include "hdg_tracer_implicit.hpp"
 #include "hdg_amg.hpp"
 #include "hdg_diagnostics.hpp"
 #include "hdg_probes.hpp"
@@ -604,6 +606,8 @@ struct Engine {
     for (int q = 0; q < 2; q++) if (cgm_ev[q]) { (void)hipEventDestroy(cgm_ev[q]); cgm_ev[q] = nullptr; }
     if (psi_h) { (void)hipHostFree(psi_h); psi_h = nullptr; }
     for (int q = 0; q < 2; q++) if (psi_ev[q]) { (void)hipEventDestroy(psi_ev[q]); psi_ev[q] = nullptr; }
+    if (tdi_h) { (void)hipHostFree(tdi_h); tdi_h = nullptr; }
+    for (int q = 0; q < 2; q++) if (tdi_ev[q]) { (void)hipEventDestroy(tdi_ev[q]); tdi_ev[q] = nullptr; }
     if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
     delete tab;
     tab = nullptr;
@@ -3156,7 +3160,7 @@ struct Engine {
     }
     // hdg_implicit.py:192-193: the tracer is advanced only after a SUCCESSFUL step (a failed Krylov solve must leave it
     // where Q and p stay), so the update sits before each of the two normal returns, not in a scope guard
-    auto tracer_end = [&]() { if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur); };
+    auto tracer_end = [&]() { if (tracer_on) { axpby(NTv(), dtt, q_t, 1.0, q_cur); tracer_implicit_diffusion(); } };
     if (vel_linear_on()) vel_linear_apply(curQ, visc[0]);  // slot 0: Q_n, forward Euler, beside f(t_k)
     ensure_dinv(0, dtt);
     { Timed tb_(*this, T_BDM); bdm(curQ, Qstar[0]); }             // hdg_implicit.py:98
@@ -3302,7 +3306,7 @@ struct Engine {
     shift(curP, nullptr);
     it_sum[0] += it; it_cnt[0]++;
     if (its) *its = it;
-    if (tracer_on) axpby(NTv(), dtt, q_t, 1.0, q_cur);  // dg_implicit.py:131-132, after a successful solve only
+    if (tracer_on) { axpby(NTv(), dtt, q_t, 1.0, q_cur); tracer_implicit_diffusion(); }  // dg_implicit.py:131-132, after a successful solve only
   }
   // operator-level access (hdg_apply_dg_operator): out = K x of dg_implicit.py:48-71 (unscaled rows, phi not y)
   void dg_operator(const double* qstar, const double* u, const double* p, double dtt, double* out_u, double* out_p) {
@@ -3899,7 +3903,7 @@ struct Engine {
   // the tendency of every tracer: transport, plus diffusion when some kappa_t != 0 (with the wall terms when some side is fixed)
   void tracer_tendency(const double* q, const double* u, double* out) {
     tracer_adv(q, u, out, n_tr);
-    if (!tr_kappa.empty()) tracer_diff(q, d_kappa, tr_kappa.data(), out, n_tr, tw_kind.empty() ? -1 : 0);
+    if (!tr_kappa.empty() && !tdi_mode) tracer_diff(q, d_kappa, tr_kappa.data(), out, n_tr, tw_kind.empty() ? -1 : 0);
   }
   // ---- fixed-value walls and the wall flux (include/hdg_tracer_walls.h).  Per tracer and side (structured:
   // bottom, right, top, left; general: the whole boundary at index 0) a kind (0 no flux, 1 fixed value) and a value; a fixed side
@@ -4041,6 +4045,155 @@ struct Engine {
     }
     out2[0] = lam;
     out2[1] = kmax * cfg.dt * lam;
+  }
+  // ---- implicit tracer diffusion (include/hdg_tracer_implicit.h, hdg_tracer_implicit.hpp).  In implicit
+  // mode the tendencies carry transport alone (tracer_tendency), and where a step forms its new tracers every tracer with
+  // kappa_t != 0 becomes the solution of (I - dt kappa_t M^-1 D_w) q = q~ + dt kappa_t l_w: a Lie splitting, first order in dt.
+  // Structured meshes on one rank.  The five work vectors are scratch, written from their start in every solve: no state.
+  int tdi_mode = 0;  // 0 explicit, 1 implicit
+  double tdi_rtol = 1e-10;
+  int tdi_maxit = 2000;
+  double *tdi_x = nullptr, *tdi_r = nullptr, *tdi_p = nullptr, *tdi_y = nullptr, *tdi_w = nullptr, *tdi_part = nullptr, *tdi_sc = nullptr,
+         *tdi_tau = nullptr, *tdi_h = nullptr;
+  hipEvent_t tdi_ev[2] = {nullptr, nullptr};
+  std::vector<int> tdi_its = std::vector<int>(HDG_MAX_TRACERS, 0);        // the last solve, per tracer
+  std::vector<double> tdi_res = std::vector<double>(HDG_MAX_TRACERS, 0.0);
+  std::string tdi_failure;                                                 // the last solve's, until tdi_raise reports it
+  long tdi_solves = 0, tdi_iterations = 0;                                 // solves and operator passes since the engine exists
+  void tdi_alloc() {
+    if (tdi_x) return;
+    tracer_alloc();
+    for (double** v : {&tdi_x, &tdi_r, &tdi_p, &tdi_y, &tdi_w}) *v = dalloc(NTv());
+    tdi_part = dalloc(3L * HDG_MAX_TRACERS * cell_grid().x);
+    tdi_sc = dalloc((long)HDG_MAX_TRACERS * TDI_NSC);
+    tdi_tau = dalloc(HDG_MAX_TRACERS);
+    HIPCHECK(hipHostMalloc((void**)&tdi_h, sizeof(double) * 2));
+    for (int q = 0; q < 2; q++) HIPCHECK(hipEventCreateWithFlags(&tdi_ev[q], hipEventDisableTiming));
+  }
+  void set_tracer_diffusion_mode(int mode, double rtol, int max_iterations) {
+    if (step_open) throw std::string("hdg_set_tracer_diffusion_mode: a step is open (between hdg_begin_step and the end of the step)");
+    if (mode != 0 && mode != 1) throw std::string("hdg_set_tracer_diffusion_mode: mode " + std::to_string(mode) + " is neither 0 (explicit) nor 1 (implicit)");
+    if (!(rtol > 0.0) || !std::isfinite(rtol)) throw std::string("hdg_set_tracer_diffusion_mode: rtol = " + std::to_string(rtol) + " is not a finite value > 0");
+    if (max_iterations < 1) throw std::string("hdg_set_tracer_diffusion_mode: max_iterations = " + std::to_string(max_iterations) + " is not positive");
+    tdi_mode = mode; tdi_rtol = rtol; tdi_maxit = max_iterations;
+  }
+  // the ghost rows of the tracers still in the solve (the periodic square reads them): one call per run of neighbours in t
+  void tdi_halo(double* v, const std::vector<char>& on) {
+    if (!periodic) return;
+    const int n = (int)on.size();
+    for (int t = 0; t < n;) {
+      if (!on[(size_t)t]) { t++; continue; }
+      int e = t;
+      while (e < n && on[(size_t)e]) e++;
+      halo_rows(v + t * NPv, (long)g.R * g.nx, g.nx, NP * 2 * (e - t), 1);
+      t = e;
+    }
+  }
+  // q_t <- the solution of (I - tau_t M^-1 D_w) x = q_t + tau_t l_w for the n tracer-major fields at q; tau[n]: host values, copied
+  // to the small device array tdi_tau the kernels read, and the choice of the tracers that take part.  slot: the wall rows, as in
+  // tracer_diff.  A tracer that does not converge keeps its values, and tdi_failure says so.
+  void tdi_solve(double* q, int n, const double* tau_host, int slot) {
+    tdi_alloc();
+    diff_setup();
+    std::vector<char> on((size_t)n);
+    std::vector<double> sc0((size_t)n * TDI_NSC, 0.0);
+    int nact = 0;
+    for (int t = 0; t < n; t++) {
+      on[(size_t)t] = tau_host[t] != 0.0;
+      nact += on[(size_t)t];
+      sc0[(size_t)t * TDI_NSC + TDI_STATE] = on[(size_t)t] ? (double)TDI_ITERATING : (double)TDI_IDLE;
+    }
+    std::fill(tdi_its.begin(), tdi_its.end(), 0);
+    std::fill(tdi_res.begin(), tdi_res.end(), 0.0);
+    tdi_failure.clear();
+    if (nact == 0) return;
+    tdi_solves++;
+    HIPCHECK(hipMemcpyAsync(tdi_sc, sc0.data(), sizeof(double) * sc0.size(), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipMemcpyAsync(tdi_tau, tau_host, sizeof(double) * n, hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));  // sc0 and tau_host leave scope
+    const int nblk = (int)cell_grid().x;
+    double *part_rr = tdi_part, *part_rw = tdi_part + (long)HDG_MAX_TRACERS * nblk, *part_bb = tdi_part + 2L * HDG_MAX_TRACERS * nblk;
+    const double rtol2 = tdi_rtol * tdi_rtol;
+    auto helm = [&](auto init, const double* in, double* out, double* p0, double* p1) {
+      tally(LC_OTHER, 3.0 * nact * bP());
+      by_degree([&](auto k) {
+        constexpr int KK = decltype(k)::value;
+        by_tracer_block<TracerBlock<KK>::TB>(n, [&](auto tb) {
+          constexpr int TB = decltype(tb)::value;
+          constexpr bool INIT = decltype(init)::value;
+          dim3 grid = cell_grid();
+          grid.y = (unsigned)((n + TB - 1) / TB);
+          if (slot >= 0)
+            k_tracer_helm<KK, TB, true, INIT><<<grid, bs(), 0, stream>>>(g, d_difftab, tdi_tau, tdi_sc, n, NPv, in, out, tdi_x, p0, p1, d_walltab,
+                                                                         d_wkind + 4 * slot, d_wval + 4 * slot);
+          else
+            k_tracer_helm<KK, TB, false, INIT><<<grid, bs(), 0, stream>>>(g, d_difftab, tdi_tau, tdi_sc, n, NPv, in, out, tdi_x, p0, p1, nullptr,
+                                                                          nullptr, nullptr);
+        });
+      });
+    };
+    auto scalars = [&](int first, int last, double* hflag) {
+      tally(LC_OTHER, 0.0);
+      k_tdi_scalars<<<1, HDG_TDI_SC_BLOCK, 0, stream>>>(n, nblk, first, last, rtol2, part_rr, part_rw, part_bb, tdi_sc, hflag);
+    };
+    tdi_halo(q, on);
+    helm(std::true_type{}, q, tdi_r, part_rr, part_bb);  // x_0 = q~, r_0, (r_0, r_0), (b, b)
+    bool seen_done = false;
+    for (int it = 0; it < tdi_maxit; it++) {
+      tdi_halo(tdi_r, on);
+      helm(std::false_type{}, tdi_r, tdi_w, part_rw, nullptr);
+      scalars(it == 0, 0, tdi_h + (it & 1));
+      HIPCHECK(hipEventRecord(tdi_ev[it & 1], stream));
+      tally(LC_OTHER, 9.0 * nact * bP());
+      dim3 grid = cell_grid();
+      grid.y = (unsigned)n;
+      by_degree([&](auto k) { k_tdi_update<k()><<<grid, bs(), 0, stream>>>(g, tdi_sc, NPv, tdi_w, tdi_p, tdi_y, tdi_x, tdi_r, part_rr); });
+      tdi_iterations++;
+      if (it >= 1) {  // the flag word of the previous iteration: every tracer frozen means the launches since did nothing
+        HIPCHECK(hipEventSynchronize(tdi_ev[(it - 1) & 1]));
+        if (tdi_h[(it - 1) & 1] == 0.0) { seen_done = true; break; }
+      }
+    }
+    if (!seen_done) scalars(0, 1, tdi_h);  // the residual of the last update is still unjudged
+    {
+      tally(LC_OTHER, 2.0 * nact * bP());
+      dim3 grid = cell_grid();
+      grid.y = (unsigned)n;
+      by_degree([&](auto k) { k_tdi_accept<k()><<<grid, bs(), 0, stream>>>(g, tdi_sc, NPv, tdi_x, q); });
+    }
+    std::vector<double> sc1((size_t)n * TDI_NSC);
+    HIPCHECK(hipMemcpyAsync(sc1.data(), tdi_sc, sizeof(double) * sc1.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    for (int t = 0; t < n; t++) {
+      const double* st = sc1.data() + (size_t)t * TDI_NSC;
+      if (!on[(size_t)t]) continue;
+      tdi_its[(size_t)t] = (int)st[TDI_ITS];
+      tdi_res[(size_t)t] = st[TDI_RES];
+      if (st[TDI_STATE] == (double)TDI_CONVERGED || !tdi_failure.empty()) continue;
+      char buf[200];
+      snprintf(buf, sizeof(buf), "implicit tracer diffusion: tracer %d %s after %d iteration(s), relative residual %.3e (rtol %.3e)", t,
+               st[TDI_STATE] == (double)TDI_BROKE_DOWN ? "broke down" : "did not converge", (int)st[TDI_ITS], st[TDI_RES], tdi_rtol);
+      tdi_failure = buf;
+    }
+  }
+  // the split step: called where a step has formed its transported tracers q_cur
+  void tracer_implicit_diffusion() {
+    if (!tdi_mode || tr_kappa.empty()) return;
+    std::vector<double> tau((size_t)n_tr);
+    for (int t = 0; t < n_tr; t++) tau[(size_t)t] = cfg.dt * tr_kappa[(size_t)t];
+    tdi_solve(q_cur, n_tr, tau.data(), tw_kind.empty() ? -1 : 0);
+  }
+  // a solve that failed inside a step is reported once the step is complete: the flow has advanced, the tracer is the transported one
+  void tdi_raise() {
+    if (tdi_failure.empty()) return;
+    const std::string m = tdi_failure;
+    tdi_failure.clear();
+    throw NotConverged{m};
+  }
+  // test hook: n fields (device layout, tracer-major at q_t), tau[n] on the host; the walls that are set (row t for field t)
+  void solve_tracer_diffusion(int n, const double* tau) {
+    if (!tw_kind.empty()) walls_setup();
+    tdi_solve(q_t, n, tau, tw_kind.empty() ? -1 : 0);
   }
   // ---- Boussinesq buoyancy: the forcing slot j of a step becomes b_rhs[j] + B(q^(j)),
   // B(q) = sum_t beta_t q_t g embedded in the velocity space (hdg_buoyancy.hpp).  The s + 1 vectors buoy[j] stand beside brhs and
@@ -4443,7 +4596,7 @@ struct Engine {
     buoyancy_slot(i);
   }
   void tracer_finish_step() {  // hdg_imex.py:638-639
-    if (tracer_on) copy(q_cur, q_fin, NTv());
+    if (tracer_on) { copy(q_cur, q_fin, NTv()); tracer_implicit_diffusion(); }
   }
 
   // ------------------------------------------------------------------ per-step outputs (hdg_row_log.hpp)
@@ -4862,7 +5015,7 @@ struct Engine {
     double kmax = 0.0;
     for (double x : tr_kappa) kmax = std::max(kmax, x);
     double out2[2];
-    if (kmax > 0.0) { tracer_diffusion_number(out2); rates[1] = kmax * out2[0]; }
+    if (kmax > 0.0 && !tdi_mode) { tracer_diffusion_number(out2); rates[1] = kmax * out2[0]; }  // implicit: no limit (section 28)
     if (visc_nu > 0.0) { viscosity_number(visc_nu, visc_wall, out2); rates[2] = visc_nu * out2[0]; }
     if (drag_on()) rates[2] += drag_S;  // both spectra are real and non-positive: the rates add (section 26)
     if (cor_f0 != 0.0 || cor_beta != 0.0) rates[3] = coriolis_bound(cor_f0, cor_beta);
@@ -5064,6 +5217,7 @@ struct Engine {
     for (size_t t = 0; t < tr_kappa.size(); t++) f.add("tracer_kappa[" + std::to_string(t) + "]", tr_kappa[t]);  // only with some kappa != 0
     for (size_t m = 0; m < tw_kind.size(); m++)  // one line per (tracer, side) with a fixed value, and only then
       if (tw_kind[m]) f.add("tracer_wall[" + std::to_string(m / 4) + "][" + std::to_string(m % 4) + "]", tw_val[m]);
+    if (tdi_mode) f.add("tracer_diffusion_mode", (long)tdi_mode);  // only in implicit mode (section 28)
     for (size_t t = 0; t < by_beta.size(); t++) f.add("buoyancy_beta[" + std::to_string(t) + "]", by_beta[t]);  // only with some beta != 0
     if (!by_beta.empty()) { f.add("gravity[0]", by_g[0]); f.add("gravity[1]", by_g[1]); }
     if (viscosity_on()) { f.add("viscosity", visc_nu); f.add("viscosity_wall", (long)visc_wall); }  // only with nu != 0
@@ -5732,6 +5886,7 @@ int hdg_step(hdg_handle* h) {
   E.step();
   E.end_of_step();
   E.step_open = false;  // a whole step: complete
+  E.tdi_raise();
   HDG_API_END(h)
 }
 int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
@@ -5742,6 +5897,7 @@ int hdg_run_separable(hdg_handle* h, int nsteps, const double* scales) {
     E.step();
     E.end_of_step();
     E.step_open = false;
+    E.tdi_raise();
     E.harvest_completed();  // keeps the number of live timer events bounded over a long run
   }
   HDG_API_END(h)
@@ -5751,6 +5907,7 @@ int hdg_implicit_step(hdg_handle* h, int* its_tentative, int* its_pressure) {
   E.implicit_step(its_tentative, its_pressure);
   E.end_of_step();
   E.step_open = false;  // a whole step: complete
+  E.tdi_raise();
   HDG_API_END(h)
 }
 // ---- implicit DG discretisation (dg_implicit.py:10-136), single rank
@@ -5767,6 +5924,7 @@ int hdg_dg_implicit_step(hdg_handle* h, int* its) {
   E.dg_implicit_step(its);
   E.end_of_step();
   E.step_open = false;  // a whole step: complete
+  E.tdi_raise();
   HDG_API_END(h)
 }
 int hdg_apply_dg_operator(hdg_handle* h, const double* Qstar, const double* u, const double* p, double dt, double* out_u,
@@ -5886,6 +6044,7 @@ int hdg_tracer_finish_step(hdg_handle* h) {
   HDG_API_BEGIN(h)
   E.tracer_finish_step();
   if (E.tracer_on) { E.end_of_step(); E.step_open = false; }
+  E.tdi_raise();
   HDG_API_END(h)
 }
 int hdg_cg_size(hdg_handle* h, long* n_cg) {
@@ -6233,6 +6392,46 @@ int hdg_apply_tracer_wall_diffusion(hdg_handle* h, const int kind[4], const doub
   E.put_P(q, E.wP1);
   E.apply_tracer_wall_diffusion(kind, value, E.wP1, E.q_t);
   E.get_P(E.q_t, out);
+  HDG_API_END(h)
+}
+
+
+// ---- implicit tracer diffusion (include/hdg_tracer_implicit.h)
+// structured meshes on one rank; 0: go on
+static int tdi_refusal(hdg_handle* h, const char* call) {
+  if (!h || !h->eng) return HDG_ERR_ARG;
+  if (h->eng->general) { h->err = std::string(call) + ": general meshes are not supported (structured meshes only)"; return HDG_ERR_UNSUPPORTED; }
+  if (h->eng->comm->size > 1) { h->err = std::string(call) + ": strip partitions are not supported (one rank only)"; return HDG_ERR_UNSUPPORTED; }
+  return 0;
+}
+int hdg_set_tracer_diffusion_mode(hdg_handle* h, int mode, double rtol, int max_iterations) {
+  if (const int rc = tdi_refusal(h, "hdg_set_tracer_diffusion_mode")) return rc;
+  HDG_API_BEGIN(h)
+  E.set_tracer_diffusion_mode(mode, rtol, max_iterations);
+  HDG_API_END(h)
+}
+int hdg_get_tracer_diffusion_solve(hdg_handle* h, int n, int* its, double* res) {
+  HDG_API_BEGIN(h)
+  if (!its || !res) throw std::string("null argument");
+  if (n < 1 || n > HDG_MAX_TRACERS) throw std::string("hdg_get_tracer_diffusion_solve: n = " + std::to_string(n) + " is out of range");
+  for (int t = 0; t < n; t++) { its[t] = E.tdi_its[(size_t)t]; res[t] = E.tdi_res[(size_t)t]; }
+  HDG_API_END(h)
+}
+int hdg_solve_tracer_diffusion(hdg_handle* h, int n, const double* tau, const double* q_in, double* q_out, int* its) {
+  if (const int rc = tdi_refusal(h, "hdg_solve_tracer_diffusion")) return rc;
+  HDG_API_BEGIN(h)
+  if (!tau || !q_in || !q_out) throw std::string("null argument");
+  if (E.step_open) throw std::string("hdg_solve_tracer_diffusion: a step is open (between hdg_begin_step and the end of the step)");
+  if (n < 1 || n > E.n_tr) throw std::string("hdg_solve_tracer_diffusion: " + std::to_string(n) + " field(s) on an engine of " + std::to_string(E.n_tr) + " tracer(s)");
+  for (int t = 0; t < n; t++)
+    if (!(tau[t] >= 0.0) || !std::isfinite(tau[t])) throw std::string("hdg_solve_tracer_diffusion: tau[" + std::to_string(t) + "] is not a finite value >= 0");
+  hdg::Engine::TallyGuard keep(E);
+  E.tracer_alloc();
+  for (int t = 0; t < n; t++) E.put_P(q_in + t * E.NPb, E.q_t + t * E.NPv);
+  E.solve_tracer_diffusion(n, tau);
+  for (int t = 0; t < n; t++) { E.get_P(E.q_t + t * E.NPv, q_out + t * E.NPb); if (its) its[t] = E.tdi_its[(size_t)t]; }
+  if (hipStreamSynchronize(E.stream) != hipSuccess) throw hdg::HipError{"hipStreamSynchronize failed"};
+  E.tdi_raise();
   HDG_API_END(h)
 }
 

@@ -99,6 +99,10 @@ def build_parser():
     parser.add_argument("--tracer_diffusivity", metavar="K", type=float, nargs="+", default=None,
                         help="molecular diffusivity of the tracers (with --tracer_advection): one value for all of them or "
                              "exactly --tracers values; explicit in time, see the printed diffusion number")
+    parser.add_argument("--tracer_diffusion", choices=["explicit", "implicit"], default=None,
+                        help="how the tracers diffuse (with --tracer_diffusivity): explicit in the stages (the default), or "
+                             "implicit, one backward-Euler solve per step on the device: no limit on the diffusion number, first "
+                             "order in dt; single GPU, structured meshes")
     parser.add_argument("--tracer_wall", metavar=("SIDE", "VALUE"), nargs="+", action="append", default=None,
                         help="SIDE VALUE [T]: hold tracer T (without T: every tracer) at VALUE on the wall SIDE (bottom, right, top, "
                              "left on the unit square; boundary with --problem kelvinhelmholtz); repeatable; acts through "
@@ -248,6 +252,14 @@ def check_tracers(args):
         for m, x in enumerate(kappa):
             if not (np.isfinite(x) and x >= 0):
                 raise RuntimeError(f"--tracer_diffusivity: value {m} ({x}) is not a finite number >= 0")
+    if args.tracer_diffusion is not None:
+        if kappa is None:
+            raise RuntimeError("--tracer_diffusion needs --tracer_diffusivity")
+        if args.tracer_diffusion == "implicit" and args.gpus > 1:
+            raise RuntimeError(f"--tracer_diffusion implicit does not support --gpus {args.gpus} (the solve is single-rank)")
+        if args.tracer_diffusion == "implicit" and args.problem == "kelvinhelmholtz":
+            raise RuntimeError("--tracer_diffusion implicit: the disk of --problem kelvinhelmholtz is a general mesh "
+                               "(structured meshes only)")
     tracer_walls(args)
     beta = args.buoyancy
     if args.gravity is not None and beta is None:
@@ -698,6 +710,8 @@ def make_timestepper(args, ranks, mesh, degree, dt, callbacks):
     if args.tracer_diffusivity is not None:
         kappa = args.tracer_diffusivity
         several["tracer_diffusivity"] = kappa[0] if len(kappa) == 1 else kappa
+        if args.tracer_diffusion == "implicit":
+            several["tracer_diffusion"] = "implicit"
     if args.tracer_wall:
         several["tracer_walls"] = tracer_walls(args)
     if args.buoyancy is not None:
@@ -789,7 +803,11 @@ def _run(args, ranks):
         print(f"number of tracers = {args.tracers}")
     if args.tracer_diffusivity is not None:
         print(f"tracer diffusivity = {' '.join(repr(x) for x in args.tracer_diffusivity)}")
-        print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g} (limit {timestepper.diffusion_limit:.6g})")
+        if args.tracer_diffusion == "implicit":
+            print("tracer diffusion = implicit")
+            print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g}")
+        else:
+            print(f"tracer diffusion number = {timestepper._engine.tracer_diffusion_number()[1]:.6g} (limit {timestepper.diffusion_limit:.6g})")
     if args.tracer_wall:
         for t, w in enumerate(timestepper._engine.tracer_walls() or []):
             print(f"tracer wall = tracer {t}: " + (", ".join(f"{side} {value!r}" for side, value in w.items()) or "no flux"))
@@ -915,6 +933,10 @@ def _run(args, ranks):
             integral = eng.integrate_pressure(q.dat.data)
             half_sq = timestepper.compute_diagnostics(Q, p, q)["tracer_half_sq"]
             print(f"{q.name()}: integral = {integral!r}, half square integral = {half_sq!r}")
+        print()
+    if args.tracer_diffusion == "implicit":
+        rows = np.asarray(timestepper.tracer_diffusion_iterations or [np.zeros(args.tracers)], dtype=float)
+        print("tracer diffusion iterations per solve (mean) = " + " ".join(f"{x:.1f}" for x in rows.mean(axis=0)))
         print()
     if args.tracer_wall:
         sides = ("boundary",) if args.problem == "kelvinhelmholtz" else WALL_SIDES

@@ -136,6 +136,13 @@ class IncompressibleEuler(ABC):
         self._label = label
         # tracer_diffusivity=: kappa of every tracer (a scalar or n_tracers values); None: no call at all
         self._tracer_diffusivity = engine_options.pop("tracer_diffusivity", None)
+        # tracer_diffusion=: 'explicit' (the default: no call at all) or 'implicit', the backward-Euler solve at the end of every
+        # step
+        self._tracer_diffusion = engine_options.pop("tracer_diffusion", "explicit")
+        if self._tracer_diffusion not in ("explicit", "implicit"):
+            raise ValueError(f"tracer_diffusion must be 'explicit' or 'implicit' (got {self._tracer_diffusion!r})")
+        if self._tracer_diffusion == "implicit" and self._tracer_diffusivity is None:
+            raise ValueError('tracer_diffusion="implicit" needs tracer_diffusivity=')
         # tracer_walls=: fixed-value walls of the tracers, a dict {side: value} or n_tracers of them;
         # None: no call at all
         self._tracer_walls = engine_options.pop("tracer_walls", None)
@@ -174,6 +181,7 @@ class IncompressibleEuler(ABC):
         self.particles = None  # solve(..., particles=xy): dict of the recorded particle positions
         self.step_sizes = None  # solve(..., cfl=C): one row (t, dt, A dt) per step taken
         self.step_decisions = None  # ... and one row (t, A, dt held, dt proposed) per decision of the controller
+        self.tracer_diffusion_iterations = None  # tracer_diffusion="implicit": the iteration counts of every step's solve
         self._t_adaptive = None  # the start time of the next step while an adaptive run is under way
 
     # -- engine and function spaces ------------------------------------------------------------
@@ -204,7 +212,10 @@ class IncompressibleEuler(ABC):
         if self._tracer_diffusivity is not None:
             self._engine.set_tracer_diffusivity(self._tracer_diffusivity)
             self.diffusion_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
-            warn_if_diffusion_unstable(self._engine.tracer_diffusion_number()[1], self.diffusion_limit)
+            if self._tracer_diffusion == "implicit":  # no limit to warn about: the term is solved for
+                self._engine.set_tracer_diffusion_mode("implicit")
+            else:
+                warn_if_diffusion_unstable(self._engine.tracer_diffusion_number()[1], self.diffusion_limit)
         if self._viscosity is not None:  # independent of the tracer check above
             self._engine.set_viscosity(self._viscosity, "free_slip" if self._wall is None else self._wall)
             self.viscosity_limit = explicit_stability_limit(opts["a_expl"], opts["b_expl"])
@@ -390,6 +401,11 @@ class IncompressibleEuler(ABC):
             for callback in self.callbacks:
                 callback(*self._functions(Q, p, self._callback_names), t, q_tracer=qt)
 
+    def _note_tracer_solve(self, tracer):
+        """tracer_diffusion="implicit": one row of iteration counts (n_tracers,) per step, in self.tracer_diffusion_iterations"""
+        if tracer and self.tracer_diffusion_iterations is not None:
+            self.tracer_diffusion_iterations.append(self._engine.tracer_diffusion_solve()[0])
+
     def _time(self, k):
         """The time at which step k starts: k dt at a fixed step size, the running sum of the step sizes in an adaptive run"""
         return k * self._dt if self._t_adaptive is None else self._t_adaptive
@@ -468,6 +484,7 @@ class IncompressibleEuler(ABC):
                 self._t_adaptive = t
                 with PerformanceLog("timestep"):
                     self._advance(k, f_rhs, tracer)
+                self._note_tracer_solve(tracer)
                 sizes.append((t, self._dt, A * self._dt))
                 t, k = t + self._dt, k + 1
                 self._call_back(t, tracer)
@@ -555,6 +572,7 @@ class IncompressibleEuler(ABC):
         eng = self._engine
         controller = self._step_controller(T_final, warmup, checkpoint, restart, cfl, dt_min, dt_max, adapt_every, max_steps)
         self.step_sizes = self.step_decisions = None
+        self.tracer_diffusion_iterations = [] if self._tracer_diffusion == "implicit" else None
         nt = self.get_timesteps(T_final, warmup) if controller is None else controller[1]  # adaptive: the size of the row logs
         if checkpoint is not None and int(checkpoint_every) < 0:
             raise ValueError(f"checkpoint_every must be >= 0 (got {checkpoint_every})")
@@ -582,6 +600,7 @@ class IncompressibleEuler(ABC):
         for k in (range(k0, nt) if controller is None else ()):
             with PerformanceLog("timestep"):
                 t = self._advance(k, f_rhs, tracer)
+            self._note_tracer_solve(tracer)
             if checkpoint is not None and (k + 1 == nt or (checkpoint_every and (k + 1) % int(checkpoint_every) == 0)):
                 self._write_checkpoint(checkpoint, k + 1, t)
             self._call_back(t, tracer)
