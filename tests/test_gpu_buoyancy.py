@@ -2,7 +2,9 @@
 
 Bounds.  The hook: 1e-12 max|f| -- the embedding of DG_k in DG_{k+1} is exact, what remains is the rounding of the nodal <-> modal
 conversions.  Whole steps, the rest state and the gravity wave: 2e-8, the project's whole-step bound, for Q, p and every q.
-Switched off, everything is bitwise what it is without the feature."""
+Switched off, everything is bitwise what it is without the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys

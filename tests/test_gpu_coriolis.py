@@ -1,7 +1,9 @@
 """The Coriolis term on the GPU (include/hdg_coriolis.h) against tests/coriolis_reference.py.
 
 Bounds, the project's: the hook relative 1e-10; whole steps and strips 2e-8 for Q and p; the manufactured solution's L2 error
-relative 1e-6 against the reference's.  Switched off, everything is bitwise what it is without the feature."""
+relative 1e-6 against the reference's.  Switched off, everything is bitwise what it is without the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys

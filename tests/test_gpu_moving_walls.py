@@ -3,7 +3,9 @@ tests/moving_walls_reference.py.
 
 Bounds.  The two hooks and the force budget: relative 1e-10, section 21's bound for its operator hook (table and conversion
 rounding against entries of size Lambda_u).  Whole steps, strips: 2e-8, the project's whole-step bound, for Q and p.  Switched
-off, everything is bitwise what a viscous engine computes that never heard of the feature."""
+off, everything is bitwise what a viscous engine computes that never heard of the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys

@@ -3,7 +3,9 @@
 Bounds.  The operator hook: relative 1e-10, the bound of the advection hook (tests/test_gpu_tracer.py).  Whole steps: 2e-8, the
 project's whole-step bound.  L2 errors against the analytic decay: relative 1e-6 (the rule of DESIGN.md section 3 for
 manufactured errors).  A member of a batch against the same tracer alone: 1e-12 max|q| (tests/test_gpu_multi_tracer.py).
-Switched off, everything is bitwise what it is without the feature."""
+Switched off, everything is bitwise what it is without the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys

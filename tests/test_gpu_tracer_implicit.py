@@ -3,7 +3,9 @@ tests/tracer_implicit_reference.py.
 
 Bounds.  The solve hook against the dense solve: 1e-9 max|x| at rtol 1e-12 (the CG error is at most about cond(A) rtol, and
 cond(A) <= 1 + tau rho <= 5001 here).  Iteration counts at rtol 1e-10: the reference CG's plus 10 % plus 2.  Whole steps: 2e-8,
-the project's whole-step bound.  Batches, restarts and the switched-off engine: bitwise."""
+the project's whole-step bound.  Batches, restarts and the switched-off engine: bitwise.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys

@@ -3,7 +3,9 @@
 Bounds.  The operator hook: relative 1e-10 (section 19's).  Whole steps: 2e-8, the project's whole-step bound.  L2 errors
 against the analytic decay: relative 1e-6.  A member of a batch against the same tracer alone: 1e-12 max|q|.  The flux budget:
 ten times the residual the numpy reference leaves in the same identity.  Switched off, everything is bitwise what it is
-without the feature."""
+without the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import ctypes as C
 import os
 import subprocess

@@ -2,7 +2,9 @@
 
 Bounds.  The hook: relative 1e-10 (section 19's bound for its operator hook: table and conversion rounding against entries of
 size Lambda).  Whole steps, strips: 2e-8, the project's whole-step bound, for Q and p.  The manufactured solution's L2 error:
-relative 1e-6 against the reference's.  Switched off, everything is bitwise what it is without the feature."""
+relative 1e-6 against the reference's.  Switched off, everything is bitwise what it is without the feature.
+
+Larger meshes (several waves, workgroups and XCD row bands; row padding): tests/test_gpu_stencil_sizes.py runs the hooks there."""
 import os
 import subprocess
 import sys
